@@ -74,6 +74,88 @@ PARITY_GATES = {
     "n5000_f32": "fast fp32 MFMA configuration: decisions and BLOCKS within 1e-5 on the first frame; not the parity configuration",
 }
 PX_PRODUCTS = 15  # digit products per element and 32 rows of k (csrc/kernels_pexact.hip: 5 digits, levels 0..4)
+# SyntheticSequence keeps every point in view over its whole trajectory, checked over a horizon of 100, 200, ... frames that
+# covers the run: its scene (points, map, frames) is a different one for each horizon, and past ~300 frames, with the camera
+# drifting and turning every frame, no point stays in view and there is none.  Every run uses the scene of the first horizon
+# (that of the default line and of the parity gate's sampled frames); longer runs repeat its frames (frame_plan).
+SEQ_FRAMES_MAX = 100
+DUMP_P_ROWS = 2048  # --dump-outputs: P in full up to this order, above it a seeded DUMP_P_ROWS x DUMP_P_ROWS sample (32 MB in fp64)
+DUMP_SEED = 0x5EED
+
+
+def frame_plan(warmup, steps, cap=SEQ_FRAMES_MAX):
+    """How a run walks the synthetic sequence: (frames to generate, [(w, t), ...]) -- for each pass, the state is reset to
+    the seeded map, frames [0, w) run untimed and frames [w, t) timed.  warmup + steps <= cap: one pass, warm-up then the
+    timed steps.  Longer: every pass replays the first min(warmup, cap // 2) frames untimed and times the rest of the
+    sequence, until `steps` timed steps are done; warm-up beyond that runs first, as untimed passes."""
+    if warmup + steps <= cap:
+        return warmup + steps, [(warmup, warmup + steps)]
+    w = min(warmup, cap // 2)
+    plan = []
+    for k in range(w, warmup, cap):
+        plan.append((min(cap, warmup - k),) * 2)
+    for k in range(0, steps, cap - w):
+        plan.append((w, w + min(cap - w, steps - k)))
+    return cap, plan
+
+
+def time_plan(plan, reset, step):
+    """Seconds of the timed frames of `plan` (frame_plan) for a line that steps one engine: reset() puts the seeded map back,
+    step(t) runs frame t."""
+    import torch
+
+    dt = 0.0
+    for w, t in plan:
+        reset()
+        for i in range(w):
+            step(i)
+        if t > w:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(w, t):
+                step(i)
+            torch.cuda.synchronize()
+            dt += time.perf_counter() - t0
+    return dt
+
+
+def dump_outputs(path, eng, group, ranks, sharded, info):
+    """--dump-outputs: what the timed path handed its caller after the LAST timed step -- the state (camera x13, feature
+    parameters, covariance P) and that step's EkfStepInfo counters -- as float64 .npy files under `path` (rank 0 writes).
+    P is written in full up to DUMP_P_ROWS rows; above, P_sample holds P[rows][:, rows] for a seeded, sorted choice of
+    DUMP_P_ROWS indices (P_rows, stored as float64), beside the full diagonal.  Collective on sharded runs.  The inputs are
+    the same on every run with the same arguments; the outputs are bitwise the same with --sweep-mode 1, while the default
+    persistent sweep sums its fp64 terms in arrival order, so repeated runs agree to ~1e-8 of max|P|, not bit for bit."""
+    if group is not None:
+        x, fp, P = group.get_state()
+    elif sharded:
+        # every rank fills the camera rows and its own row block of an n x n buffer; rank 0 keeps the camera rows, the
+        # others contribute only their own rows, so a sum over ranks assembles each sampled entry exactly once
+        P = np.full((eng.n, eng.n), np.nan)
+        x, fp, _ = eng.get_state(P_out=P)
+        if ranks.rank != 0:
+            P[:13] = np.nan
+        P = np.nan_to_num(P, nan=0.0)
+    else:
+        x, fp, P = eng.get_state()
+    n = P.shape[0]
+    rows = np.arange(n) if n <= DUMP_P_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_P_ROWS, replace=False))
+    sample, diag = P[np.ix_(rows, rows)], np.diagonal(P).copy()
+    if sharded and group is None:
+        import torch
+
+        for a in (sample, diag):
+            t = torch.from_numpy(a).to(ranks.device or "cpu")
+            ranks.dist.all_reduce(t, op=ranks.dist.ReduceOp.SUM)
+            a[...] = t.cpu().numpy()
+    if ranks.rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    out = {"x13": x, "feature_pos": fp, "P_diag": diag, "P_rows": rows, "P_sample": sample,
+           # the step's counters; n_sweep_retries is left out: it counts timed-out sweeps that were re-run, not results
+           "step_info": [getattr(info, f) for f, _ in info._fields_ if f != "n_sweep_retries"]}
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def measured_mfma_loop(dtype):
@@ -415,7 +497,13 @@ def main():
     ap.add_argument("--no-roofline-pass", action="store_true")
     ap.add_argument("--no-fast-line", action="store_true",
                     help="exact-configuration workloads: skip the secondary fast-fp32 line (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (x13, feature parameters, P in full "
+                         "or a seeded sample, that step's counters) as float64 DIR/<name>.npy, for comparing two builds (bitwise "
+                         "repeatable with --sweep-mode 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -437,7 +525,7 @@ def main():
         args.transport = "rccl" if (ranks.dist is None or ranks.dist.get_backend() == "nccl") else "callback"
     N, W, H, precision, dtype = WORKLOADS[args.workload]
     exact = precision in (2, 3, 4)  # the exact int8 update (fp32- or fp64-stored covariance)
-    n_frames = args.warmup + args.steps
+    n_frames, plan = frame_plan(args.warmup, args.steps)
     seq = SyntheticSequence(N, n_frames, width=W, height=H)
     sharded = args.mode == "sharded" and world > 1
     emulate = args.emulate_shards if world == 1 else 0
@@ -493,39 +581,49 @@ def main():
             e.upload_images(images)
 
     def run(timing):
-        for e in (group.engines if group else [eng]):
-            e.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, P0)
-            if ncc:
-                e.upload_image(img0)
-                e.capture_templates(np.arange(N), uv0)
-            e.timing(timing)
+        """seconds of the timed steps of `plan` and the step infos of its last pass; with `timing`, the engine's own timers
+        cover exactly the timed steps"""
+        engines = group.engines if group else [eng]
 
         def frames(e, lo, hi):
             return [(e.step_staged_image(t) if ncc else e.step_frame(t)) for t in range(lo, hi)]
 
-        if group:
-            group.run(lambda r, e: frames(e, 0, args.warmup))
-        else:
-            frames(eng, 0, args.warmup)
-        for e in (group.engines if group else [eng]):
-            e.timing_reset()
-        ranks.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        if group:
-            infos = group.run(lambda r, e: frames(e, args.warmup, n_frames))[0]
-        else:
-            infos = frames(eng, args.warmup, n_frames)
-        torch.cuda.synchronize()
-        ranks.barrier()
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        for e in (group.engines if group else [eng]):
-            e.synchronize()  # async error mode: a failed factorisation in the LAST frame's update surfaces here (raises)
+        def advance(lo, hi):
+            return group.run(lambda r, e: frames(e, lo, hi))[0] if group else frames(eng, lo, hi)
+
+        dt, infos, timed_yet = 0.0, [], False
+        for w, t in plan:
+            for e in engines:
+                e.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, P0)
+                if ncc:
+                    e.upload_image(img0)
+                    e.capture_templates(np.arange(N), uv0)
+                e.timing(timing and not timed_yet)
+            advance(0, w)
+            if t == w:
+                continue
+            for e in engines:  # the timers count from the first timed step on, and only timed steps
+                if timed_yet:
+                    e.timing(timing)
+                else:
+                    e.timing_reset()
+            timed_yet = True
+            ranks.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            infos = advance(w, t)
+            torch.cuda.synchronize()
+            ranks.barrier()
+            torch.cuda.synchronize()
+            dt += time.perf_counter() - t0
+            for e in engines:
+                e.synchronize()  # async error mode: a failed factorisation in the LAST frame's update surfaces here (raises)
         return dt, infos
 
     elapsed, infos = run(False)
     elapsed = ranks.max_over_ranks(elapsed)
+    if args.dump_outputs:  # before the roofline pass and the secondary lines reset the state
+        dump_outputs(args.dump_outputs, eng, group, ranks, sharded, infos[-1])
 
     roof, stages, roof_sweep = None, None, None
     pmc_traffic = committed_pmc_traffic(args.workload) if args.matcher == "descriptors" else (None, None, {})
@@ -654,15 +752,8 @@ def main():
         if rank == 0:  # the SAME workload on one GPU (this rank's), for the strong-scaling ratio
             e1 = engine.EkfEngine(seq.cam, seq.par, N, **kw)
             e1.upload_frames(seq.frames)
-            e1.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, seq.P0)
-            for t in range(args.warmup):
-                e1.step_frame(t)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for t in range(args.warmup, n_frames):
-                e1.step_frame(t)
-            torch.cuda.synchronize()
-            dt1 = time.perf_counter() - t0
+            dt1 = time_plan(plan, lambda: e1.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, seq.P0),
+                            e1.step_frame)
             e1.close()
             single_ref = {"value": args.steps / dt1, "unit": "EKF updates/s", "ms_per_step": 1e3 * dt1 / args.steps,
                           "note": "the same workload, steps and warm-up on ONE GPU (rank 0's), unsharded engine, measured "
@@ -720,15 +811,8 @@ def main():
     if world == 1 and not group and not ncc:
         # the same frames through ekf_step with HOST keypoints and descriptors (what a caller without staged frames pays): never `value`
         eng.timing(False)
-        eng.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, P0)
-        for t in range(args.warmup):
-            eng.step(*seq.frames[t])
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for t in range(args.warmup, n_frames):
-            eng.step(*seq.frames[t])
-        torch.cuda.synchronize()
-        dth = time.perf_counter() - t0
+        dth = time_plan(plan, lambda: eng.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, P0),
+                        lambda t: eng.step(*seq.frames[t]))
         eng.synchronize()
         kp_bytes = float(np.mean([len(k) for k, _ in seq.frames])) * (8 + eng.desc_bytes)
         out["pcie_inclusive"] = {
@@ -746,15 +830,8 @@ def main():
         ef = engine.EkfEngine(seq.cam, seq.par, N, max_keypoints=len(seq.frames[0][0]) + 64, precision=1, device=local_rank)
         ef.upload_frames(seq.frames)
         ef.set_async_errors(True)
-        ef.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, seq.P0)
-        for t in range(args.warmup):
-            ef.step_frame(t)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for t in range(args.warmup, n_frames):
-            ef.step_frame(t)
-        torch.cuda.synchronize()
-        dtf = time.perf_counter() - t0
+        dtf = time_plan(plan, lambda: ef.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, seq.P0),
+                        ef.step_frame)
         ef.synchronize()
         ef.close()
         out["fast_fp32_configuration"] = {

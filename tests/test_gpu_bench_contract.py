@@ -119,3 +119,47 @@ def test_sweep_timing_through_the_abi():
     e.timing_reset()
     assert e.sweep_timing()["panels"] == 0
     e.close()
+
+
+@pytest.mark.parametrize("steps", [3, 320])
+def test_dump_outputs_holds_the_state_of_the_last_timed_step(tmp_path, steps):
+    """--dump-outputs DIR: float64 .npy files of what the last timed step left (x13, feature parameters, P -- in full at
+    this size -- and that step's counters), under 64 MB, the same as the engine gives for the same frames stepped from the
+    seeded map; --steps sets the number of timed steps, also past the end of the synthetic sequence (320 steps: several
+    passes over its frames, each after the same 2 warm-up frames)."""
+    import numpy as np
+
+    import bench
+    from openekfmonoslam_amd import engine
+    from openekfmonoslam_amd.synth import SyntheticSequence
+
+    warmup = 2
+    n_frames, plan = bench.frame_plan(warmup, steps)
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "n200_f64", "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(d), "--no-cpu-baseline", "--no-roofline-pass"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    names = {"x13", "feature_pos", "P_diag", "P_rows", "P_sample", "step_info"}
+    assert {p.stem for p in d.iterdir()} == names and all(p.suffix == ".npy" for p in d.iterdir())
+    assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+    out = {k: np.load(d / f"{k}.npy") for k in names}
+    assert all(a.dtype == np.float64 for a in out.values())
+
+    seq = SyntheticSequence(200, n_frames)
+    e = engine.EkfEngine(seq.cam, seq.par, 200, max_keypoints=len(seq.frames[0][0]) + 64, precision=0)
+    e.set_state(seq.x13, seq.feature_pos, seq.feature_type, seq.feature_desc, seq.P0)
+    infos = [e.step(*f) for f in seq.frames[: plan[-1][1]]]  # the last pass
+    x, fp, P = e.get_state()
+    e.close()
+    n = P.shape[0]
+    np.testing.assert_array_equal(out["P_rows"], np.arange(n))
+    last = infos[-1]
+    assert list(out["step_info"]) == [last.n_predicted, last.n_matches, last.n_hypotheses, last.n_inliers, last.n_outliers,
+                                      last.n_rescued, last.status]
+    np.testing.assert_allclose(out["x13"], x, rtol=0, atol=1e-9 * np.abs(x).max())
+    np.testing.assert_allclose(out["feature_pos"], fp, rtol=0, atol=1e-9 * np.abs(fp).max())
+    np.testing.assert_allclose(out["P_sample"], P, rtol=0, atol=1e-9 * np.abs(P).max())
+    np.testing.assert_array_equal(out["P_diag"], np.diagonal(out["P_sample"]))

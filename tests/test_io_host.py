@@ -109,15 +109,6 @@ def test_config_loader_reads_the_reference_schema(io_check, tmp_path):
     assert r.returncode == 1 and "not found" in r.stdout
 
 
-def test_config_loader_on_the_reference_file_itself(io_check):
-    ref = "/root/reference/experiments/s3/config.yml"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present (GPU box)")
-    cam, par, run = _parse_config_output(subprocess.check_output([io_check, "config", ref], text=True))
-    _expect(cam, par)
-    assert run[8] == 60 and run[4] == 1
-
-
 def test_png_reader_and_writer_against_pillow(io_check, tmp_path):
     from PIL import Image
 

@@ -243,7 +243,7 @@ int ekf_get_image_level(EkfEngine *e, int level, uint8_t *out, int *width, int *
 int ekf_capture_templates(EkfEngine *e, const int32_t *feat_idx, const double *uv, int count);
 int ekf_match_ncc(EkfEngine *e, EkfMatch *matches, int *n_matches);
 int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels,
-                   EkfStepInfo *info);
+                   EkfStepInfo *info); /* (matcher: ekf_set_image_matcher) */
 /* detectNewImageFeatures(image, featuresPrediction, newImageFeaturesMaxSize, newImageFeatures)
  *                                                              EKF/DetectNewImageFeatures.cpp:337
  * on the CURRENT image, masked by the gate ellipses of the last full prediction made while an image was loaded
@@ -262,6 +262,29 @@ int ekf_images_upload(EkfEngine *e, int n_frames, const uint8_t *images, int wid
                       int channels);
 int ekf_select_staged_image(EkfEngine *e, int frame); /* build the pyramid of a staged frame */
 int ekf_step_staged_image(EkfEngine *e, int frame, EkfStepInfo *info);
+
+/* -- image in, descriptor matcher: keypoint detector + BRIEF-32 on the device ---------------------------------
+ * The reference's shipped matcher, STAR keypoints + BRIEF-32 + Hamming distance (EKF/Matching.cpp:188-210), with this
+ * build's own detector and descriptor in front of the matcher of ekf_match (no bit-parity with
+ * OpenCV's STAR or its BRIEF pattern is claimed):
+ *   keypoint   the integer corner measure of ekf_detect_new_features, R >= min_response, >= 16 px from every edge,
+ *              5x5 non-maximum suppression (strictly above the window's earlier pixels in raster order, >= the later ones);
+ *   BRIEF-32   256 tests S(c + a_i) < S(c + b_i) on the pairs of csrc/brief_pattern.h (offsets in [-19, 19]), S = sum of
+ *              the 9x9 gray box, reads clamped to the frame; test i sets bit 7 - i % 8 of byte i / 8.
+ * Keypoints are listed in raster order (y, then x) at integer pixels. */
+enum { EKF_IMAGE_MATCHER_NCC = 0, EKF_IMAGE_MATCHER_KEYPOINTS = 1 };
+/* how ekf_step_image / ekf_step_staged_image match: NCC templates (default, unchanged) or detector + BRIEF-32 + the Hamming
+ * matcher of ekf_match; KEYPOINTS needs an EKF_DESCRIPTOR_U8_HAMMING, unsharded engine (else EKF_ERR_INVALID_ARG) */
+int ekf_set_image_matcher(EkfEngine *e, int matcher, double min_response);
+/* detector + descriptors on the CURRENT image; masked = 1: inside the gates of the last full prediction, 0: whole frame.
+ * Writes min(found, capacity) keypoints in raster order; *n_found = found. kps / desc32 may be NULL (count only). */
+int ekf_detect_keypoints(EkfEngine *e, double min_response, int masked, EkfKeypoint *kps, uint8_t *desc32, int capacity,
+                         int *n_found);
+/* BRIEF-32 of the current image at the given pixels (what a new map feature keeps, AddMapFeature.cpp:317-337); the centre
+ * of (u, v) is the pixel (floor(u + 0.5), floor(v + 0.5)) */
+int ekf_describe(EkfEngine *e, const double *uv, int count, uint8_t *desc32);
+/* keypoints the last KEYPOINTS-mode image step detected and kept (kept < detected: capacity max_keypoints reached) */
+int ekf_get_step_keypoints(const EkfEngine *e, int *detected, int *kept);
 
 /* -- instrumentation ------------------------------------------------------------------------------------- */
 int ekf_timing_enable(EkfEngine *e, int on); /* HIP-event timing of stages and of the P-update kernel */

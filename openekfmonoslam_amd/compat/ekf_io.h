@@ -510,8 +510,12 @@ class ImageEKF {
 public:
     // EKF::EKF(pathConfigFile, outputPath)  EKF.cpp:124-146.  detectorThreshold: threshold of this build's corner
     // measure (the reference's detector thresholds live in the FeatureDetector section, which is OpenCV-specific).
-    ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9)
-        : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold)
+    // imageMatcher: EKF_IMAGE_MATCHER_NCC (templates, the default) or EKF_IMAGE_MATCHER_KEYPOINTS (the reference's
+    // detector + BRIEF-32 + Hamming matcher, this build's detector and descriptor; keypointThreshold = its threshold).
+    ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
+             int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
+        : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -521,6 +525,7 @@ public:
         cfg.precision = precision; cfg.device = -1;
         const int rc = ekf_engine_create(&cfg, &e_);
         if (rc != EKF_OK) throw std::runtime_error("ekf_engine_create failed (no MI355X visible?)");
+        chk(ekf_set_image_matcher(e_, imageMatcher, keypointThreshold), "ekf_set_image_matcher");
         if (!outputPath_.empty()) { // EKF.cpp:129-137: output.yml + log.txt (+ a video this build does not write)
             if (!out_.open(outputPath_ + "output.yml")) throw std::runtime_error("cannot write " + outputPath_ + "output.yml");
             log_.open((outputPath_ + "log.txt").c_str(), std::ios_base::out);
@@ -612,7 +617,8 @@ private:
     {
         if (rc != EKF_OK) throw std::runtime_error(std::string(what) + ": " + ekf_last_error(e_));
     }
-    // detectNewImageFeatures + addFeaturesToStateAndCovariance (+ templates for matcher mode B)
+    // detectNewImageFeatures + addFeaturesToStateAndCovariance (+ the BRIEF-32 descriptor each new feature keeps,
+    // AddMapFeature.cpp:317-337, with the keypoint matcher; + templates with the NCC matcher)
     void addNewFeatures(int wanted)
     {
         const int N0 = ekf_num_features(e_);
@@ -623,6 +629,12 @@ private:
         chk(ekf_detect_new_features(e_, wanted, run_.detectNewFeaturesImageAreasDivideTimes, run_.detectNewFeaturesImageMaskEllipseSize,
                                     detectorThreshold_, uv.data(), &got), "ekf_detect_new_features");
         if (got <= 0) return;
+        if (keypoints_) {
+            std::vector<uint8_t> desc((size_t)got * EKF_DESC_BYTES);
+            chk(ekf_describe(e_, uv.data(), got, desc.data()), "ekf_describe");
+            chk(ekf_add_features(e_, uv.data(), desc.data(), got), "ekf_add_features");
+            return;
+        }
         chk(ekf_add_features(e_, uv.data(), 0, got), "ekf_add_features");
         std::vector<int32_t> idx(got);
         for (int i = 0; i < got; ++i) idx[i] = N0 + i;
@@ -692,6 +704,7 @@ private:
     int steps_;
     std::string outputPath_;
     double detectorThreshold_;
+    bool keypoints_; // EKF_IMAGE_MATCHER_KEYPOINTS: new features keep a BRIEF-32 descriptor, no templates
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

@@ -136,7 +136,8 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.mt_valid,  d.mt_kp,     d.mt_dist,   d.matches,     d.msel,      d.mout,     d.match_of_feat,
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
-                    e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz};
+                    e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -1123,14 +1124,16 @@ static int upload_keypoints(EkfEngine *e, const EkfKeypoint *kps, const uint8_t 
     return EKF_OK;
 }
 
-static int match_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, int *n_matches)
+// d_nkp != nullptr: keypoints detected on the device, n_kp is their capacity and the count is read by the kernel
+static int match_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, int *n_matches,
+                     const int *d_nkp = nullptr)
 {
     // kernels read e->d.kps / kdesc; staged frames alias them in
     EkfKeypoint *save_k = e->d.kps;
     uint8_t *save_d = e->d.kdesc;
     e->d.kps = const_cast<EkfKeypoint *>(d_kps);
     e->d.kdesc = const_cast<uint8_t *>(d_desc);
-    launch_match(e, e->n_pred, n_kp);
+    launch_match(e, e->n_pred, n_kp, nullptr, false, d_nkp);
     e->d.kps = save_k;
     e->d.kdesc = save_d;
     int rc = read_counts(e);
@@ -1489,10 +1492,15 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches);
 
 static int step_dev_fast(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info);
 
+static int detect_step_keypoints(EkfEngine *e);
+
+// detect: the keypoints of this frame are detected and described on the device, into d_kps / d_desc (= d.kps / d.kdesc,
+// n_kp = their capacity), between the prediction and the matching (ekf_set_image_matcher(EKF_IMAGE_MATCHER_KEYPOINTS))
 static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info,
-                    bool use_ncc = false)
+                    bool use_ncc = false, bool detect = false)
 {
-    if (!use_ncc && !e->img.valid && !e->keep_step_preds && e->shard_world == 1) return step_dev_fast(e, d_kps, d_desc, n_kp, info);
+    if (!use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1)
+        return step_dev_fast(e, d_kps, d_desc, n_kp, info);
     EkfStepInfo li;
     std::memset(&li, 0, sizeof(li));
     int status = EKF_OK, rc;
@@ -1506,10 +1514,11 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean))) return rc; // + timesPredicted++ (EKF.cpp:572)
     li.n_predicted = np;
     tm.mark();
-    // 4. matching (:337)
+    // 4. matching (:337); keypoints from images: detector + descriptor inside the gates of this prediction (Matching.cpp:188-210)
+    if (detect && (rc = detect_step_keypoints(e))) return rc;
     int M = 0;
     if (lean) rc = match_sharded_dev(e, use_ncc, d_kps, d_desc, n_kp, &M); // every rank matches the predictions of its own features
-    else rc = use_ncc ? match_ncc_dev(e, &M) : match_dev(e, d_kps, d_desc, n_kp, &M);
+    else rc = use_ncc ? match_ncc_dev(e, &M) : match_dev(e, d_kps, d_desc, n_kp, &M, detect ? e->d.counts + CNT_KP_FOUND : nullptr);
     if (rc) return rc;
     li.n_matches = M;
     tm.mark();
@@ -1556,6 +1565,10 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     if ((rc = update_dev(e, nr, true, lean))) return rc;
     tm.mark();
     if ((rc = read_counts(e))) return rc;
+    if (detect) {
+        e->step_kp_detected = e->h_counts[CNT_KP_FOUND];
+        e->step_kp_kept = std::min(e->step_kp_detected, e->kcap);
+    }
     if ((rc = recover_failed_update(e, &status))) return rc;
     tm.finish();
     li.status = status;
@@ -1808,6 +1821,12 @@ int ekf_capture_templates(EkfEngine *e, const int32_t *feat_idx, const double *u
     return check_async(e);
 }
 
+// the detector threshold on the integer corner measure, from the double of the ABI (not NaN: the callers refuse it)
+static long long response_threshold(double min_response)
+{
+    return min_response >= 9.2e18 ? 0x7fffffffffffffffLL : (min_response <= 0 ? 0 : (long long)min_response);
+}
+
 // detectNewImageFeatures (EKF/DetectNewImageFeatures.cpp:337-367) on the current image: device = masked corner
 // candidates (kernels_detect.hip), host = the zone heuristic of searchFeaturesByZone (:171-330), with the two
 // nondeterministic choices of the reference made deterministic: zones of equal population keep their id order (qsort
@@ -1815,7 +1834,8 @@ int ekf_capture_templates(EkfEngine *e, const int32_t *feat_idx, const double *u
 int ekf_detect_new_features(EkfEngine *e, int max_new, int divide_times, double mask_ellipse_size, double min_response,
                             double *uv_out, int *count)
 {
-    if (!e || !count || max_new < 0 || divide_times < 0 || divide_times > 6 || (max_new > 0 && !uv_out)) return EKF_ERR_INVALID_ARG;
+    if (!e || !count || max_new < 0 || divide_times < 0 || divide_times > 6 || (max_new > 0 && !uv_out) || std::isnan(min_response))
+        return EKF_ERR_INVALID_ARG;
     *count = 0;
     if (!e->img.valid) {
         e->err = "new-feature detection: no image uploaded";
@@ -1850,7 +1870,7 @@ int ekf_detect_new_features(EkfEngine *e, int max_new, int divide_times, double 
 
     struct Cand { int x, y; long long r; };
     std::vector<Cand> cands;
-    const long long thr = min_response >= 9.2e18 ? 0x7fffffffffffffffLL : (min_response <= 0 ? 0 : (long long)min_response);
+    const long long thr = response_threshold(min_response);
     for (int c = 0; c < ncell; ++c)
         if (resp[c] >= 0 && resp[c] >= thr) cands.push_back(Cand{xy[2 * c], xy[2 * c + 1], resp[c]});
     if ((int)cands.size() <= max_new) { // :357-370: fewer than asked for -> all of them
@@ -1923,6 +1943,142 @@ int ekf_detect_new_features(EkfEngine *e, int max_new, int divide_times, double 
     return EKF_OK;
 }
 
+// ------------------------------------------------------------------------ keypoints + BRIEF-32 (image in, descriptor matcher)
+// scratch of the detector (one bit per pixel of the current frame) and the staging of the stage calls (det_cap entries)
+static int ensure_kp_scratch(EkfEngine *e, int det_cap)
+{
+    const size_t words = kp_rowmask_words(e->img.w[0], e->img.h[0]);
+    if (e->rowmask_cap < words) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (e->d.kp_rowmask) (void)hipFree(e->d.kp_rowmask);
+        e->d.kp_rowmask = nullptr;
+        e->rowmask_cap = 0;
+        HIPCHK(hipMalloc((void **)&e->d.kp_rowmask, words * sizeof(unsigned long long)));
+        e->rowmask_cap = words;
+    }
+    if (e->det_cap < det_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (void *p : {(void *)e->d.det_kps, (void *)e->d.det_desc, (void *)e->d.det_centres})
+            if (p) (void)hipFree(p);
+        e->d.det_kps = nullptr;
+        e->d.det_desc = nullptr;
+        e->d.det_centres = nullptr;
+        e->det_cap = 0;
+        HIPCHK(hipMalloc((void **)&e->d.det_kps, (size_t)det_cap * sizeof(EkfKeypoint)));
+        HIPCHK(hipMalloc((void **)&e->d.det_desc, (size_t)det_cap * EKF_DESC_BYTES));
+        HIPCHK(hipMalloc((void **)&e->d.det_centres, (size_t)det_cap * 2 * sizeof(int)));
+        e->det_cap = det_cap;
+    }
+    return EKF_OK;
+}
+
+// the step's keypoints: masked detection into d.kps (the first kcap in raster order), their descriptors into d.kdesc; the
+// count stays on the device (counts[CNT_KP_FOUND]) for k_match and k_brief -- no read-back
+static int detect_step_keypoints(EkfEngine *e)
+{
+    if (!e->img.valid) {
+        e->err = "keypoint matcher: no image uploaded";
+        return EKF_ERR_INVALID_ARG;
+    }
+    int rc = ensure_kp_scratch(e, 0);
+    if (rc) return rc;
+    launch_kp_detect(e, response_threshold(e->kp_min_response), true, e->d.kp_rowmask, e->d.kps, e->kcap, e->d.counts + CNT_KP_FOUND);
+    launch_brief(e, e->d.kps, nullptr, e->kcap, e->d.counts + CNT_KP_FOUND, e->d.kdesc);
+    return check_async(e);
+}
+
+static int step_image_dev(EkfEngine *e, EkfStepInfo *info)
+{
+    if (e->image_matcher == EKF_IMAGE_MATCHER_KEYPOINTS) return step_dev(e, e->d.kps, e->d.kdesc, e->kcap, info, false, true);
+    return step_dev(e, nullptr, nullptr, 0, info, true);
+}
+
+int ekf_set_image_matcher(EkfEngine *e, int matcher, double min_response)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if ((matcher != EKF_IMAGE_MATCHER_NCC && matcher != EKF_IMAGE_MATCHER_KEYPOINTS) || std::isnan(min_response)) {
+        e->err = "ekf_set_image_matcher: unknown matcher or NaN threshold";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (matcher == EKF_IMAGE_MATCHER_KEYPOINTS && e->desc_f32) {
+        e->err = "keypoint matcher: BRIEF-32 needs an EKF_DESCRIPTOR_U8_HAMMING engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (matcher == EKF_IMAGE_MATCHER_KEYPOINTS && e->shard_world > 1) {
+        e->err = "keypoint matcher: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    e->image_matcher = matcher;
+    e->kp_min_response = min_response;
+    return EKF_OK;
+}
+
+int ekf_detect_keypoints(EkfEngine *e, double min_response, int masked, EkfKeypoint *kps, uint8_t *desc32, int capacity,
+                         int *n_found)
+{
+    if (!e || !n_found || capacity < 0 || std::isnan(min_response)) return EKF_ERR_INVALID_ARG;
+    *n_found = 0;
+    if (!e->img.valid) {
+        e->err = "keypoint detection: no image uploaded";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (desc32 && e->desc_f32) {
+        e->err = "keypoint detection: BRIEF-32 descriptors need an EKF_DESCRIPTOR_U8_HAMMING engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    int rc = ensure_kp_scratch(e, std::max(capacity, 1));
+    if (rc) return rc;
+    launch_kp_detect(e, response_threshold(min_response), masked != 0, e->d.kp_rowmask, e->d.det_kps, capacity,
+                     e->d.counts + CNT_KP_FOUND);
+    if ((rc = read_counts(e))) return rc;
+    const int found = e->h_counts[CNT_KP_FOUND], n = std::min(found, capacity);
+    if (desc32 && n > 0) launch_brief(e, e->d.det_kps, nullptr, n, nullptr, e->d.det_desc);
+    if (kps && n > 0) HIPCHK(hipMemcpyAsync(kps, e->d.det_kps, (size_t)n * sizeof(EkfKeypoint), hipMemcpyDeviceToHost, e->stream));
+    if (desc32 && n > 0) HIPCHK(hipMemcpyAsync(desc32, e->d.det_desc, (size_t)n * EKF_DESC_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    *n_found = found;
+    return check_async(e);
+}
+
+int ekf_describe(EkfEngine *e, const double *uv, int count, uint8_t *desc32)
+{
+    if (!e || count < 0 || (count > 0 && (!uv || !desc32))) return EKF_ERR_INVALID_ARG;
+    if (!e->img.valid) {
+        e->err = "ekf_describe: no image uploaded";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (e->desc_f32) {
+        e->err = "ekf_describe: BRIEF-32 descriptors need an EKF_DESCRIPTOR_U8_HAMMING engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (count == 0) return EKF_OK;
+    std::vector<int> c(2 * (size_t)count);
+    for (size_t i = 0; i < c.size(); ++i) {
+        if (!(std::fabs(uv[i]) <= 1.0e7)) { // also NaN
+            e->err = "ekf_describe: pixel position not finite or out of range";
+            return EKF_ERR_INVALID_ARG;
+        }
+        c[i] = (int)std::floor(uv[i] + 0.5);
+    }
+    HIPCHK(hipSetDevice(e->device));
+    int rc = ensure_kp_scratch(e, count);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(e->d.det_centres, c.data(), c.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    launch_brief(e, nullptr, e->d.det_centres, count, nullptr, e->d.det_desc);
+    HIPCHK(hipMemcpyAsync(desc32, e->d.det_desc, (size_t)count * EKF_DESC_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return check_async(e);
+}
+
+int ekf_get_step_keypoints(const EkfEngine *e, int *detected, int *kept)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (detected) *detected = e->step_kp_detected;
+    if (kept) *kept = e->step_kp_kept;
+    return EKF_OK;
+}
+
 static int match_ncc_dev(EkfEngine *e, int *n_matches)
 {
     if (!e->img.valid) {
@@ -1952,7 +2108,7 @@ int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, in
 {
     int rc = ekf_image_upload(e, image, width, height, stride, channels);
     if (rc) return rc;
-    return step_dev(e, nullptr, nullptr, 0, info, true);
+    return step_image_dev(e, info);
 }
 
 int ekf_images_upload(EkfEngine *e, int n_frames, const uint8_t *images, int width, int height, int stride, int channels)
@@ -2018,7 +2174,7 @@ int ekf_step_staged_image(EkfEngine *e, int frame, EkfStepInfo *info)
     HIPCHK(hipSetDevice(e->device));
     int rc = staged_pyramid(e, frame);
     if (rc) return rc;
-    return step_dev(e, nullptr, nullptr, 0, info, true);
+    return step_image_dev(e, info);
 }
 
 // -------------------------------------------------------------------------------------------------- timing

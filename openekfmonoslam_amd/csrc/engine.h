@@ -52,7 +52,7 @@ enum {
     CNT_RS_NEXT,      // RANSAC: next hypothesis to examine
     CNT_RS_DONE,      // RANSAC: loop finished
     CNT_NRESC,        // rescued count
-    CNT_AUX0,         // (free)
+    CNT_KP_FOUND,     // keypoints the detector found in the current image (k_kp_compact)
     CNT_AUX1,
     CNT_SHARD0,       // sharded filter: CNT_SHARD0 + r = first entry of a feature-sorted match list that rank r owns
                       // (r = 0 .. world, at most 16 ranks: slots 12 .. 28; k_shard_bounds)
@@ -104,6 +104,10 @@ struct DeviceArrays {
     EkfKeypoint *mt_xy = nullptr; // NCC matcher: matched pixel per prediction slot
     uint8_t *tmpl = nullptr;      // NCC matcher: 3 levels x 121 bytes per feature
     double *gates = nullptr;      // new-feature detector: gate + centre + radius (8 doubles) per prediction of the last full prediction
+    unsigned long long *kp_rowmask = nullptr; // keypoint detector: one bit per pixel of the frame, 64-pixel row segments
+    EkfKeypoint *det_kps = nullptr;  // ekf_detect_keypoints / ekf_describe: output staging (det_cap entries)
+    uint8_t *det_desc = nullptr;
+    int *det_centres = nullptr;      // ekf_describe: integer centres
     long long *cell_resp = nullptr; // detector: best response per 16x16 cell
     int *cell_xy = nullptr;         // detector: its pixel
     EkfMatch *matches = nullptr; // compacted matches (prediction order) / uploaded matches
@@ -256,6 +260,11 @@ struct EkfEngine {
     bool keep_step_preds = false; // snapshot every full prediction for ekf_get_step_predictions
     int n_step_preds = 0;
     int cells_cap = 0;        // detector cell buffers allocated for this many cells
+    int image_matcher = EKF_IMAGE_MATCHER_NCC; // ekf_set_image_matcher: how image steps match
+    double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
+    int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
+    size_t rowmask_cap = 0;   // words of d.kp_rowmask
+    int det_cap = 0;          // entries of d.det_kps / det_desc / det_centres
     int n_kp = 0;
     long long pu_tilemap_nt = -1;
     std::map<long long, std::pair<void *, int>> pu_tables; // built work lists of the downdate: key -> (device list, units per XCD)
@@ -364,8 +373,9 @@ bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool sta
 bool launch_predict_with_features(EkfEngine *e, int count); // step path: prepare, then covariance strips + all features in one launch
 // d_count != nullptr: n_list is an upper bound, the list's length is read on the device
 void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false);
-// d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device
-void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred = nullptr, bool with_ransac_init = false);
+// d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device; d_nkp likewise for n_kp
+void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred = nullptr, bool with_ransac_init = false,
+                  const int *d_nkp = nullptr);
 // d_M != nullptr (RANSAC launchers): M is an upper bound, the number of matches is read on the device
 void launch_match_index(EkfEngine *e, int M, const int *d_M = nullptr);
 // sharded filter: per-rank boundaries of a feature-sorted match list -> counts[CNT_SHARD0 ..]
@@ -401,6 +411,12 @@ void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int 
 void launch_match_ncc(EkfEngine *e, int n_pred);
 void launch_gate_snapshot(EkfEngine *e, int n_pred);
 void launch_detect_cells(EkfEngine *e, int n_gates, int cells_x, int cells_y, long long *d_resp, int *d_xy);
+// keypoints of the current image (kernels_detect.hip): the first `cap` in raster order -> out, all of them -> *d_found;
+// masked: inside the gates of the last full prediction.  rowmask: kp_rowmask_words(w, h) words of scratch
+void launch_kp_detect(EkfEngine *e, long long thr, bool masked, unsigned long long *rowmask, EkfKeypoint *out, int cap, int *d_found);
+size_t kp_rowmask_words(int w, int h);
+// BRIEF-32 of the keypoints' pixels (centres == nullptr) or of integer centres; d_n != nullptr: n is a bound, count on the device
+void launch_brief(EkfEngine *e, const EkfKeypoint *kps, const int *centres, int n, const int *d_n, uint8_t *desc);
 void launch_publish_counts(EkfEngine *e, int *d_mirror, int seq);
 // The same publication from inside a kernel that ends a stage (saves the separate launch): called by EVERY thread of a
 // block after the block's last write to `counts`; lanes 0..15 copy the counters to the GPU-writable host page, lane 0

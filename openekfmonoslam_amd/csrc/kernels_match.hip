@@ -13,10 +13,11 @@ namespace ekf {
 __global__ void __launch_bounds__(256)
 k_match(const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *feat_desc,
         const EkfKeypoint *kps, const uint8_t *kdesc, int n_kp, double coef, int *mt_valid, int *mt_kp,
-        float *mt_dist, int desc_bytes, int desc_f32, const int *d_npred, int slot0)
+        float *mt_dist, int desc_bytes, int desc_f32, const int *d_npred, int slot0, const int *d_nkp)
 {
     // slot0: first prediction slot of this launch (a rank of a sharded filter matches the predictions of ITS features only)
     if (d_npred && slot0 + (int)blockIdx.x >= *d_npred) return; // grid = upper bound, count on the device
+    if (d_nkp) n_kp = min(*d_nkp, n_kp); // keypoints detected on the device: n_kp = the capacity, the count is read here
     __shared__ Gate g;
     __shared__ uint32_t qd[1024]; // the map feature's descriptor: 8 words (CV_8U) or up to 1024 floats (CV_32F)
     constexpr int PASS = 8; // keypoints per thread and pass: their loads are in flight together, one barrier pair per pass
@@ -169,7 +170,7 @@ k_match_compact(const int *plist, int n_pred, const int *mt_valid, const int *mt
     if (tid == 1023) *out_count = total;
 }
 
-void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred, bool with_ransac_init)
+void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred, bool with_ransac_init, const int *d_nkp)
 {
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
@@ -178,7 +179,8 @@ void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred, bool w
     }
     k_match<<<n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, e->d.kps,
                                            e->d.kdesc, n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
-                                           e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, d_npred, 0);
+                                           e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, d_npred, 0,
+                                           d_nkp);
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
                                                e->d.kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
                                                with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N);
@@ -193,7 +195,7 @@ void launch_match_slots(EkfEngine *e, int n_kp, int s_lo, int s_hi)
     if (s_hi <= s_lo) return;
     k_match<<<s_hi - s_lo, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, e->d.kps, e->d.kdesc, n_kp,
                                                 e->cfg.par.matchingCompCoefSecondBestVSFirst, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
-                                                e->desc_bytes, e->desc_f32 ? 1 : 0, nullptr, s_lo);
+                                                e->desc_bytes, e->desc_f32 ? 1 : 0, nullptr, s_lo, nullptr);
 }
 
 void launch_match_compact(EkfEngine *e, int n_pred)

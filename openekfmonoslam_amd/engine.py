@@ -17,6 +17,7 @@ from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MATCH_DTYPE, PREDICTION_DTYPE
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
 PRECISION_F64, PRECISION_F32, PRECISION_F32_EXACT, PRECISION_F64_EXACT, PRECISION_AUTO = 0, 1, 2, 3, 4
+IMAGE_MATCHER_NCC, IMAGE_MATCHER_KEYPOINTS = 0, 1
 
 
 class EkfEngineConfig(C.Structure):
@@ -96,6 +97,10 @@ ABI = {
     "ekf_images_upload": (_i, [_vp, _i, _vp, _i, _i, _i, _i]),
     "ekf_select_staged_image": (_i, [_vp, _i]),
     "ekf_step_staged_image": (_i, [_vp, _i, C.POINTER(EkfStepInfo)]),
+    "ekf_set_image_matcher": (_i, [_vp, _i, C.c_double]),
+    "ekf_detect_keypoints": (_i, [_vp, C.c_double, _i, _vp, _vp, _i, C.POINTER(_i)]),
+    "ekf_describe": (_i, [_vp, _vp, _i, _vp]),
+    "ekf_get_step_keypoints": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_timing_enable": (_i, [_vp, _i]),
     "ekf_timing_reset": (_i, [_vp]),
     "ekf_timing_get": (_i, [_vp, C.POINTER(EkfStageTimes)]),
@@ -505,6 +510,40 @@ class EkfEngine:
         self._chk(self.L.ekf_detect_new_features(self.h, int(max_new), int(divide_times), float(mask_ellipse_size),
                                                  float(min_response), _p(out), C.byref(n)))
         return out[: n.value].copy()
+
+    # ---- image in, descriptor matcher (keypoint detector + BRIEF-32 on the device)
+    def set_image_matcher(self, matcher, min_response=1e9):
+        """IMAGE_MATCHER_NCC (default) or IMAGE_MATCHER_KEYPOINTS for step_image / step_staged_image; min_response =
+        threshold of the keypoint detector on the integer corner measure"""
+        self._chk(self.L.ekf_set_image_matcher(self.h, int(matcher), float(min_response)))
+
+    def detect_keypoints(self, min_response=1e9, masked=False, capacity=None, descriptors=True):
+        """keypoints of the current image in raster order -> (KEYPOINT_DTYPE [k], uint8 [k, 32]) with k = min(found,
+        capacity); masked: only inside the gates of the last full prediction.  Also sets self.last_found."""
+        n = _i(0)
+        if capacity is None:
+            self._chk(self.L.ekf_detect_keypoints(self.h, float(min_response), int(bool(masked)), None, None, 0, C.byref(n)))
+            capacity = n.value
+        kps = np.zeros(max(int(capacity), 1), dtype=KEYPOINT_DTYPE)
+        desc = np.zeros((max(int(capacity), 1), DESC_BYTES), dtype=np.uint8)
+        self._chk(self.L.ekf_detect_keypoints(self.h, float(min_response), int(bool(masked)), _p(kps),
+                                              _p(desc) if descriptors else None, int(capacity), C.byref(n)))
+        self.last_found = n.value
+        k = min(n.value, int(capacity))
+        return kps[:k].copy(), desc[:k].copy()
+
+    def describe(self, uv):
+        """BRIEF-32 of the current image at pixel positions uv [k, 2] (centre: floor(u + 0.5), floor(v + 0.5)) -> [k, 32] u8"""
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros((max(len(uv), 1), DESC_BYTES), dtype=np.uint8)
+        self._chk(self.L.ekf_describe(self.h, _p(uv), len(uv), _p(out)))
+        return out[: len(uv)].copy()
+
+    def step_keypoints(self):
+        """(detected, kept) keypoints of the last KEYPOINTS-mode image step"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_step_keypoints(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def upload_images(self, images):
         arr = np.ascontiguousarray(np.stack(images), dtype=np.uint8)

@@ -1128,14 +1128,7 @@ static int upload_keypoints(EkfEngine *e, const EkfKeypoint *kps, const uint8_t 
 static int match_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, int *n_matches,
                      const int *d_nkp = nullptr)
 {
-    // kernels read e->d.kps / kdesc; staged frames alias them in
-    EkfKeypoint *save_k = e->d.kps;
-    uint8_t *save_d = e->d.kdesc;
-    e->d.kps = const_cast<EkfKeypoint *>(d_kps);
-    e->d.kdesc = const_cast<uint8_t *>(d_desc);
-    launch_match(e, e->n_pred, n_kp, nullptr, false, d_nkp);
-    e->d.kps = save_k;
-    e->d.kdesc = save_d;
+    launch_match(e, d_kps, d_desc, e->n_pred, n_kp, nullptr, false, d_nkp);
     int rc = read_counts(e);
     if (rc) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
@@ -1158,16 +1151,10 @@ static int match_sharded_dev(EkfEngine *e, bool use_ncc, const EkfKeypoint *d_kp
         e->err = "NCC matcher: no image uploaded";
         return EKF_ERR_INVALID_ARG;
     }
-    EkfKeypoint *save_k = e->d.kps;
-    uint8_t *save_d = e->d.kdesc;
-    if (!use_ncc) { // kernels read e->d.kps / kdesc; staged frames alias them in
-        e->d.kps = const_cast<EkfKeypoint *>(d_kps);
-        e->d.kdesc = const_cast<uint8_t *>(d_desc);
-    }
     int rc = EKF_OK;
     if (np > 0) {
         if (use_ncc) launch_match_ncc_slots(e, e->slot_rb[me], e->slot_rb[me + 1]);
-        else launch_match_slots(e, n_kp, e->slot_rb[me], e->slot_rb[me + 1]);
+        else launch_match_slots(e, d_kps, d_desc, n_kp, e->slot_rb[me], e->slot_rb[me + 1]);
         rc = exchange_rows(e, EKF_XCHG_MATCH_VALID, e->d.mt_valid, sizeof(int), e->slot_rb, "the match flags");
         if (!rc) rc = use_ncc ? exchange_rows(e, EKF_XCHG_MATCH_XY, e->d.mt_xy, sizeof(EkfKeypoint), e->slot_rb, "the matched pixels")
                               : exchange_rows(e, EKF_XCHG_MATCH_KP, e->d.mt_kp, sizeof(int), e->slot_rb, "the matched keypoint indices");
@@ -1177,10 +1164,8 @@ static int match_sharded_dev(EkfEngine *e, bool use_ncc, const EkfKeypoint *d_kp
         if (use_ncc) {
             if (np > 0) launch_match_compact_slots(e, np, e->d.mt_xy);
             else HIPCHK(hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream));
-        } else launch_match_compact(e, np);
+        } else launch_match_compact(e, d_kps, np);
     }
-    e->d.kps = save_k;
-    e->d.kdesc = save_d;
     if (rc) return rc;
     if ((rc = read_counts(e))) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
@@ -1324,9 +1309,11 @@ static int update_dev(EkfEngine *e, int M, bool update_cov, bool lean = false)
 // is still in d.msel -- runs again on the launch-per-panel sweep, which has no cross-workgroup waits, from the untouched P
 // (S, nu and the gathered rows are formed again); *status stays EKF_OK when that succeeds and the engine counts the retry.
 // Anything else (S not positive definite) goes to *status: that update is skipped, as the reference skips it (cv::invert
-// returns zeros, K = 0: EKF/Update.cpp:101-108).  Returns a hard error (HIP, exchange) or EKF_OK.
+// returns zeros, K = 0: EKF/Update.cpp:101-108).  Returns a hard error (HIP, exchange) or EKF_OK.  Called right after a read-back,
+// so a step's unread flag (err_unread) has been read and is handled here.
 static int recover_failed_update(EkfEngine *e, int *status)
 {
+    e->err_unread = false;
     const int code = e->h_counts[CNT_ERR];
     if (!code) return EKF_OK;
     HIPCHK(hipMemsetAsync(e->d.counts + CNT_ERR, 0, sizeof(int), e->stream));
@@ -1402,10 +1389,7 @@ int ekf_rescue(EkfEngine *e, const EkfMatch *outliers, int M, uint8_t *rescued_m
     if (M == 0) return EKF_OK;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d.mout, outliers, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
-    EkfMatch *save = e->d.matches;
-    e->d.matches = e->d.mout;
-    launch_rescue(e, M);
-    e->d.matches = save;
+    launch_rescue(e, e->d.mout, M);
     HIPCHK(hipMemcpyAsync(rescued_mask, e->d.mask, (size_t)M, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return check_async(e);
@@ -1487,45 +1471,93 @@ struct StageTimer {
     }
 };
 
-// EKF::step (EKF.cpp:242-556) with keypoints already on the device
 static int match_ncc_dev(EkfEngine *e, int *n_matches);
-
-static int step_dev_fast(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info);
 
 static int detect_step_keypoints(EkfEngine *e);
 
-// detect: the keypoints of this frame are detected and described on the device, into d_kps / d_desc (= d.kps / d.kdesc,
-// n_kp = their capacity), between the prediction and the matching (ekf_set_image_matcher(EKF_IMAGE_MATCHER_KEYPOINTS))
+// EKF::step (EKF.cpp:242-556) with keypoints already on the device.  detect: the keypoints of this frame are detected and
+// described on the device, into d_kps / d_desc (= d.kps / d.kdesc, n_kp = their capacity), between the prediction and the
+// matching (ekf_set_image_matcher(EKF_IMAGE_MATCHER_KEYPOINTS)).
+//
+// Device counts (descriptor matcher on host-detected keypoints, no image loaded, no kept predictions, one GPU): how many
+// features were predicted, how many matches there are and how many outliers were re-predicted only decide launch sizes, so the
+// launches use upper bounds (N, N, the outlier count) and the kernels read the counts on the device.  What the host still needs
+// to know -- the RANSAC result (loop state and inlier count: the size of the first update), the rescued count (the size of the
+// second), the error flag -- comes from three read-backs instead of six (two with ekf_set_async_errors); each one idles the GPU
+// for ~10-15 us.  Every other step reads the counts back after each stage, because the host sizes or records launches by them:
+// with an image loaded the prediction's gates are snapshotted for the detectors (n_gates), kept predictions are packed for
+// ekf_get_step_predictions, the NCC matcher is launched per prediction, and a sharded engine divides predictions, matches and
+// updates between the ranks by owner.
 static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info,
                     bool use_ncc = false, bool detect = false)
 {
-    if (!use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1)
-        return step_dev_fast(e, d_kps, d_desc, n_kp, info);
+    const bool dev_counts = !use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1;
+    const bool lean = e->shard_world > 1; // sharded: rows of H.P travel when consumed, not after every prediction
+    int *cnt = e->d.counts;
     EkfStepInfo li;
     std::memset(&li, 0, sizeof(li));
     int status = EKF_OK, rc;
     const int retries0 = e->sweep_retries;
+    // A failed update is seen at the next read-back; until then everything enqueued behind it has left the filter alone
+    // (filter_frozen, engine.h).  The previous step's last update can still be unread (err_unread, ekf_set_async_errors): a
+    // device-count step sees it at its first read-back, after its own prediction ran frozen, and starts again (below); a
+    // host-count step reads it before it launches anything.  Either way that update runs again or is skipped and reported here.
+    if (!dev_counts && e->err_unread) {
+        if ((rc = read_counts(e))) return rc;
+        if ((rc = recover_failed_update(e, &status))) return rc;
+    }
+    bool restarted = false;
+restart:
     StageTimer tm(e);
     tm.mark();
-    // 1-2. prediction (:273-284)
-    launch_predict(e);
+    // 1-2. prediction (:273-284), timesPredicted++ (EKF.cpp:572)
     int np = 0;
-    const bool lean = e->shard_world > 1; // sharded: rows of H.P travel when consumed, not after every prediction
-    if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean))) return rc; // + timesPredicted++ (EKF.cpp:572)
-    li.n_predicted = np;
+    if (dev_counts) { // covariance strips and pixel predictions in one launch; with more than 256 features the compaction of
+                      // the predicted list rides in the launch of the H P rows
+        const bool deferred = launch_predict_with_features(e, e->N);
+        launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred);
+    } else {
+        launch_predict(e);
+        if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean))) return rc;
+    }
     tm.mark();
     // 4. matching (:337); keypoints from images: detector + descriptor inside the gates of this prediction (Matching.cpp:188-210)
-    if (detect && (rc = detect_step_keypoints(e))) return rc;
     int M = 0;
-    if (lean) rc = match_sharded_dev(e, use_ncc, d_kps, d_desc, n_kp, &M); // every rank matches the predictions of its own features
-    else rc = use_ncc ? match_ncc_dev(e, &M) : match_dev(e, d_kps, d_desc, n_kp, &M, detect ? e->d.counts + CNT_KP_FOUND : nullptr);
-    if (rc) return rc;
-    li.n_matches = M;
+    if (dev_counts) {
+        launch_match(e, d_kps, d_desc, e->N, n_kp, cnt + CNT_NPRED, true); // + the RANSAC loop state and the feature -> match index
+    } else {
+        if (detect && (rc = detect_step_keypoints(e))) return rc;
+        if (lean) rc = match_sharded_dev(e, use_ncc, d_kps, d_desc, n_kp, &M); // every rank matches the predictions of its own features
+        else rc = use_ncc ? match_ncc_dev(e, &M) : match_dev(e, d_kps, d_desc, n_kp, &M, detect ? cnt + CNT_KP_FOUND : nullptr);
+        if (rc) return rc;
+    }
     tm.mark();
     // 6. 1-point RANSAC (:402); predictions/Jacobians are looked up by featureIndex (:368-392)
+    if (dev_counts) { // the first batch is launched before anything is known on the host
+        const int batch = e->cfg.ransac_batch;
+        const int seq_r = next_publish_seq(e);
+        launch_ransac_batch(e, e->N, 0, batch, cnt + CNT_NMATCH, seq_r);
+        if ((rc = wait_counts(e, seq_r))) return rc;
+        if (e->h_counts[CNT_ERR] && !restarted) {
+            // the previous step's last update failed and its final read-back was skipped: this step's prediction did not touch
+            // the filter -- recover (that update again, or skipped and reported here), then this step from its start
+            if ((rc = recover_failed_update(e, &status))) return rc;
+            restarted = true;
+            goto restart;
+        }
+        np = e->n_pred = e->h_counts[CNT_NPRED];
+        M = e->h_counts[CNT_NMATCH];
+        for (int h0 = batch, nb = batch * RANSAC_WIDE_FACTOR; !e->h_counts[CNT_RS_DONE] && h0 < M; h0 += nb) {
+            launch_ransac_batch(e, M, h0, nb); // (wide batches behind the first: see ransac_dev)
+            if ((rc = read_counts(e))) return rc;
+        }
+    } else if (M > 0 && (rc = ransac_dev(e, M, lean))) {
+        return rc;
+    }
+    li.n_predicted = np;
+    li.n_matches = M;
     int ni = 0, no = 0;
     if (M > 0) {
-        if ((rc = ransac_dev(e, M, lean))) return rc;
         li.n_hypotheses = e->h_counts[CNT_RS_NEXT];
         ni = e->h_counts[CNT_RS_BEST];
         no = M - ni;
@@ -1538,23 +1570,33 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     // 7. low-innovation update (:430)
     if ((rc = update_dev(e, ni, true, lean))) return rc;
     tm.mark();
-    // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506)
+    // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
+    // (EKF.cpp:552-556).  An outlier that is not re-predicted has pred_vis = 0 and is not rescued.
     int nr = 0;
     if (no > 0) {
         int nop = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
-            if ((rc = predict_measurements_dev(e, e->d.work_idx, no, &nop, false, lean))) return rc;
+            if (dev_counts) {
+                launch_predict_features(e, e->d.work_idx, no, false);
+                launch_hp_rows(e, e->d.plist_sub, no, false, cnt + CNT_NPRED_SUB);
+                const int seq_p = next_publish_seq(e);
+                // rescueOutliers (EKF.cpp:84-97) and the partition it feeds in one launch
+                launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc, nullptr, seq_p, true);
+                rc = wait_counts(e, seq_p);
+            } else {
+                rc = predict_measurements_dev(e, e->d.work_idx, no, &nop, false, lean);
+            }
+            if (rc) return rc;
             if (!e->h_counts[CNT_ERR]) break;
-            // the first update failed (seen at this stage's read-back; everything behind it was frozen): run it again or skip it
-            // (recover_failed_update), then this stage again
+            // the first update failed (seen at this stage's read-back; everything behind it was frozen, a fused partition did
+            // nothing and the inliers are still in d.msel): run it again or skip it (recover_failed_update), then this stage again
             if ((rc = recover_failed_update(e, &status))) return rc;
         }
-        if (nop > 0) {
-            EkfMatch *save = e->d.matches;
-            e->d.matches = e->d.mout;
-            launch_rescue(e, no);
-            e->d.matches = save;
-            launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, e->d.counts + CNT_NRESC, true, d_desc); // rescued matches join the inliers (EKF.cpp:552-556)
+        if (dev_counts) {
+            nr = e->h_counts[CNT_NRESC];
+        } else if (nop > 0) {
+            launch_rescue(e, e->d.mout, no);
+            launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc);
             if ((rc = read_counts(e))) return rc;
             nr = e->h_counts[CNT_NRESC];
         }
@@ -1564,117 +1606,14 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     // 10. high-innovation update (:529-532)
     if ((rc = update_dev(e, nr, true, lean))) return rc;
     tm.mark();
-    if ((rc = read_counts(e))) return rc;
-    if (detect) {
-        e->step_kp_detected = e->h_counts[CNT_KP_FOUND];
-        e->step_kp_kept = std::min(e->step_kp_detected, e->kcap);
-    }
-    if ((rc = recover_failed_update(e, &status))) return rc;
-    tm.finish();
-    li.status = status;
-    li.n_sweep_retries = e->sweep_retries - retries0;
-    if (info) *info = li;
-    return status;
-}
-
-// EKF::step for the common case (descriptor matcher, whole filter on this GPU, nothing asked to be kept for the host)
-// with HALF the host round trips of step_dev: how many features were predicted, how many matches there are and how many
-// outliers were re-predicted only decide launch sizes, so the launches use upper bounds (N, N, the outlier count) and
-// the kernels read the counts on the device.  What the host still needs to know -- the RANSAC result (loop state and
-// inlier count: the size of the first update), the rescued count (the size of the second), the error flag -- comes from
-// three read-backs instead of six (two with ekf_set_async_errors); each one used to idle the GPU for ~10-15 us.
-static int step_dev_fast(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info)
-{
-    EkfStepInfo li;
-    std::memset(&li, 0, sizeof(li));
-    int status = EKF_OK, rc;
-    const int retries0 = e->sweep_retries;
-    const int N = e->N;
-    int *cnt = e->d.counts;
-    // A failed update is seen at the next read-back; until then everything enqueued behind it has left the filter alone
-    // (filter_frozen, engine.h), so whatever ran meanwhile is simply run again after recover_failed_update.
-    bool restarted = false;
-restart:
-    StageTimer tm(e);
-    tm.mark();
-    // 1-2. prediction (:273-284), timesPredicted++ (EKF.cpp:572)
-    {   // covariance strips and pixel predictions in one launch; with more than 256 features the compaction of the predicted list
-        // rides in the launch of the H P rows
-        const bool deferred = launch_predict_with_features(e, N);
-        launch_hp_rows(e, e->d.plist, N, true, cnt + CNT_NPRED, deferred);
-    }
-    tm.mark();
-    // 4. matching (:337)
-    {
-        EkfKeypoint *save_k = e->d.kps;
-        uint8_t *save_d = e->d.kdesc;
-        e->d.kps = const_cast<EkfKeypoint *>(d_kps);
-        e->d.kdesc = const_cast<uint8_t *>(d_desc);
-        launch_match(e, N, n_kp, cnt + CNT_NPRED, true); // + the RANSAC loop state and the feature -> match index (same launch)
-        e->d.kps = save_k;
-        e->d.kdesc = save_d;
-    }
-    tm.mark();
-    // 6. 1-point RANSAC (:402): the first batch is launched before anything is known on the host
-    const int batch = e->cfg.ransac_batch;
-    const int seq_r = next_publish_seq(e);
-    launch_ransac_batch(e, N, 0, batch, cnt + CNT_NMATCH, seq_r);
-    if ((rc = wait_counts(e, seq_r))) return rc;
-    if (e->h_counts[CNT_ERR] && !restarted) {
-        // the previous step's last update failed and its final read-back was skipped (ekf_set_async_errors): this step's prediction
-        // did not touch the filter -- recover (that update again, or skipped and reported here), then this step from its start
-        if ((rc = recover_failed_update(e, &status))) return rc;
-        restarted = true;
-        goto restart;
-    }
-    const int np = e->h_counts[CNT_NPRED], M = e->h_counts[CNT_NMATCH];
-    e->n_pred = np;
-    li.n_predicted = np;
-    li.n_matches = M;
-    for (int h0 = batch, nb = batch * RANSAC_WIDE_FACTOR; !e->h_counts[CNT_RS_DONE] && h0 < M; h0 += nb) {
-        launch_ransac_batch(e, M, h0, nb); // (wide batches behind the first: see ransac_dev)
+    if (dev_counts && e->async_errors) {
+        e->err_unread = true; // reported by the next step, ekf_synchronize or ekf_get_state
+    } else {
         if ((rc = read_counts(e))) return rc;
-    }
-    int ni = 0, no = 0;
-    if (M > 0) {
-        li.n_hypotheses = e->h_counts[CNT_RS_NEXT];
-        ni = e->h_counts[CNT_RS_BEST];
-        no = M - ni;
-        // + updateMapFeatures for the low-innovation inliers (MapManagement.cpp:88-113), same launch
-        launch_partition(e, e->d.matches, M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx);
-    }
-    li.n_inliers = ni;
-    li.n_outliers = no;
-    tm.mark();
-    // 7. low-innovation update (:430)
-    if ((rc = update_dev(e, ni, true))) return rc;
-    tm.mark();
-    // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506).  An outlier that is not
-    // re-predicted has pred_vis = 0 and is not rescued; with none re-predicted nothing is (the reference's case is
-    // undefined behaviour, see step_dev).
-    int nr = 0;
-    if (no > 0) {
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            launch_predict_features(e, e->d.work_idx, no, false);
-            launch_hp_rows(e, e->d.plist_sub, no, false, cnt + CNT_NPRED_SUB);
-            const int seq_p = next_publish_seq(e);
-            // rescueOutliers (EKF.cpp:84-97) and the partition it feeds in one launch: rescued matches join the inliers (EKF.cpp:552-556)
-            launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc, nullptr, seq_p, true);
-            if ((rc = wait_counts(e, seq_p))) return rc;
-            if (!e->h_counts[CNT_ERR]) break;
-            // the first update failed: the partition above did nothing (the inliers are still in d.msel); that update again or
-            // skipped, then this stage again
-            if ((rc = recover_failed_update(e, &status))) return rc;
+        if (detect) {
+            e->step_kp_detected = e->h_counts[CNT_KP_FOUND];
+            e->step_kp_kept = std::min(e->step_kp_detected, e->kcap);
         }
-        nr = e->h_counts[CNT_NRESC];
-    }
-    li.n_rescued = nr;
-    tm.mark();
-    // 10. high-innovation update (:529-532)
-    if ((rc = update_dev(e, nr, true))) return rc;
-    tm.mark();
-    if (!e->async_errors) {
-        if ((rc = read_counts(e))) return rc;
         if ((rc = recover_failed_update(e, &status))) return rc;
     }
     tm.finish();

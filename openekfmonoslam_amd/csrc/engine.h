@@ -254,6 +254,7 @@ struct EkfEngine {
     bool last_update_persist = false;     // that update's sweep was the persistent launch
     int ps_cap[2] = {0, 0};    // resident workgroups of k_chol_persist<false / true> on this device (0: not asked yet, -1: unusable)
     bool async_errors = false; // ekf_set_async_errors: no read-back at the end of a step
+    bool err_unread = false;   // the last step returned without reading the error flag back (cleared by recover_failed_update)
     bool p_exact_sym = false; // P known to be bitwise symmetric (engine-maintained invariant)
     int n_pred = 0;           // predictions of the last full prediction
     int n_gates = 0;          // gates snapshotted for the new-feature detector
@@ -373,18 +374,19 @@ bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool sta
 bool launch_predict_with_features(EkfEngine *e, int count); // step path: prepare, then covariance strips + all features in one launch
 // d_count != nullptr: n_list is an upper bound, the list's length is read on the device
 void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false);
-// d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device; d_nkp likewise for n_kp
-void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred = nullptr, bool with_ransac_init = false,
-                  const int *d_nkp = nullptr);
+// keypoints kps / kdesc; d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device; d_nkp
+// likewise for n_kp
+void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_pred, int n_kp, const int *d_npred = nullptr,
+                  bool with_ransac_init = false, const int *d_nkp = nullptr);
 // d_M != nullptr (RANSAC launchers): M is an upper bound, the number of matches is read on the device
 void launch_match_index(EkfEngine *e, int M, const int *d_M = nullptr);
 // sharded filter: per-rank boundaries of a feature-sorted match list -> counts[CNT_SHARD0 ..]
 void launch_shard_bounds(EkfEngine *e, const EkfMatch *list, int count);
 void launch_shard_bounds_idx(EkfEngine *e, const int *list, const int *d_count); // ... of a feature-index list whose length is on the device
 // sharded filter: matching and RANSAC hypotheses divided by feature ownership (kernels_match.hip, kernels_ncc.hip, kernels_ransac.hip)
-void launch_match_slots(EkfEngine *e, int n_kp, int s_lo, int s_hi);
+void launch_match_slots(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_kp, int s_lo, int s_hi);
 void launch_match_ncc_slots(EkfEngine *e, int s_lo, int s_hi);
-void launch_match_compact(EkfEngine *e, int n_pred);
+void launch_match_compact(EkfEngine *e, const EkfKeypoint *kps, int n_pred);
 void launch_match_compact_slots(EkfEngine *e, int n_pred, const EkfKeypoint *d_slot_xy);
 void launch_ransac_hyp(EkfEngine *e, int M, int h0, int batch, const int *d_M, int h_lo, int h_hi);
 void launch_ransac_select(EkfEngine *e, int M, int h0, int batch, const int *d_M, int publish_seq);
@@ -399,7 +401,7 @@ void launch_planes_move(EkfEngine *e, bool pack, int m_k, int c_lo, int c_hi, in
 void launch_dx_planes(EkfEngine *e, int m_k);
 void launch_slice_columns(EkfEngine *e, int m, int c_lo, int c_hi);
 void launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi);
-void launch_rescue(EkfEngine *e, int M);
+void launch_rescue(EkfEngine *e, const EkfMatch *matches, int M);
 void launch_state_only_predict(EkfEngine *e, EkfPrediction *d_out); // predictMeasurementState on current state
 void launch_add_features(EkfEngine *e, const double *d_uv, int count, double *d_Jpo, double *d_Jhr);
 void launch_compact_P(EkfEngine *e, int n_new, const int *d_new2old);

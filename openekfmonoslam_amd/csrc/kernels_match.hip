@@ -170,19 +170,20 @@ k_match_compact(const int *plist, int n_pred, const int *mt_valid, const int *mt
     if (tid == 1023) *out_count = total;
 }
 
-void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred, bool with_ransac_init, const int *d_nkp)
+void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_pred, int n_kp, const int *d_npred,
+                  bool with_ransac_init, const int *d_nkp)
 {
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
         if (with_ransac_init) launch_ransac_init(e, e->N);
         return;
     }
-    k_match<<<n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, e->d.kps,
-                                           e->d.kdesc, n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
+    k_match<<<n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, kps,
+                                           kdesc, n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
                                            e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, d_npred, 0,
                                            d_nkp);
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
-                                               e->d.kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
+                                               kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
                                                with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N);
 }
 
@@ -190,21 +191,21 @@ void launch_match(EkfEngine *e, int n_pred, int n_kp, const int *d_npred, bool w
 // gates and matches the prediction slots [s_lo, s_hi) -- the predictions of the features it owns: the predicted list is in feature
 // order, so they are ONE run of slots -- into the per-slot tables; the ranks all-gather the tables (engine.cpp) and every rank
 // compacts the same complete tables into the same match list.
-void launch_match_slots(EkfEngine *e, int n_kp, int s_lo, int s_hi)
+void launch_match_slots(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_kp, int s_lo, int s_hi)
 {
     if (s_hi <= s_lo) return;
-    k_match<<<s_hi - s_lo, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, e->d.kps, e->d.kdesc, n_kp,
+    k_match<<<s_hi - s_lo, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, kps, kdesc, n_kp,
                                                 e->cfg.par.matchingCompCoefSecondBestVSFirst, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
                                                 e->desc_bytes, e->desc_f32 ? 1 : 0, nullptr, s_lo, nullptr);
 }
 
-void launch_match_compact(EkfEngine *e, int n_pred)
+void launch_match_compact(EkfEngine *e, const EkfKeypoint *kps, int n_pred)
 {
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
         return;
     }
-    k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->d.kps, 0, e->d.matches,
+    k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, kps, 0, e->d.matches,
                                                e->d.counts + CNT_NMATCH, nullptr, nullptr, nullptr, nullptr, 0);
 }
 

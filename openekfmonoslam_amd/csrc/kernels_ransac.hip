@@ -215,10 +215,10 @@ k_rescue(const EkfMatch *m, int M, const int *vis, const double *uv_tab, const d
     mask[i] = (vis[fi] && v < chi2) ? 1 : 0;
 }
 
-void launch_rescue(EkfEngine *e, int M)
+void launch_rescue(EkfEngine *e, const EkfMatch *matches, int M)
 {
     if (M <= 0) return;
-    k_rescue<<<(M + 255) / 256, 256, 0, e->stream>>>(e->d.matches, M, e->d.pred_vis, e->d.pred_uv, e->d.pred_S,
+    k_rescue<<<(M + 255) / 256, 256, 0, e->stream>>>(matches, M, e->d.pred_vis, e->d.pred_uv, e->d.pred_S,
                                                      e->cfg.par.ransacChi2Threshold, e->d.mask);
 }
 

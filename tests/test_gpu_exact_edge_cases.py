@@ -388,14 +388,20 @@ def test_stalled_persistent_sweep_is_retried_on_the_launch_per_panel_sweep(eng_m
         assert np.array_equal(P, P.T)  # (the first downdate after an upload symmetrises: the retry must do it, the frozen one must not have)
 
 
-@pytest.mark.parametrize("async_errors", [False, True], ids=["sync", "async"])
-@pytest.mark.parametrize("which", [0, 1, 2, 3], ids=["li_frame0", "hi_frame0", "li_frame1", "hi_frame1"])
-def test_stalled_sweep_inside_a_step_is_invisible_to_the_caller(eng_mod, oracle_lib, which, async_errors):
+_STALLS = [pytest.param(which, async_errors, False, id=f"{wid}-{aid}")
+           for which, wid in enumerate(["li_frame0", "hi_frame0", "li_frame1", "hi_frame1"])
+           for async_errors, aid in ((False, "sync"), (True, "async"))]
+_STALLS.append(pytest.param(1, True, True, id="hi_frame0-async-host_counts_after"))
+
+
+@pytest.mark.parametrize("which,async_errors,host_counts_after", _STALLS)
+def test_stalled_sweep_inside_a_step_is_invisible_to_the_caller(eng_mod, oracle_lib, which, async_errors, host_counts_after):
     """The same stall inside EKF::step (the staged-frames path bench.py times), on the first or the second update of a frame, with
     and without ekf_set_async_errors: the failed update is seen at the step's next read-back (or, async, at the NEXT step's first
     one -- that step's prediction must not have touched the filter), everything enqueued behind it was frozen, the update is run
     again and the stages behind it repeated.  Decisions, state, covariance and the map's timesMatched equal the oracle's after
-    every frame; EkfStepInfo.n_sweep_retries reports the retry in the step that performed it."""
+    every frame; EkfStepInfo.n_sweep_retries reports the retry in the step that performed it.  host_counts_after: the steps
+    behind frame 0 read their counts on the host (ekf_keep_step_predictions), so frame 0's unread failure reaches such a step."""
     seq = SyntheticSequence(170, 3, seed=5)
     e, o = make_pair(eng_mod, oracle_lib, seq, precision=EXACT)
     e.upload_frames(seq.frames)
@@ -403,6 +409,8 @@ def test_stalled_sweep_inside_a_step_is_invisible_to_the_caller(eng_mod, oracle_
     e.stall_sweep(which)  # persistent sweeps from now on: frame 0 LI, frame 0 HI, frame 1 LI, ...
     retried = 0
     for t in range(3):
+        if t == 1 and host_counts_after:
+            e.keep_step_predictions(True)
         gi = e.step_frame(t)
         oi = o.step(*seq.frames[t], ALGORITHMIC)
         assert gi.status == 0

@@ -143,6 +143,13 @@ int ekf_convert_inverse_depth_to_depth(EkfEngine *e, int *converted_index);
 /* the 13x13 camera block of the covariance, row-major: what EKF::step logs as StateCovarianceMatrixEstimation
  * (EKF/EKF.cpp:626) -- without moving the whole matrix */
 int ekf_get_camera_covariance(EkfEngine *e, double P13[169]);
+/* The map as 3-D points (EkfMapPoint per feature, map order), computed on the device: world position and 3x3
+ * covariance, the same point in the camera's axes with the pose uncertainty included, the linearity index and the
+ * feature's bookkeeping -- 216 bytes per feature cross the bus instead of P.  Read-only: x, P and the map tables are
+ * untouched.  Synchronises the stream and reports a pending asynchronous error as ekf_get_state does (the points are
+ * still produced).  points may be NULL (count only).  capacity < number of features -> EKF_ERR_CAPACITY, *count =
+ * number needed.  Not available on a sharded engine. */
+int ekf_get_map_points(EkfEngine *e, EkfMapPoint *points, int capacity, int *count);
 /* features the last full prediction did not see (unseenFeatures of predictCameraMeasurements,
  * EKF/MeasurementPrediction.cpp:705; EKF::step removes them under the conditions of EKF/EKF.cpp:583-592).
  * Ascending feature indices; feat_idx may be NULL to get the count only. */

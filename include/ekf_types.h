@@ -82,6 +82,20 @@ typedef struct EkfKeypoint {
     float x, y;
 } EkfKeypoint;
 
+/* One landmark of the map as a 3-D point (ekf_get_map_points).  No counterpart in the reference, whose map is only
+ * ever read in the filter's own parametrisation.  r, q = camera position and orientation (state elements 0..2, 3..6),
+ * R(q) = Core/EKFMath.cpp:133-155, m(theta, phi) = Core/EKFMath.cpp:159-166. */
+typedef struct EkfMapPoint {
+    double xyz[3];     /* world position X: (x y z) of a depth feature, (x0 y0 z0) + m(theta, phi) / rho otherwise  */
+    double cov[9];     /* 3x3 row-major covariance of X (world axes), exactly symmetric                              */
+    double cam[3];     /* the same point in the camera's axes: R(q)' (X - r)                                         */
+    double cov_cam[9]; /* 3x3 covariance of cam, camera position and orientation uncertainty included                */
+    double linearity;  /* computeLinearityIndex (EKF/MapManagement.cpp:312-341); 1e300 for a depth feature           */
+    int32_t type;      /* EKF_FEATURE_DEPTH / EKF_FEATURE_INVERSE_DEPTH                                              */
+    int32_t covpos;    /* first row of the feature in P                                                              */
+    uint32_t times_predicted, times_matched;
+} EkfMapPoint;         /* 25 doubles + 4 x 32 bit = 216 bytes, no padding                                            */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

@@ -504,6 +504,40 @@ private:
     int depth_;
 };
 
+// ------------------------------------------------------------------------------------------------- the map as 3-D points
+// (the reference shows its map in a PCL viewer, which this build does not have; the points and their covariances come from
+// the device, ekf_get_map_points, 216 bytes per feature instead of the covariance matrix)
+inline void mapPoints(EkfEngine *e, std::vector<EkfMapPoint> &points)
+{
+    int n = 0;
+    points.resize((size_t)ekf_num_features(e));
+    const int rc = ekf_get_map_points(e, points.empty() ? 0 : points.data(), (int)points.size(), &n);
+    if (rc != EKF_OK) throw std::runtime_error(std::string("ekf_get_map_points: ") + ekf_last_error(e));
+    points.resize((size_t)n);
+}
+
+// ASCII PLY: one vertex per feature in map order; x y z = world position, sx sy sz = square roots of the diagonal of its
+// covariance, inverse_depth = 1 while the feature is still in the inverse-depth parametrisation.  %.17g: the numbers
+// parse back to the same doubles.
+inline void writeMapPly(EkfEngine *e, const std::string &path)
+{
+    std::vector<EkfMapPoint> pts;
+    mapPoints(e, pts);
+    std::FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "ply\nformat ascii 1.0\ncomment OpenEKFMonoSLAM map: position and standard deviation per landmark\n");
+    std::fprintf(f, "element vertex %d\n", (int)pts.size());
+    std::fprintf(f, "property double x\nproperty double y\nproperty double z\n");
+    std::fprintf(f, "property double sx\nproperty double sy\nproperty double sz\n");
+    std::fprintf(f, "property uchar inverse_depth\nend_header\n");
+    for (size_t i = 0; i < pts.size(); ++i) {
+        const EkfMapPoint &p = pts[i];
+        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g %d\n", p.xyz[0], p.xyz[1], p.xyz[2], std::sqrt(p.cov[0]),
+                     std::sqrt(p.cov[4]), std::sqrt(p.cov[8]), p.type == EKF_FEATURE_INVERSE_DEPTH ? 1 : 0);
+    }
+    if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + path);
+}
+
 // ------------------------------------------------------------------------------------------------ ImageEKF
 // class EKF of the reference (1PointRansacEKF/EKF.h:41-63) with its own constructor arguments, image in.
 class ImageEKF {
@@ -605,6 +639,9 @@ public:
         logState();
         return info;
     }
+    // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
+    void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
+    void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path); }
     EkfEngine *engine() { return e_; }
     int steps() const { return steps_; }
     const EkfCamera &camera() const { return cam_; }

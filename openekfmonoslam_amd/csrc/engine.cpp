@@ -130,7 +130,7 @@ void ekf_engine_destroy(EkfEngine *e)
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     DeviceArrays &d = e->d;
-    void *ptrs[] = {d.state,     d.feat_pos,  d.feat_type, d.feat_covpos, d.feat_desc, d.feat_times_predicted, d.feat_times_matched, d.P, d.P2, d.mm_scratch, d.mm_index,        d.pred_vis, d.pred_vis_full, d.step_preds,
+    void *ptrs[] = {d.state,     d.feat_pos,  d.feat_type, d.feat_covpos, d.feat_desc, d.feat_times_predicted, d.feat_times_matched, d.P, d.P2, d.mm_scratch, d.mm_index, d.map_points, d.pred_vis, d.pred_vis_full, d.step_preds,
                     d.pred_uv,   d.pred_vis2, d.pred_uv2,  d.pred_S,      d.Hs,        d.Hf,       d.HP,
                     d.work_idx,  d.work_flag, d.plist,     d.plist_sub,   d.counts, d.shard_feat,    d.kps,      d.kdesc,
                     d.mt_valid,  d.mt_kp,     d.mt_dist,   d.matches,     d.msel,      d.mout,     d.match_of_feat,
@@ -721,6 +721,35 @@ int ekf_get_camera_covariance(EkfEngine *e, double P13[169])
         HIPCHK(hipMemcpy2D(P13, 13 * 8, e->d.P, (size_t)e->ldP * 8, 13 * 8, 13, hipMemcpyDeviceToHost));
     }
     return EKF_OK;
+}
+
+int ekf_get_map_points(EkfEngine *e, EkfMapPoint *points, int capacity, int *count)
+{
+    if (!e || !count || (points && capacity < 0)) return EKF_ERR_INVALID_ARG;
+    *count = 0;
+    NOT_WHEN_SHARDED(e)
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int pending = take_pending_error(e); // as ekf_get_state: the points are still produced from what the failed update left
+    const int N = e->N;
+    *count = N;
+    if (N == 0 || !points) return pending;
+    if (capacity < N) {
+        e->err = "ekf_get_map_points: capacity " + std::to_string(capacity) + " < " + std::to_string(N) + " features";
+        return EKF_ERR_CAPACITY;
+    }
+    if (!e->d.map_points) {
+        const hipError_t st = dalloc(&e->d.map_points, (size_t)e->cap);
+        if (st != hipSuccess) {
+            e->err = std::string("hipMalloc map_points: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    launch_map_points(e, e->d.map_points);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(points, e->d.map_points, (size_t)N * sizeof(EkfMapPoint), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return pending;
 }
 
 int ekf_get_unseen_features(EkfEngine *e, int32_t *feat_idx, int *count)

@@ -76,6 +76,7 @@ struct DeviceArrays {
     void *P2 = nullptr; // second buffer of the same size, allocated on the first removal (compaction target)
     double *mm_scratch = nullptr; // map management scratch: Jpo/Jhr of a batch, 3 x ldP conversion rows, N linearity values
     int *mm_index = nullptr;      // new2old row map (ncap ints)
+    EkfMapPoint *map_points = nullptr; // ekf_get_map_points: cap records, allocated by its first call
     // prediction tables, keyed by feature index
     int *pred_vis = nullptr;      // visibility per feature, latest prediction (full or subset)
     int *pred_vis_full = nullptr; // visibility per feature, last FULL prediction (the step's unseenFeatures)
@@ -407,6 +408,7 @@ void launch_add_features(EkfEngine *e, const double *d_uv, int count, double *d_
 void launch_compact_P(EkfEngine *e, int n_new, const int *d_new2old);
 void launch_linearity(EkfEngine *e, double *d_out);
 void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3);
+void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
 void launch_ncc_pyramid(EkfEngine *e, const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3], const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);

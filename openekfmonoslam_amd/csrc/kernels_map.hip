@@ -3,6 +3,7 @@
 //   addFeaturesToStateAndCovariance   EKF/AddMapFeature.cpp:221-359   -> k_addfeat_prepare / _rows / _corner
 //   removeFeaturesFromStateAndCovariance EKF/MapManagement.cpp:212-259 -> k_compact_P (+ host-side SoA compaction)
 //   computeLinearityIndex / convertToDepth EKF/MapManagement.cpp:312-490 -> k_linearity, k_convert_*
+// and the read-only export of the map as 3-D points with covariances (k_map_points; no counterpart in the reference).
 // The reference re-allocates and copies all of P for every added feature (O(n^2) each); here P lives in a
 // capacity-strided buffer, an append is two 6 x n strip products per feature (all new features in one launch),
 // a removal is one gather pass into a second buffer.  All strip kernels are HBM/latency-bound.
@@ -149,7 +150,25 @@ __global__ void __launch_bounds__(256) k_compact_P(const T *P, T *P2, int ld, in
 }
 
 // -------------------------------------------------------------------------------- inverse depth -> depth
-// computeLinearityIndex, EKF/MapManagement.cpp:312-341 (one thread per feature; depth features get +inf)
+// computeLinearityIndex, EKF/MapManagement.cpp:312-341 for one inverse-depth feature: p = its six parameters, r = camera
+// position, var_rho = the feature's P[rho][rho].  The one copy of the formula (k_linearity, k_map_points).
+__device__ __forceinline__ double linearity_index(const double *p, const double *x, double var_rho)
+{
+    const double inv_err = sqrt(var_rho);
+    const double sigma = inv_err / (p[5] * p[5]);
+    double m[3];
+    dir_vec(p[3], p[4], m);
+    const double xyz[3] = {p[0] + m[0] / p[5], p[1] + m[1] / p[5], p[2] + m[2] / p[5]};
+    const double tc[3] = {xyz[0] - x[0], xyz[1] - x[1], xyz[2] - x[2]};
+    const double tf[3] = {xyz[0] - p[0], xyz[1] - p[1], xyz[2] - p[2]};
+    double dot = 0.0;
+    for (int k = 0; k < 3; ++k) dot += tc[k] * tf[k];
+    const double df = sqrt(tf[0] * tf[0] + tf[1] * tf[1] + tf[2] * tf[2]);
+    const double dc = sqrt(tc[0] * tc[0] + tc[1] * tc[1] + tc[2] * tc[2]);
+    return 4.0 * sigma * (dot / (df * dc)) / dc;
+}
+
+// one thread per feature; depth features get +inf
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_linearity(const double *st, const double *feat_pos, const int *feat_type, const int *feat_covpos, int N, const T *P, int ld,
@@ -161,20 +180,20 @@ k_linearity(const double *st, const double *feat_pos, const int *feat_type, cons
         out[f] = 1e300;
         return;
     }
-    const double *p = feat_pos + 6 * (size_t)f, *x = st + ST_X;
+    const double *p = feat_pos + 6 * (size_t)f;
     const int ii = feat_covpos[f] + 5;
-    const double inv_err = sqrt((double)P[(size_t)ii * ld + ii]);
-    const double sigma = inv_err / (p[5] * p[5]);
-    double m[3];
-    dir_vec(p[3], p[4], m);
-    const double xyz[3] = {p[0] + m[0] / p[5], p[1] + m[1] / p[5], p[2] + m[2] / p[5]};
-    const double tc[3] = {xyz[0] - x[0], xyz[1] - x[1], xyz[2] - x[2]};
-    const double tf[3] = {xyz[0] - p[0], xyz[1] - p[1], xyz[2] - p[2]};
-    double dot = 0.0;
-    for (int k = 0; k < 3; ++k) dot += tc[k] * tf[k];
-    const double df = sqrt(tf[0] * tf[0] + tf[1] * tf[1] + tf[2] * tf[2]);
-    const double dc = sqrt(tc[0] * tc[0] + tc[1] * tc[1] + tc[2] * tc[2]);
-    out[f] = 4.0 * sigma * (dot / (df * dc)) / dc;
+    out[f] = linearity_index(p, st + ST_X, (double)P[(size_t)ii * ld + ii]);
+}
+
+// d X / d (x0 y0 z0 theta phi rho) of X = (x0 y0 z0) + m(theta, phi) / rho, 3x6 row-major (EKF/MapManagement.cpp:343-392);
+// mi = m(theta, phi).  The one copy of the formula (k_convert_prepare, k_map_points).
+__device__ __forceinline__ void inverse_depth_to_xyz_jacobian(double theta, double phi, double rho, const double *mi, double *J)
+{
+    for (int i = 0; i < 18; ++i) J[i] = 0.0;
+    J[0] = J[7] = J[14] = 1.0;
+    J[0 * 6 + 3] = cos(phi) * cos(theta) / rho;  J[2 * 6 + 3] = -cos(phi) * sin(theta) / rho;
+    J[0 * 6 + 4] = -sin(phi) * sin(theta) / rho; J[1 * 6 + 4] = -cos(phi) / rho; J[2 * 6 + 4] = -sin(phi) * cos(theta) / rho;
+    J[0 * 6 + 5] = -mi[0] / (rho * rho); J[1 * 6 + 5] = -mi[1] / (rho * rho); J[2 * 6 + 5] = -mi[2] / (rho * rho);
 }
 
 // convertToDepth, EKF/MapManagement.cpp:343-392: XYZ position and the 3x6 Jacobian; one thread.
@@ -185,11 +204,7 @@ __global__ void k_convert_prepare(double *feat_pos, int *feat_type, int fi, doub
     const double theta = p[3], phi = p[4], rho = p[5];
     double mi[3];
     dir_vec(theta, phi, mi);
-    for (int i = 0; i < 18; ++i) J[i] = 0.0;
-    J[0] = J[7] = J[14] = 1.0;
-    J[0 * 6 + 3] = cos(phi) * cos(theta) / rho;  J[2 * 6 + 3] = -cos(phi) * sin(theta) / rho;
-    J[0 * 6 + 4] = -sin(phi) * sin(theta) / rho; J[1 * 6 + 4] = -cos(phi) / rho; J[2 * 6 + 4] = -sin(phi) * cos(theta) / rho;
-    J[0 * 6 + 5] = -mi[0] / (rho * rho); J[1 * 6 + 5] = -mi[1] / (rho * rho); J[2 * 6 + 5] = -mi[2] / (rho * rho);
+    inverse_depth_to_xyz_jacobian(theta, phi, rho, mi, J);
     p[0] += mi[0] / rho; p[1] += mi[1] / rho; p[2] += mi[2] / rho;
     p[3] = p[4] = p[5] = 0.0;
     feat_type[fi] = EKF_FEATURE_DEPTH;
@@ -237,6 +252,111 @@ __global__ void __launch_bounds__(256) k_convert_apply(T *P, int ld, int n, int 
         P[(size_t)(pos + a) * ld + c] = v;
         P[(size_t)c * ld + pos + a] = v;
     }
+}
+
+// ------------------------------------------------------------------------------------ map export (read-only)
+// ekf_get_map_points: every feature as a world point X with its 3x3 covariance, the same point in the camera's axes with
+// a covariance that includes the pose uncertainty, and the linearity index.  z = (r, q, y) with y the feature's d = 6 or
+// 3 parameters, Z = P on rows/columns {0..6} u {pos..pos+d-1}:
+//     cov     = Jw P[pos.., pos..] Jw'         Jw = d X / d y (3 x d; identity for a depth feature)
+//     cov_cam = Jc Z Jc'                       Jc = [ -R' | d(R(q)' a)/dq at a = X - r | R' Jw ]  (3 x (7 + d))
+// One 64-lane wavefront per feature, MP_WAVES per workgroup.  The lanes gather Z into LDS as doubles (entry e of the
+// D x D matrix to lane e mod 64: runs of 7 and d consecutive columns of one row of P), lane 0 forms X, Jw and Jc, six
+// lanes form the upper triangle of each covariance, and 27 lanes store the 216-byte record as 8-byte words.  All
+// arithmetic is fp64 whatever T is.  Nothing but out is written.  Latency-bound: <= 1.4 KB read per feature.
+constexpr int MP_WAVES = 4, MP_D = 13, MP_WORDS = sizeof(EkfMapPoint) / 8;
+static_assert(sizeof(EkfMapPoint) == 216 && MP_WORDS * 8 == sizeof(EkfMapPoint), "EkfMapPoint is 27 packed 8-byte words");
+
+template <typename T>
+__global__ void __launch_bounds__(64 * MP_WAVES)
+k_map_points(const double *st, const double *feat_pos, const int *feat_type, const int *feat_covpos, const unsigned *times_predicted,
+             const unsigned *times_matched, int N, const T *P, int ld, EkfMapPoint *out)
+{
+    __shared__ double sZ[MP_WAVES][MP_D * MP_D], sJc[MP_WAVES][3 * MP_D], sJw[MP_WAVES][18];
+    __shared__ EkfMapPoint sOut[MP_WAVES];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f = blockIdx.x * MP_WAVES + w;
+    const bool live = f < N; // no early return: the workgroup meets at the barriers below
+    const int type = live ? feat_type[f] : EKF_FEATURE_DEPTH, pos = live ? feat_covpos[f] : 0;
+    const bool invd = type == EKF_FEATURE_INVERSE_DEPTH;
+    const int d = invd ? 6 : 3, D = 7 + d;
+    double *Z = sZ[w], *Jc = sJc[w], *Jw = sJw[w];
+    EkfMapPoint &o = sOut[w];
+    if (live) {
+        for (int e = lane; e < D * D; e += 64) {
+            const int i = e / D, j = e - i * D;
+            const int gi = i < 7 ? i : pos + i - 7, gj = j < 7 ? j : pos + j - 7;
+            Z[i * MP_D + j] = (double)P[(size_t)gi * ld + gj];
+        }
+        if (lane == 0) {
+            const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)f;
+            double X[3] = {y[0], y[1], y[2]}, jw[18];
+            if (invd) {
+                double m[3];
+                dir_vec(y[3], y[4], m);
+                inverse_depth_to_xyz_jacobian(y[3], y[4], y[5], m, jw);
+                X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
+            } else {
+                for (int i = 0; i < 18; ++i) jw[i] = 0.0;
+                jw[0] = jw[7] = jw[14] = 1.0;
+            }
+            double R[9], dq[12];
+            quat_to_rot(x + 3, R);
+            const double a[3] = {X[0] - x[0], X[1] - x[1], X[2] - x[2]};
+            const double qc[4] = {x[3], -x[4], -x[5], -x[6]}; // R(q)' = R(conj q); chain rule: vector columns negated
+            jac_rot_by_quat(qc, a, dq);
+            for (int i = 0; i < 3; ++i) {
+                o.xyz[i] = X[i];
+                o.cam[i] = R[i] * a[0] + R[3 + i] * a[1] + R[6 + i] * a[2];
+                for (int k = 0; k < 3; ++k) Jc[i * MP_D + k] = -R[k * 3 + i];
+                Jc[i * MP_D + 3] = dq[i * 4];
+                for (int k = 1; k < 4; ++k) Jc[i * MP_D + 3 + k] = -dq[i * 4 + k];
+                for (int k = 0; k < 6; ++k) {
+                    Jw[i * 6 + k] = jw[i * 6 + k];
+                    Jc[i * MP_D + 7 + k] = R[i] * jw[k] + R[3 + i] * jw[6 + k] + R[6 + i] * jw[12 + k];
+                }
+            }
+            o.type = type;
+            o.covpos = pos;
+            o.times_predicted = times_predicted[f];
+            o.times_matched = times_matched[f];
+        }
+    }
+    __syncthreads();
+    if (live) {
+        // lanes 0..5: upper triangle of cov_cam; lanes 8..13: upper triangle of cov; lane 16: linearity
+        const int t = lane & 7;
+        const int ra = t < 3 ? 0 : (t < 5 ? 1 : 2), rb = t < 3 ? t : (t < 5 ? t - 2 : 2);
+        if (lane < 6) {
+            double s = 0.0;
+            for (int i = 0; i < D; ++i) {
+                double u = 0.0;
+                for (int j = 0; j < D; ++j) u += Z[i * MP_D + j] * Jc[rb * MP_D + j];
+                s += Jc[ra * MP_D + i] * u;
+            }
+            o.cov_cam[ra * 3 + rb] = s;
+            o.cov_cam[rb * 3 + ra] = s;
+        } else if (lane >= 8 && lane < 14) {
+            double s;
+            if (invd) {
+                s = 0.0;
+                for (int i = 0; i < 6; ++i) {
+                    double u = 0.0;
+                    for (int j = 0; j < 6; ++j) u += Z[(7 + i) * MP_D + 7 + j] * Jw[rb * 6 + j];
+                    s += Jw[ra * 6 + i] * u;
+                }
+            } else {
+                s = Z[(7 + ra) * MP_D + 7 + rb]; // the stored block itself
+            }
+            o.cov[ra * 3 + rb] = s;
+            o.cov[rb * 3 + ra] = s;
+        } else if (lane == 16) {
+            o.linearity = invd ? linearity_index(feat_pos + 6 * (size_t)f, st + ST_X, Z[12 * MP_D + 12]) : 1e300;
+        }
+    }
+    __syncthreads();
+    if (live && lane < MP_WORDS)
+        reinterpret_cast<unsigned long long *>(out + f)[lane] = reinterpret_cast<const unsigned long long *>(&o)[lane];
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
@@ -293,6 +413,20 @@ void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3)
         k_convert_rows<double><<<nb, 256, 0, s>>>((const double *)e->d.P, e->ldP, e->n, pos, d_J, d_T3);
         k_convert_apply<double><<<nb, 256, 0, s>>>((double *)e->d.P, e->ldP, e->n, pos, d_J, d_T3);
     }
+}
+
+void launch_map_points(EkfEngine *e, EkfMapPoint *d_out)
+{
+    if (e->N <= 0) return;
+    const int nb = (e->N + MP_WAVES - 1) / MP_WAVES;
+    if (e->f32)
+        k_map_points<float><<<nb, 64 * MP_WAVES, 0, e->stream>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
+                                                                 e->d.feat_times_predicted, e->d.feat_times_matched, e->N,
+                                                                 (const float *)e->d.P, e->ldP, d_out);
+    else
+        k_map_points<double><<<nb, 64 * MP_WAVES, 0, e->stream>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
+                                                                  e->d.feat_times_predicted, e->d.feat_times_matched, e->N,
+                                                                  (const double *)e->d.P, e->ldP, d_out);
 }
 
 // Measurement aid (ekf_round_covariance_to_f32): every stored entry of an fp64 covariance replaced by its nearest fp32 value.

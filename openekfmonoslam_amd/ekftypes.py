@@ -59,6 +59,22 @@ class EkfStepInfo(C.Structure):
     ]
 
 
+class EkfMapPoint(C.Structure):
+    """One landmark as a 3-D point (ekf_get_map_points); 216 bytes, no padding."""
+
+    _fields_ = [
+        ("xyz", C.c_double * 3),
+        ("cov", C.c_double * 9),
+        ("cam", C.c_double * 3),
+        ("cov_cam", C.c_double * 9),
+        ("linearity", C.c_double),
+        ("type", C.c_int32),
+        ("covpos", C.c_int32),
+        ("times_predicted", C.c_uint32),
+        ("times_matched", C.c_uint32),
+    ]
+
+
 PREDICTION_DTYPE = np.dtype(
     [("featureIndex", "<i4"), ("_pad", "<i4"), ("imagePos", "<f8", (2,)), ("covarianceMatrix", "<f8", (4,))]
 )
@@ -66,6 +82,12 @@ MATCH_DTYPE = np.dtype(
     [("featureIndex", "<i4"), ("keypointIndex", "<i4"), ("imagePos", "<f8", (2,)), ("distance", "<f4"), ("_pad", "<f4")]
 )
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4")])
+# numpy view of an EkfMapPoint array: same fields, the covariances as (3, 3)
+MAP_POINT_DTYPE = np.dtype(
+    [("xyz", "<f8", (3,)), ("cov", "<f8", (3, 3)), ("cam", "<f8", (3,)), ("cov_cam", "<f8", (3, 3)), ("linearity", "<f8"),
+     ("type", "<i4"), ("covpos", "<i4"), ("times_predicted", "<u4"), ("times_matched", "<u4")]
+)
+assert MAP_POINT_DTYPE.itemsize == C.sizeof(EkfMapPoint) == 216
 assert PREDICTION_DTYPE.itemsize == 56 and MATCH_DTYPE.itemsize == 32 and KEYPOINT_DTYPE.itemsize == 8
 
 DESC_BYTES = 32

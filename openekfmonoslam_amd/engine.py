@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MATCH_DTYPE, PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfParams,
-                       EkfStepInfo)
+from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, PREDICTION_DTYPE, STATUS_NAMES, EkfCamera,
+                       EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
@@ -69,6 +69,7 @@ ABI = {
     "ekf_keep_step_predictions": (_i, [_vp, _i]),
     "ekf_get_step_predictions": (_i, [_vp, _vp, C.POINTER(_i)]),
     "ekf_get_camera_covariance": (_i, [_vp, _vp]),
+    "ekf_get_map_points": (_i, [_vp, C.POINTER(EkfMapPoint), _i, C.POINTER(_i)]),
     "ekf_get_unseen_features": (_i, [_vp, _vp, C.POINTER(_i)]),
     "ekf_state_dim": (_i, [_vp]),
     "ekf_descriptor_bytes": (_i, [_vp]),
@@ -303,6 +304,15 @@ class EkfEngine:
         P = np.zeros((13, 13))
         self._chk(self.L.ekf_get_camera_covariance(self.h, _p(P)))
         return P
+
+    def map_points(self):
+        """The map as 3-D points, computed on the device: a structured array (MAP_POINT_DTYPE: xyz, cov (3, 3), cam,
+        cov_cam (3, 3), linearity, type, covpos, times_predicted, times_matched) viewed on the ctypes buffer the
+        library filled.  Read-only for the filter."""
+        buf = (EkfMapPoint * max(self.N, 1))()
+        n = _i(0)
+        self._chk(self.L.ekf_get_map_points(self.h, buf, len(buf), C.byref(n)))
+        return np.frombuffer(buf, dtype=MAP_POINT_DTYPE)[: n.value]
 
     def unseen_features(self):
         idx = np.zeros(max(self.N, 1), dtype=np.int32)

@@ -2,7 +2,9 @@
 //     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
-// outdir/output.yml in the reference's layout.  Matcher mode B (NCC templates), so no OpenCV is needed.
+// outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
+// the map as 3-D points with their standard deviations (ImageEKF::writeMapPly).  Matcher mode B (NCC templates), so no
+// OpenCV is needed.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -44,6 +46,7 @@ int main(int argc, const char *argv[])
                             info.n_matches, info.n_inliers, info.n_rescued, (int)extendedKalmanFilter.state.mapFeatures.size(), x[0], x[1], x[2]);
                 image = generator.getNextImage();
             }
+            if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
         // (a detector threshold or the fp32 configuration asked for: the driver class with its extra constructor arguments)
@@ -60,6 +63,7 @@ int main(int argc, const char *argv[])
                         x[0], x[1], x[2]);
             image = generator.getNextImage();
         }
+        if (!outputPath.empty()) extendedKalmanFilter.writeMapPly(outputPath + "map.ply");
     } catch (const std::exception &ex) {
         std::fprintf(stderr, "ekf_sequence: %s\n", ex.what());
         return 1;

@@ -249,6 +249,20 @@ int ekf_get_image_level(EkfEngine *e, int level, uint8_t *out, int *width, int *
  * initialised at: addFeaturesToStateAndCovariance keeps the descriptor there, EKF/AddMapFeature.cpp:317-337) */
 int ekf_capture_templates(EkfEngine *e, const int32_t *feat_idx, const double *uv, int count);
 int ekf_match_ncc(EkfEngine *e, EkfMatch *matches, int *n_matches);
+/* Predicted appearance (opt-in; off: the path above, bit for bit).  A template is treated as a small plane through the
+ * feature's world point that faces the camera which captured it; with the mode on, a capture also keeps a 41x41 source
+ * patch per pyramid level and the capture pose, and every NCC search compares a template re-rendered from the current
+ * pose estimate.  A level whose samples leave the source patch, or a feature captured with the mode
+ * off (or present at ekf_set_state), uses the stored template.  Allocates 3 x 1681 + 363 bytes + 9 doubles per feature
+ * of capacity on first use; turning it off keeps the tables.  EKF_ERR_INVALID_ARG on a sharded engine;
+ * EKF_IMAGE_MATCHER_KEYPOINTS ignores the mode. */
+int ekf_set_template_warp(EkfEngine *e, int on);
+/* levels re-rendered / fallen back in the last NCC match: 3 x predictions in total with the mode on, 0 and 0 with it off */
+int ekf_get_template_warp_counts(const EkfEngine *e, int *warped_levels, int *fallback_levels);
+/* the 3 x 121 bytes the last NCC match compared for the listed features (features it did not predict: the stored
+ * template).  The re-rendered table is not carried through a change of the map: after ekf_add_features, a removal, a
+ * conversion, ekf_set_state or ekf_reset, and until the next match, the stored templates are returned.  Readback for tests */
+int ekf_get_match_templates(EkfEngine *e, const int32_t *feat_idx, int count, uint8_t *tmpl363);
 int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels,
                    EkfStepInfo *info); /* (matcher: ekf_set_image_matcher) */
 /* detectNewImageFeatures(image, featuresPrediction, newImageFeaturesMaxSize, newImageFeatures)

@@ -639,6 +639,10 @@ public:
         logState();
         return info;
     }
+    // NCC templates re-rendered from the predicted viewpoint before every search (ekf_set_template_warp); call it before
+    // init() so that the first features keep their source patches.  A setter, not a config key: the reference's
+    // config.yml schema has none.  Ignored by the keypoint matcher.
+    void setTemplateWarp(bool on) { chk(ekf_set_template_warp(e_, on ? 1 : 0), "ekf_set_template_warp"); }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path); }

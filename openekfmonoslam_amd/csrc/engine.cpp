@@ -137,7 +137,7 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -653,6 +653,8 @@ int ekf_set_state(EkfEngine *e, const double x13[13], int n_features, const doub
     e->n_step_preds = 0;
     HIPCHK(hipMemset(e->d.feat_times_predicted, 0, (size_t)e->cap * sizeof(unsigned)));
     HIPCHK(hipMemset(e->d.feat_times_matched, 0, (size_t)e->cap * sizeof(unsigned)));
+    if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * 9 * sizeof(double))); // template warp: no feature has a source patch
+    e->last_match_warped = false; // d.wtmpl belongs to the map the last match saw
     return EKF_OK;
 }
 
@@ -814,6 +816,7 @@ int ekf_add_features(EkfEngine *e, const double *uv, const uint8_t *desc32, int 
     else HIPCHK(hipMemsetAsync(dd, 0, (size_t)count * e->desc_bytes, e->stream));
     HIPCHK(hipMemsetAsync(e->d.feat_times_predicted + e->N, 0, (size_t)count * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->d.feat_times_matched + e->N, 0, (size_t)count * 4, e->stream));
+    if (e->d.wpose) HIPCHK(hipMemsetAsync(e->d.wpose + 9 * (size_t)e->N, 0, (size_t)count * 9 * sizeof(double), e->stream));
     launch_add_features(e, d_uv, count, d_Jpo, d_Jhr);
     for (int j = 0; j < count; ++j) {
         e->h_type.push_back(EKF_FEATURE_INVERSE_DEPTH);
@@ -822,6 +825,7 @@ int ekf_add_features(EkfEngine *e, const double *uv, const uint8_t *desc32, int 
     e->N += count;
     e->n += 6 * count;
     e->n_pred = 0;
+    e->last_match_warped = false; // d.wtmpl has no rows for the new features
     refresh_row_map(e);
     HIPCHK(hipStreamSynchronize(e->stream));
     return check_async(e);
@@ -850,6 +854,13 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     std::vector<uint8_t> tmpl((size_t)N * 363);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(tmpl.data(), e->d.tmpl, tmpl.size(), hipMemcpyDeviceToHost));
+    constexpr size_t WSRC = 3 * 41 * 41; // template warp: source patches and capture poses follow their features
+    std::vector<uint8_t> wsrc(e->d.wsrc ? (size_t)N * WSRC : 0);
+    std::vector<double> wpose(e->d.wpose ? (size_t)N * 9 : 0);
+    if (!wsrc.empty()) {
+        HIPCHK(hipMemcpy(wsrc.data(), e->d.wsrc, wsrc.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(wpose.data(), e->d.wpose, wpose.size() * 8, hipMemcpyDeviceToHost));
+    }
     HIPCHK(hipMemcpy(pos.data(), e->d.feat_pos, pos.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(desc.data(), e->d.feat_desc, desc.size(), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tp.data(), e->d.feat_times_predicted, (size_t)N * 4, hipMemcpyDeviceToHost));
@@ -861,6 +872,10 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
         std::memmove(&pos[6 * (size_t)w], &pos[6 * (size_t)i], 6 * sizeof(double));
         std::memmove(&desc[(size_t)w * e->desc_bytes], &desc[(size_t)i * e->desc_bytes], e->desc_bytes);
         std::memmove(&tmpl[(size_t)w * 363], &tmpl[(size_t)i * 363], 363);
+        if (!wsrc.empty()) {
+            std::memmove(&wsrc[(size_t)w * WSRC], &wsrc[(size_t)i * WSRC], WSRC);
+            std::memmove(&wpose[(size_t)w * 9], &wpose[(size_t)i * 9], 9 * sizeof(double));
+        }
         tp[w] = tp[i];
         tm[w] = tm[i];
         e->h_type[w] = e->h_type[i];
@@ -878,6 +893,10 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
         HIPCHK(hipMemcpy(e->d.feat_pos, pos.data(), (size_t)6 * w * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_desc, desc.data(), (size_t)w * e->desc_bytes, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.tmpl, tmpl.data(), (size_t)w * 363, hipMemcpyHostToDevice));
+        if (!wsrc.empty()) {
+            HIPCHK(hipMemcpy(e->d.wsrc, wsrc.data(), (size_t)w * WSRC, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(e->d.wpose, wpose.data(), (size_t)w * 9 * 8, hipMemcpyHostToDevice));
+        }
         HIPCHK(hipMemcpy(e->d.feat_times_predicted, tp.data(), (size_t)w * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_times_matched, tm.data(), (size_t)w * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_type, e->h_type.data(), (size_t)w * 4, hipMemcpyHostToDevice));
@@ -887,6 +906,7 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     e->n = n_new;
     refresh_row_map(e);
     e->n_pred = 0;
+    e->last_match_warped = false; // d.wtmpl is not compacted: until the next match ekf_get_match_templates shows the stored ones
     return check_async(e);
 }
 
@@ -1785,6 +1805,8 @@ int ekf_capture_templates(EkfEngine *e, const int32_t *feat_idx, const double *u
     HIPCHK(hipMemcpyAsync(e->d.work_idx, feat_idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->d.pred_uv2, uv, (size_t)count * 2 * sizeof(double), hipMemcpyHostToDevice, e->stream));
     launch_ncc_capture(e, e->d.work_idx, e->d.pred_uv2, count);
+    // template warp: source patches and the capture pose with the mode on; a capture with it off leaves "no source patch"
+    if (e->d.wpose) launch_ncc_warp_capture(e, e->d.work_idx, e->d.pred_uv2, count, e->warp_on);
     HIPCHK(hipStreamSynchronize(e->stream)); // the host arrays may be reused by the caller
     return check_async(e);
 }
@@ -2053,11 +2075,64 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches)
         e->err = "NCC matcher: no image uploaded";
         return EKF_ERR_INVALID_ARG;
     }
+    e->last_match_warped = e->warp_on;
     launch_match_ncc(e, e->n_pred);
     int rc = read_counts(e);
     if (rc) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
+    e->warp_counts[0] = e->last_match_warped ? e->h_counts[CNT_WARP_OK] : 0;
+    e->warp_counts[1] = e->last_match_warped ? e->h_counts[CNT_WARP_FB] : 0;
     return check_async(e);
+}
+
+int ekf_set_template_warp(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) {
+        e->err = "template warp: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (on && !e->d.wpose) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        const size_t cap = (size_t)e->cap;
+        hipError_t st = dalloc(&e->d.wsrc, cap * 3 * 41 * 41);
+        if (st == hipSuccess) st = dalloc(&e->d.wtmpl, cap * 363);
+        if (st == hipSuccess) st = dalloc(&e->d.wpose, cap * 9); // zeroed: no feature has a source patch yet
+        if (st != hipSuccess) {
+            for (void *p : {(void *)e->d.wsrc, (void *)e->d.wtmpl, (void *)e->d.wpose})
+                if (p) (void)hipFree(p);
+            e->d.wsrc = e->d.wtmpl = nullptr;
+            e->d.wpose = nullptr;
+            e->err = std::string("template warp tables: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    e->warp_on = on != 0;
+    return EKF_OK;
+}
+
+int ekf_get_template_warp_counts(const EkfEngine *e, int *warped_levels, int *fallback_levels)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (warped_levels) *warped_levels = e->warp_counts[0];
+    if (fallback_levels) *fallback_levels = e->warp_counts[1];
+    return EKF_OK;
+}
+
+int ekf_get_match_templates(EkfEngine *e, const int32_t *feat_idx, int count, uint8_t *tmpl363)
+{
+    if (!e || count < 0 || (count > 0 && (!feat_idx || !tmpl363))) return EKF_ERR_INVALID_ARG;
+    for (int i = 0; i < count; ++i)
+        if (feat_idx[i] < 0 || feat_idx[i] >= e->N) return EKF_ERR_INVALID_ARG;
+    if (count == 0) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const uint8_t *src = e->last_match_warped ? e->d.wtmpl : e->d.tmpl;
+    std::vector<uint8_t> all((size_t)e->N * 363);
+    HIPCHK(hipMemcpy(all.data(), src, all.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; ++i) std::memcpy(tmpl363 + (size_t)i * 363, &all[(size_t)feat_idx[i] * 363], 363);
+    return EKF_OK;
 }
 
 int ekf_match_ncc(EkfEngine *e, EkfMatch *matches, int *n_matches)

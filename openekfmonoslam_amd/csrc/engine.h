@@ -56,6 +56,8 @@ enum {
     CNT_AUX1,
     CNT_SHARD0,       // sharded filter: CNT_SHARD0 + r = first entry of a feature-sorted match list that rank r owns
                       // (r = 0 .. world, at most 16 ranks: slots 12 .. 28; k_shard_bounds)
+    CNT_WARP_OK = 29, // template warp: levels re-rendered for the last NCC match (k_ncc_warp)
+    CNT_WARP_FB,      // ... and levels that fell back to the stored template
     CNT_COUNT = 32
 };
 constexpr int MAX_SHARD_WORLD = 16;
@@ -104,6 +106,10 @@ struct DeviceArrays {
     float *mt_dist = nullptr;
     EkfKeypoint *mt_xy = nullptr; // NCC matcher: matched pixel per prediction slot
     uint8_t *tmpl = nullptr;      // NCC matcher: 3 levels x 121 bytes per feature
+    // template warp (ekf_set_template_warp; allocated by its first call)
+    uint8_t *wsrc = nullptr;      // 3 levels x 41 x 41 source bytes per feature
+    double *wpose = nullptr;      // 9 per feature: capture position r0, quaternion q0 (all zero: no source patch), capture pixel
+    uint8_t *wtmpl = nullptr;     // the templates the match compares with the mode on: same layout as tmpl
     double *gates = nullptr;      // new-feature detector: gate + centre + radius (8 doubles) per prediction of the last full prediction
     unsigned long long *kp_rowmask = nullptr; // keypoint detector: one bit per pixel of the frame, 64-pixel row segments
     EkfKeypoint *det_kps = nullptr;  // ekf_detect_keypoints / ekf_describe: output staging (det_cap entries)
@@ -263,6 +269,9 @@ struct EkfEngine {
     int n_step_preds = 0;
     int cells_cap = 0;        // detector cell buffers allocated for this many cells
     int image_matcher = EKF_IMAGE_MATCHER_NCC; // ekf_set_image_matcher: how image steps match
+    bool warp_on = false;          // ekf_set_template_warp: NCC templates re-rendered from the predicted pose before every search
+    bool last_match_warped = false; // the last NCC match compared d.wtmpl (else d.tmpl)
+    int warp_counts[2] = {0, 0};   // levels warped / fallen back in the last NCC match
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -412,6 +421,8 @@ void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, m
 void launch_ncc_pyramid(EkfEngine *e, const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3], const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);
+// template warp: source patches + capture pose of the listed features (keep = false: marks them "no source patch")
+void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep);
 void launch_match_ncc(EkfEngine *e, int n_pred);
 void launch_gate_snapshot(EkfEngine *e, int n_pred);
 void launch_detect_cells(EkfEngine *e, int n_gates, int cells_x, int cells_y, long long *d_resp, int *d_xy);

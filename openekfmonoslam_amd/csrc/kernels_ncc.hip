@@ -64,6 +64,132 @@ k_ncc_capture(Pyr pyr, const int *feat_idx, const double *uv, uint8_t *tmpl)
     tmpl[((size_t)feat_idx[i] * 3 + l) * NCC_TT + t] = (uint8_t)pyr_at(pyr, l, cx + dx, cy + dy);
 }
 
+// ---- template warp -------------------------------------------------------------------------
+// A template is the image of a small plane through the feature's world point X that faces the camera which first saw it.
+// k_ncc_warp_capture keeps, per feature and level, the 41 x 41 pixels around the capture pixel and the capture pose;
+// k_ncc_warp re-renders the 11 x 11 template of every prediction slot from the current pose estimate before the search:
+// template pixel -> ray of the current camera -> plane -> pixel of the capture camera -> bilinear sample of the source.
+// A level whose samples leave the source (or whose geometry is degenerate) keeps the stored template, whole.
+constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S, WARP_R = WARP_S / 2;
+
+// block = (item, level): source patch; the level-0 block also writes the pose record (keep = 0: zeros = "no source patch")
+__global__ void __launch_bounds__(256)
+k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double *st, uint8_t *wsrc, double *wpose, int keep)
+{
+    const int i = blockIdx.x, l = blockIdx.y, fi = feat_idx[i];
+    if (l == 0 && threadIdx.x < 9) {
+        const int t = threadIdx.x;
+        wpose[9 * (size_t)fi + t] = !keep ? 0.0 : (t < 7 ? st[ST_X + t] : uv[2 * i + t - 7]);
+    }
+    if (!keep) return;
+    const int cx = to_level(uv[2 * i], l), cy = to_level(uv[2 * i + 1], l);
+    for (int t = threadIdx.x; t < WARP_SS; t += 256)
+        wsrc[((size_t)fi * 3 + l) * WARP_SS + t] = (uint8_t)pyr_at(pyr, l, cx + t % WARP_S - WARP_R, cy + t / WARP_S - WARP_R);
+}
+
+// One workgroup per prediction slot, 128 lanes per level (121 active): fp64, everything a lane touches after the staging
+// is in LDS (5 KB of source bytes, 30 doubles of constants).  Latency-bound like k_ncc_match: ~0.4 KFLOP and one 10-step
+// Newton solve per lane.  out already holds a copy of the stored templates; only whole warped levels are written.
+__global__ void __launch_bounds__(384)
+k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const double *st, CamD c, const double *feat_pos,
+           const int *feat_type, const uint8_t *wsrc, const double *wpose, uint8_t *out, int *counts)
+{
+    __shared__ uint8_t s_src[3 * WARP_SS + 1];
+    __shared__ double s_R[9], s_R0[9], s_n[3], s_r[3], s_r0[3], s_nXr, s_uv0[2];
+    __shared__ int s_bad[3];
+
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k >= *d_npred) return;
+    const int fi = plist[k];
+    const double *pose = wpose + 9 * (size_t)fi;
+    const bool has_src = pose[3] != 0.0 || pose[4] != 0.0 || pose[5] != 0.0 || pose[6] != 0.0; // uniform over the block
+    if (!has_src) {
+        if (tid == 0) atomicAdd(counts + CNT_WARP_FB, 3);
+        return;
+    }
+    for (int i = tid; i < 3 * WARP_SS; i += 384) s_src[i] = wsrc[(size_t)fi * 3 * WARP_SS + i];
+    if (tid < 3) s_bad[tid] = 0;
+    if (tid == 0) {
+        const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)fi;
+        double X[3] = {y[0], y[1], y[2]};
+        if (feat_type[fi] == EKF_FEATURE_INVERSE_DEPTH) {
+            double m[3];
+            dir_vec(y[3], y[4], m);
+            X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
+        }
+        quat_to_rot(x + 3, s_R);
+        quat_to_rot(pose + 3, s_R0);
+        const double a[3] = {pose[0] - X[0], pose[1] - X[1], pose[2] - X[2]};
+        const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        double nXr = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            s_n[i] = a[i] / an;
+            s_r[i] = x[i];
+            s_r0[i] = pose[i];
+            nXr += s_n[i] * (X[i] - x[i]);
+        }
+        s_nXr = nXr;
+        s_uv0[0] = pose[7];
+        s_uv0[1] = pose[8];
+    }
+    __syncthreads();
+
+    const int l = tid >> 7, t = tid & 127;
+    const bool live = t < NCC_TT;
+    const double sc = (double)(1 << l);
+    bool bad = false;
+    int val = 0;
+    if (live) {
+        const int cxl = to_level(uv_tab[2 * fi], l), cyl = to_level(uv_tab[2 * fi + 1], l);
+        const double px = ((double)(cxl + t % NCC_T - NCC_R) + 0.5) * sc - 0.5, py = ((double)(cyl + t / NCC_T - NCC_R) + 0.5) * sc - 0.5;
+        // undistortPoint (closed form), then the ray in world axes
+        const double pdx = px - c.cx, pdy = py - c.cy;
+        const double mx = c.dx * pdx, my = c.dy * pdy;
+        const double rd2 = mx * mx + my * my;
+        const double f = 1.0 + c.k1 * rd2 + c.k2 * rd2 * rd2;
+        const double hc[3] = {pdx * f / c.fx, pdy * f / c.fy, 1.0};
+        double d[3];
+        mat3_vec(s_R, hc, d);
+        const double nd = s_n[0] * d[0] + s_n[1] * d[1] + s_n[2] * d[2];
+        bad = !(nd < 0.0); // n points from the plane to the capturing camera: a ray that meets its front has n . d < 0
+        if (!bad) {
+            const double lam = s_nXr / nd;
+            bad = !(lam > 0.0);
+            if (!bad) {
+                const double w[3] = {s_r[0] + lam * d[0] - s_r0[0], s_r[1] + lam * d[1] - s_r0[1], s_r[2] + lam * d[2] - s_r0[2]};
+                const double h0 = s_R0[0] * w[0] + s_R0[3] * w[1] + s_R0[6] * w[2];
+                const double h1 = s_R0[1] * w[0] + s_R0[4] * w[1] + s_R0[7] * w[2];
+                const double h2 = s_R0[2] * w[0] + s_R0[5] * w[1] + s_R0[8] * w[2];
+                bad = !(h2 > 0.0);
+                if (!bad) {
+                    double s[2];
+                    distort(c, c.cx + c.fx * h0 / h2, c.cy + c.fy * h1 / h2, s);
+                    const double sx = (s[0] + 0.5) / sc - 0.5 - (double)(to_level(s_uv0[0], l) - WARP_R);
+                    const double sy = (s[1] + 0.5) / sc - 0.5 - (double)(to_level(s_uv0[1], l) - WARP_R);
+                    bad = !(sx >= 0.0 && sx <= (double)(WARP_S - 1) && sy >= 0.0 && sy <= (double)(WARP_S - 1));
+                    if (!bad) {
+                        const int x0 = min((int)floor(sx), WARP_S - 2), y0 = min((int)floor(sy), WARP_S - 2);
+                        const double ax = sx - (double)x0, ay = sy - (double)y0;
+                        const uint8_t *p = s_src + l * WARP_SS + y0 * WARP_S + x0;
+                        const double top = (1.0 - ax) * (double)p[0] + ax * (double)p[1];
+                        const double bot = (1.0 - ax) * (double)p[WARP_S] + ax * (double)p[WARP_S + 1];
+                        const double b = (1.0 - ay) * top + ay * bot;
+                        val = min(max((int)floor(b + 0.5), 0), 255);
+                    }
+                }
+            }
+        }
+        if (bad) s_bad[l] = 1; // any lane of the level: the whole level falls back
+    }
+    __syncthreads();
+    if (live && !s_bad[l]) out[((size_t)fi * 3 + l) * NCC_TT + t] = (uint8_t)val;
+    if (tid == 0) {
+        const int nfb = s_bad[0] + s_bad[1] + s_bad[2];
+        if (nfb) atomicAdd(counts + CNT_WARP_FB, nfb);
+        if (nfb < 3) atomicAdd(counts + CNT_WARP_OK, 3 - nfb);
+    }
+}
+
 // ---- matching ----------------------------------------------------------------------------------------------
 // zncc^2 of a candidate whose 11x11 window starts at sw[oy][ox] (LDS window of row pitch `pitch`)
 __device__ inline double ncc_key(const uint8_t *win, int pitch, int ox, int oy, const uint8_t *tp, int st, int stt)
@@ -207,15 +333,34 @@ void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int 
     if (count > 0) k_ncc_capture<<<dim3(count, 3), 128, 0, e->stream>>>(pyr_of(e), d_idx, d_uv, e->d.tmpl);
 }
 
+void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep)
+{
+    if (count > 0)
+        k_ncc_warp_capture<<<dim3(count, 3), 256, 0, e->stream>>>(pyr_of(e), d_idx, d_uv, e->d.state, e->d.wsrc, e->d.wpose, keep ? 1 : 0);
+}
+
 void launch_match_compact_slots(EkfEngine *e, int n_pred, const EkfKeypoint *d_slot_xy);
+
+// the templates this match compares: the stored ones, or (ekf_set_template_warp) their re-rendering from the predicted pose
+static const uint8_t *match_templates(EkfEngine *e, int n_pred)
+{
+    if (!e->warp_on) return e->d.tmpl;
+    (void)hipMemsetAsync(e->d.counts + CNT_WARP_OK, 0, 2 * sizeof(int), e->stream);
+    (void)hipMemcpyAsync(e->d.wtmpl, e->d.tmpl, (size_t)e->N * 3 * NCC_TT, hipMemcpyDeviceToDevice, e->stream);
+    if (n_pred > 0)
+        k_ncc_warp<<<n_pred, 384, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, e->d.pred_uv, e->d.state, e->cam, e->d.feat_pos,
+                                                  e->d.feat_type, e->d.wsrc, e->d.wpose, e->d.wtmpl, e->d.counts);
+    return e->d.wtmpl;
+}
 
 void launch_match_ncc(EkfEngine *e, int n_pred)
 {
+    const uint8_t *tmpl = match_templates(e, n_pred);
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
         return;
     }
-    k_ncc_match<<<n_pred, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.tmpl, e->d.mt_valid,
+    k_ncc_match<<<n_pred, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, tmpl, e->d.mt_valid,
                                                e->d.mt_xy, e->d.mt_dist, 0);
     launch_match_compact_slots(e, n_pred, e->d.mt_xy);
 }

@@ -93,6 +93,9 @@ ABI = {
     "ekf_get_image_level": (_i, [_vp, _i, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_capture_templates": (_i, [_vp, _vp, _vp, _i]),
     "ekf_match_ncc": (_i, [_vp, _vp, C.POINTER(_i)]),
+    "ekf_set_template_warp": (_i, [_vp, _i]),
+    "ekf_get_template_warp_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "ekf_get_match_templates": (_i, [_vp, _vp, _i, _vp]),
     "ekf_step_image": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(EkfStepInfo)]),
     "ekf_detect_new_features": (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, C.POINTER(_i)]),
     "ekf_images_upload": (_i, [_vp, _i, _vp, _i, _i, _i, _i]),
@@ -506,6 +509,23 @@ class EkfEngine:
         n = C.c_int(0)
         self._chk(self.L.ekf_match_ncc(self.h, _p(out), C.byref(n)))
         return out[: n.value]
+
+    def set_template_warp(self, on=True):
+        """NCC templates re-rendered from the predicted viewpoint before every search; off: the stored ones"""
+        self._chk(self.L.ekf_set_template_warp(self.h, 1 if on else 0))
+
+    def template_warp_counts(self):
+        """(levels warped, levels fallen back) in the last NCC match"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_template_warp_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def match_templates(self, feat_idx):
+        """the templates the last NCC match compared for the listed features -> uint8 [k, 3, 11, 11]"""
+        idx = np.ascontiguousarray(feat_idx, dtype=np.int32)
+        out = np.zeros((max(len(idx), 1), 3, 11, 11), dtype=np.uint8)
+        self._chk(self.L.ekf_get_match_templates(self.h, _p(idx), len(idx), _p(out)))
+        return out[: len(idx)]
 
     def step_image(self, image):
         img, w, h, stride, ch = self._image_args(image)

@@ -242,7 +242,8 @@ int ekf_set_sweep_mode(EkfEngine *e, int mode);
  * of its 11x11 template inside the predicted ellipse (gate of Matching.cpp:217-241), coarse to fine.  The
  * reference has no such matcher (it runs an OpenCV detector + descriptor on the host, Matching.cpp:188-210);
  * the definition is this build's and is restated on the CPU in oracle/ekf_oracle.c for the parity tests.
- * Matches carry keypointIndex = -1 and integer pixel positions; templates are captured once and kept. */
+ * Matches carry keypointIndex = -1 and integer pixel positions (sub-pixel positions with ekf_set_subpixel_matches,
+ * below); templates are captured once and kept. */
 int ekf_image_upload(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels);
 int ekf_get_image_level(EkfEngine *e, int level, uint8_t *out, int *width, int *height); /* readback for tests */
 /* templates of the listed map features, cut from the CURRENT image around uv (the pixel a feature was
@@ -263,6 +264,18 @@ int ekf_get_template_warp_counts(const EkfEngine *e, int *warped_levels, int *fa
  * template).  The re-rendered table is not carried through a change of the map: after ekf_add_features, a removal, a
  * conversion, ekf_set_state or ekf_reset, and until the next match, the stored templates are returned.  Readback for tests */
 int ekf_get_match_templates(EkfEngine *e, const int32_t *feat_idx, int count, uint8_t *tmpl363);
+/* Sub-pixel matches (opt-in; off: integer pixels as above, bit for bit).  With the mode on, each axis of a match's
+ * imagePos is the vertex of the parabola through the ZNCC^2 keys of the best level-0 pixel and its two neighbours on
+ * that axis, compared against the template the search compared (the re-rendered one with the template warp):
+ *     a = km - kp,  b = (km - 2 k0) + kp,  offset = (0.5 a) / b clamped to [-0.5, 0.5],  pos = (float)((double)best + offset)
+ * in fp64, on the device.  An axis stays at the integer when a neighbour's centre is outside the frame,
+ * a neighbour has no score or scores above the best pixel, or b >= 0.  Which features match, their order, the gate test
+ * (on the integer pixel) and the distances do not change.  EKF_ERR_INVALID_ARG on a sharded engine;
+ * EKF_IMAGE_MATCHER_KEYPOINTS ignores the mode. */
+int ekf_set_subpixel_matches(EkfEngine *e, int on);
+/* axes of the last NCC match's matches that the fit moved / that stayed at the integer: 2 x matches in total with the
+ * mode on, 0 and 0 with it off */
+int ekf_get_subpixel_counts(const EkfEngine *e, int *refined_axes, int *integer_axes);
 int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels,
                    EkfStepInfo *info); /* (matcher: ekf_set_image_matcher) */
 /* detectNewImageFeatures(image, featuresPrediction, newImageFeaturesMaxSize, newImageFeatures)

@@ -643,6 +643,9 @@ public:
     // init() so that the first features keep their source patches.  A setter, not a config key: the reference's
     // config.yml schema has none.  Ignored by the keypoint matcher.
     void setTemplateWarp(bool on) { chk(ekf_set_template_warp(e_, on ? 1 : 0), "ekf_set_template_warp"); }
+    // NCC matches at sub-pixel positions: a parabola through the best pixel's and its neighbours' scores, per axis
+    // (ekf_set_subpixel_matches); at any time, it takes effect with the next step.  A setter for the same reason.
+    void setSubpixelMatches(bool on) { chk(ekf_set_subpixel_matches(e_, on ? 1 : 0), "ekf_set_subpixel_matches"); }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path); }

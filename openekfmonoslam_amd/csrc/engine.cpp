@@ -1202,7 +1202,7 @@ static int match_sharded_dev(EkfEngine *e, bool use_ncc, const EkfKeypoint *d_kp
     }
     int rc = EKF_OK;
     if (np > 0) {
-        if (use_ncc) launch_match_ncc_slots(e, e->slot_rb[me], e->slot_rb[me + 1]);
+        if (use_ncc) launch_match_ncc_slots(e, e->slot_rb[me], e->slot_rb[me + 1], e->subpix_on);
         else launch_match_slots(e, d_kps, d_desc, n_kp, e->slot_rb[me], e->slot_rb[me + 1]);
         rc = exchange_rows(e, EKF_XCHG_MATCH_VALID, e->d.mt_valid, sizeof(int), e->slot_rb, "the match flags");
         if (!rc) rc = use_ncc ? exchange_rows(e, EKF_XCHG_MATCH_XY, e->d.mt_xy, sizeof(EkfKeypoint), e->slot_rb, "the matched pixels")
@@ -2076,12 +2076,15 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches)
         return EKF_ERR_INVALID_ARG;
     }
     e->last_match_warped = e->warp_on;
-    launch_match_ncc(e, e->n_pred);
+    const bool subpix = e->subpix_on;
+    launch_match_ncc(e, e->n_pred, subpix);
     int rc = read_counts(e);
     if (rc) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
     e->warp_counts[0] = e->last_match_warped ? e->h_counts[CNT_WARP_OK] : 0;
     e->warp_counts[1] = e->last_match_warped ? e->h_counts[CNT_WARP_FB] : 0;
+    e->subpix_counts[0] = subpix ? e->h_counts[CNT_SUBPIX_FIT] : 0;
+    e->subpix_counts[1] = subpix ? e->h_counts[CNT_SUBPIX_INT] : 0;
     return check_async(e);
 }
 
@@ -2117,6 +2120,25 @@ int ekf_get_template_warp_counts(const EkfEngine *e, int *warped_levels, int *fa
     if (!e) return EKF_ERR_INVALID_ARG;
     if (warped_levels) *warped_levels = e->warp_counts[0];
     if (fallback_levels) *fallback_levels = e->warp_counts[1];
+    return EKF_OK;
+}
+
+int ekf_set_subpixel_matches(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) {
+        e->err = "sub-pixel matches: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    e->subpix_on = on != 0;
+    return EKF_OK;
+}
+
+int ekf_get_subpixel_counts(const EkfEngine *e, int *refined_axes, int *integer_axes)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (refined_axes) *refined_axes = e->subpix_counts[0];
+    if (integer_axes) *integer_axes = e->subpix_counts[1];
     return EKF_OK;
 }
 

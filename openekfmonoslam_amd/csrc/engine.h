@@ -53,11 +53,12 @@ enum {
     CNT_RS_DONE,      // RANSAC: loop finished
     CNT_NRESC,        // rescued count
     CNT_KP_FOUND,     // keypoints the detector found in the current image (k_kp_compact)
-    CNT_AUX1,
+    CNT_SUBPIX_INT,   // sub-pixel NCC matches: axes of valid matches left at the integer by the last NCC match (k_ncc_match<true>)
     CNT_SHARD0,       // sharded filter: CNT_SHARD0 + r = first entry of a feature-sorted match list that rank r owns
                       // (r = 0 .. world, at most 16 ranks: slots 12 .. 28; k_shard_bounds)
     CNT_WARP_OK = 29, // template warp: levels re-rendered for the last NCC match (k_ncc_warp)
     CNT_WARP_FB,      // ... and levels that fell back to the stored template
+    CNT_SUBPIX_FIT,   // sub-pixel NCC matches: axes of valid matches moved by the parabola fit (the others: CNT_SUBPIX_INT)
     CNT_COUNT = 32
 };
 constexpr int MAX_SHARD_WORLD = 16;
@@ -272,6 +273,8 @@ struct EkfEngine {
     bool warp_on = false;          // ekf_set_template_warp: NCC templates re-rendered from the predicted pose before every search
     bool last_match_warped = false; // the last NCC match compared d.wtmpl (else d.tmpl)
     int warp_counts[2] = {0, 0};   // levels warped / fallen back in the last NCC match
+    bool subpix_on = false;        // ekf_set_subpixel_matches: NCC matches carry the parabola-fitted position
+    int subpix_counts[2] = {0, 0}; // axes fitted / left at the integer over the valid matches of the last NCC match
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -395,7 +398,7 @@ void launch_shard_bounds(EkfEngine *e, const EkfMatch *list, int count);
 void launch_shard_bounds_idx(EkfEngine *e, const int *list, const int *d_count); // ... of a feature-index list whose length is on the device
 // sharded filter: matching and RANSAC hypotheses divided by feature ownership (kernels_match.hip, kernels_ncc.hip, kernels_ransac.hip)
 void launch_match_slots(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_kp, int s_lo, int s_hi);
-void launch_match_ncc_slots(EkfEngine *e, int s_lo, int s_hi);
+void launch_match_ncc_slots(EkfEngine *e, int s_lo, int s_hi, bool subpix);
 void launch_match_compact(EkfEngine *e, const EkfKeypoint *kps, int n_pred);
 void launch_match_compact_slots(EkfEngine *e, int n_pred, const EkfKeypoint *d_slot_xy);
 void launch_ransac_hyp(EkfEngine *e, int M, int h0, int batch, const int *d_M, int h_lo, int h_hi);
@@ -423,7 +426,7 @@ void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);
 // template warp: source patches + capture pose of the listed features (keep = false: marks them "no source patch")
 void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep);
-void launch_match_ncc(EkfEngine *e, int n_pred);
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix); // subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7
 void launch_gate_snapshot(EkfEngine *e, int n_pred);
 void launch_detect_cells(EkfEngine *e, int n_gates, int cells_x, int cells_y, long long *d_resp, int *d_xy);
 // keypoints of the current image (kernels_detect.hip): the first `cap` in raster order -> out, all of them -> *d_found;

@@ -232,9 +232,32 @@ __device__ inline void block_argmax(double &key, int &idx, double *s_key, int *s
     __syncthreads();
 }
 
+// ---- sub-pixel fit --------------------------------------------------------------------------
+// Offset of the vertex of the parabola through the keys at -1, 0, +1 pixels, one axis; *fit = 0 and offset 0 where the
+// rule leaves the integer: a neighbour outside the frame (key -2, see k_ncc_match) or without a score (-1), a neighbour
+// above the centre (the 4x4 child window does not make the best pixel a 3x3 maximum), or no curvature.  Every
+// operation is one correctly rounded fp64 add, multiply by a power of two or divide, in the order of the numpy
+// restatement (tests/ncc_subpixel_ref.py): the result is the same bits.
+__device__ inline double subpix_offset(double km, double k0, double kp, int *fit)
+{
+#pragma clang fp contract(off)
+    *fit = 0;
+    if (km < 0.0 || kp < 0.0 || km > k0 || kp > k0) return 0.0;
+    const double a = km - kp;
+    const double b = (km - 2.0 * k0) + kp;
+    if (b >= 0.0) return 0.0;
+    *fit = 1;
+    const double d = (0.5 * a) / b;
+    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
+}
+
+// SUBPIX (ekf_set_subpixel_matches): after the search the keys of the best pixel's four level-0 neighbours are evaluated
+// and each axis of the reported position is moved by subpix_offset; counts then receives the fitted / integer axes of the
+// valid matches.  SUBPIX = false is the integer matcher as it was.
+template <bool SUBPIX>
 __global__ void __launch_bounds__(256)
 k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *tmpl,
-            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0)
+            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0, int *counts)
 {
     __shared__ Gate g;
     __shared__ int s_geom[4]; // c2x, c2y, rad
@@ -252,7 +275,9 @@ k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab
         double angle;
         ellipse_from_cov(S_tab + 4 * fi, axes, &angle);
         const int aw = (int)rintf(axes[0]), ah = (int)rintf(axes[1]);
-        gate_from_ellipse((float)pu, (float)pv, aw, ah, angle, &g);
+        // (always_inline: with two instantiations this is no longer the function's only call site and the compiler would
+        // stop inlining it, in the integer matcher too)
+        [[clang::always_inline]] gate_from_ellipse((float)pu, (float)pv, aw, ah, angle, &g);
         const int major = aw > ah ? aw : ah;
         s_geom[0] = to_level(pu, 2);
         s_geom[1] = to_level(pv, 2);
@@ -295,12 +320,43 @@ k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab
         if (idx != 0x7fffffff) { bx = x0 + idx % cw; by = y0 + idx / cw; }
         bkey = key; // -3 when this level had no candidate (position carried over, as the CPU loop does)
     }
+    if constexpr (SUBPIX) {
+        // bkey is uniform over the block.  s_t and s_tsum still hold the level-0 template and its sums; every read of s_win
+        // and s_key lies before the barrier that ends block_argmax.
+        if (bkey >= 0.0) {
+            constexpr int SP = 3 + 2 * NCC_R; // 13: the 3x3 candidates around (bx, by) and their 5-pixel border
+            if (tid < SP * SP) s_win[tid] = (uint8_t)pyr_at(pyr, 0, bx - 1 - NCC_R + tid % SP, by - 1 - NCC_R + tid / SP);
+            __syncthreads();
+            if (tid < 4) { // lanes 0..3: the neighbours at x - 1, x + 1, y - 1, y + 1
+                const int ox = tid < 2 ? 2 * tid : 1, oy = tid < 2 ? 1 : 2 * (tid - 2);
+                const int x = bx - 1 + ox, y = by - 1 + oy;
+                const bool inside = x >= 0 && y >= 0 && x < pyr.w[0] && y < pyr.h[0]; // the candidate loop's rule
+                s_key[tid] = inside ? ncc_key(s_win, SP, ox, oy, s_t, s_tsum[0], s_tsum[1]) : -2.0;
+            }
+            __syncthreads();
+        }
+    }
     if (tid == 0) {
         const bool ok = bkey >= 0.64 && gate_contains(g, (double)(float)bx, (double)(float)by);
         mt_valid[k] = ok ? 1 : 0;
         EkfKeypoint p;
-        p.x = (float)bx;
-        p.y = (float)by;
+        if constexpr (SUBPIX) {
+            int fx = 0, fy = 0;
+            double dx = 0.0, dy = 0.0;
+            if (bkey >= 0.0) {
+                dx = subpix_offset(s_key[0], bkey, s_key[1], &fx);
+                dy = subpix_offset(s_key[2], bkey, s_key[3], &fy);
+            }
+            p.x = (float)((double)bx + dx);
+            p.y = (float)((double)by + dy);
+            if (ok) {
+                if (fx + fy > 0) atomicAdd(counts + CNT_SUBPIX_FIT, fx + fy);
+                if (fx + fy < 2) atomicAdd(counts + CNT_SUBPIX_INT, 2 - fx - fy);
+            }
+        } else {
+            p.x = (float)bx;
+            p.y = (float)by;
+        }
         mt_xy[k] = p;
         mt_dist[k] = ok ? (float)(1.0 - sqrt(bkey)) : 0.f;
     }
@@ -353,25 +409,37 @@ static const uint8_t *match_templates(EkfEngine *e, int n_pred)
     return e->d.wtmpl;
 }
 
-void launch_match_ncc(EkfEngine *e, int n_pred)
+// the NCC search of the prediction slots [s_lo, s_hi); subpix: with the parabola fit, whose axis counters it zeroes first
+static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_hi, bool subpix)
+{
+    if (subpix) {
+        (void)hipMemsetAsync(e->d.counts + CNT_SUBPIX_FIT, 0, sizeof(int), e->stream);
+        (void)hipMemsetAsync(e->d.counts + CNT_SUBPIX_INT, 0, sizeof(int), e->stream);
+    }
+    if (s_hi <= s_lo) return;
+    auto kern = subpix ? k_ncc_match<true> : k_ncc_match<false>;
+    kern<<<s_hi - s_lo, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, tmpl, e->d.mt_valid, e->d.mt_xy,
+                                             e->d.mt_dist, s_lo, e->d.counts);
+}
+
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix)
 {
     const uint8_t *tmpl = match_templates(e, n_pred);
+    match_ncc_slots(e, tmpl, 0, n_pred, subpix);
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
         return;
     }
-    k_ncc_match<<<n_pred, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, tmpl, e->d.mt_valid,
-                                               e->d.mt_xy, e->d.mt_dist, 0);
     launch_match_compact_slots(e, n_pred, e->d.mt_xy);
 }
 
 // sharded filter: the NCC search of the prediction slots [s_lo, s_hi) only (see launch_match_slots, kernels_match.hip); the per-slot
 // tables are completed by an all-gather and compacted by launch_match_compact_slots on every rank
-void launch_match_ncc_slots(EkfEngine *e, int s_lo, int s_hi)
+// (subpix: a sharded engine refuses ekf_set_subpixel_matches, so its callers pass false; the axis counters of a rank would
+// cover its own slots only)
+void launch_match_ncc_slots(EkfEngine *e, int s_lo, int s_hi, bool subpix)
 {
-    if (s_hi <= s_lo) return;
-    k_ncc_match<<<s_hi - s_lo, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.tmpl, e->d.mt_valid, e->d.mt_xy,
-                                                    e->d.mt_dist, s_lo);
+    match_ncc_slots(e, e->d.tmpl, s_lo, s_hi, subpix);
 }
 
 } // namespace ekf

@@ -96,6 +96,8 @@ ABI = {
     "ekf_set_template_warp": (_i, [_vp, _i]),
     "ekf_get_template_warp_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_get_match_templates": (_i, [_vp, _vp, _i, _vp]),
+    "ekf_set_subpixel_matches": (_i, [_vp, _i]),
+    "ekf_get_subpixel_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_step_image": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(EkfStepInfo)]),
     "ekf_detect_new_features": (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, C.POINTER(_i)]),
     "ekf_images_upload": (_i, [_vp, _i, _vp, _i, _i, _i, _i]),
@@ -526,6 +528,17 @@ class EkfEngine:
         out = np.zeros((max(len(idx), 1), 3, 11, 11), dtype=np.uint8)
         self._chk(self.L.ekf_get_match_templates(self.h, _p(idx), len(idx), _p(out)))
         return out[: len(idx)]
+
+    def set_subpixel_matches(self, on=True):
+        """NCC matches at the vertex of a parabola through the best pixel's and its neighbours' scores, per axis (DESIGN.md 4.7);
+        off: integer pixels"""
+        self._chk(self.L.ekf_set_subpixel_matches(self.h, 1 if on else 0))
+
+    def subpixel_counts(self):
+        """(axes moved by the fit, axes left at the integer) over the matches of the last NCC match"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_subpixel_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def step_image(self, image):
         img, w, h, stride, ch = self._image_args(image)

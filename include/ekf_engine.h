@@ -239,7 +239,9 @@ int ekf_set_sweep_mode(EkfEngine *e, int mode);
  * EKF/EKF.h:57 take the frame itself.  Mode B keeps that signature: the frame is uploaded (1, 3 = BGR or
  * 4 = RGBA bytes per pixel, as Img/FileSequenceImageGenerator.cpp:82 and android jni/EKFNative.cpp:163 deliver
  * it), reduced to a 3-level gray pyramid on the device, and each predicted feature is matched by zero-mean NCC
- * of its 11x11 template inside the predicted ellipse (gate of Matching.cpp:217-241), coarse to fine.  The
+ * of its 11x11 template inside the predicted ellipse (gate of Matching.cpp:217-241), coarse to fine.  The coarse
+ * level looks at most 16 coarse pixels (about 66 px) away from the prediction: a gate whose major semi-axis is 64 px
+ * or more is searched only that far unless ekf_set_ncc_wide_search (below) is on.  The
  * reference has no such matcher (it runs an OpenCV detector + descriptor on the host, Matching.cpp:188-210);
  * the definition is this build's and is restated on the CPU in oracle/ekf_oracle.c for the parity tests.
  * Matches carry keypointIndex = -1 and integer pixel positions (sub-pixel positions with ekf_set_subpixel_matches,
@@ -276,6 +278,17 @@ int ekf_set_subpixel_matches(EkfEngine *e, int on);
 /* axes of the last NCC match's matches that the fit moved / that stayed at the integer: 2 x matches in total with the
  * mode on, 0 and 0 with it off */
 int ekf_get_subpixel_counts(const EkfEngine *e, int *refined_axes, int *integer_axes);
+/* Wide search (opt-in; off: the path above, bit for bit).  With the mode on, a prediction whose gate exceeds the coarse
+ * window -- (major semi-axis >> 2) + 1 > 16, i.e. a major semi-axis of 64 px or more -- has its coarse level searched
+ * over the whole gate within the frame, as the default search would with an unbounded window: same candidates rule, same
+ * key, ties to the first pixel in raster order; then the same two finer levels, acceptance test and optional sub-pixel
+ * fit.  Predictions whose gate fits the window keep the default path's result, bit for bit.  Takes
+ * effect with the next match (ekf_step_image, ekf_step_staged_image, ekf_match_ncc); composes with the two modes above.
+ * EKF_ERR_INVALID_ARG on a sharded engine; EKF_IMAGE_MATCHER_KEYPOINTS ignores the mode. */
+int ekf_set_ncc_wide_search(EkfEngine *e, int on);
+/* of the last NCC match: predictions searched wide, and the coarse candidates evaluated for them (saturating at
+ * INT_MAX); 0 and 0 with the mode off */
+int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candidates);
 int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels,
                    EkfStepInfo *info); /* (matcher: ekf_set_image_matcher) */
 /* detectNewImageFeatures(image, featuresPrediction, newImageFeaturesMaxSize, newImageFeatures)

@@ -646,6 +646,9 @@ public:
     // NCC matches at sub-pixel positions: a parabola through the best pixel's and its neighbours' scores, per axis
     // (ekf_set_subpixel_matches); at any time, it takes effect with the next step.  A setter for the same reason.
     void setSubpixelMatches(bool on) { chk(ekf_set_subpixel_matches(e_, on ? 1 : 0), "ekf_set_subpixel_matches"); }
+    // NCC gates with a major semi-axis of 64 px or more searched whole instead of within 66 px of the prediction
+    // (ekf_set_ncc_wide_search); at any time, it takes effect with the next step.  A setter for the same reason.
+    void setWideSearch(bool on) { chk(ekf_set_ncc_wide_search(e_, on ? 1 : 0), "ekf_set_ncc_wide_search"); }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path); }

@@ -137,7 +137,7 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -2069,6 +2069,32 @@ int ekf_get_step_keypoints(const EkfEngine *e, int *detected, int *kept)
     return EKF_OK;
 }
 
+// wide search: the list of wide slots (cap records) and their per-tile partial results (cap x tiles of the coarse level), allocated
+// by the first match that needs them and again when a larger frame brings more tiles
+static int ensure_wide_tables(EkfEngine *e)
+{
+    const int tiles = ncc_wide_tiles(e->img.w[2], e->img.h[2]);
+    if (e->d.wide_list && tiles <= e->wide_tiles) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (void *p : {e->d.wide_list, e->d.wide_part})
+        if (p) (void)hipFree(p);
+    e->d.wide_list = e->d.wide_part = nullptr;
+    e->wide_tiles = 0;
+    uint8_t *list = nullptr, *part = nullptr;
+    hipError_t st = dalloc(&list, (size_t)e->cap * NCC_WIDE_SLOT_BYTES + NCC_WIDE_TOTALS_BYTES);
+    if (st == hipSuccess) st = dalloc(&part, (size_t)e->cap * (size_t)std::max(tiles, 1) * NCC_WIDE_PARTIAL_BYTES);
+    if (st != hipSuccess) {
+        if (list) (void)hipFree(list);
+        e->err = std::string("wide search tables: ") + hipGetErrorString(st);
+        return EKF_ERR_HIP;
+    }
+    e->d.wide_list = list;
+    e->d.wide_part = part;
+    e->wide_tiles = tiles;
+    return EKF_OK;
+}
+
 static int match_ncc_dev(EkfEngine *e, int *n_matches)
 {
     if (!e->img.valid) {
@@ -2076,15 +2102,19 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches)
         return EKF_ERR_INVALID_ARG;
     }
     e->last_match_warped = e->warp_on;
-    const bool subpix = e->subpix_on;
-    launch_match_ncc(e, e->n_pred, subpix);
-    int rc = read_counts(e);
+    const bool subpix = e->subpix_on, wide = e->wide_on;
+    int rc = wide ? ensure_wide_tables(e) : EKF_OK;
+    if (rc) return rc;
+    launch_match_ncc(e, e->n_pred, subpix, wide);
+    rc = read_counts(e);
     if (rc) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
     e->warp_counts[0] = e->last_match_warped ? e->h_counts[CNT_WARP_OK] : 0;
     e->warp_counts[1] = e->last_match_warped ? e->h_counts[CNT_WARP_FB] : 0;
     e->subpix_counts[0] = subpix ? e->h_counts[CNT_SUBPIX_FIT] : 0;
     e->subpix_counts[1] = subpix ? e->h_counts[CNT_SUBPIX_INT] : 0;
+    e->wide_counts[0] = wide ? e->h_counts[CNT_WIDE_SLOTS] : 0;
+    e->wide_counts[1] = wide ? e->h_counts[CNT_WIDE_CANDS] : 0;
     return check_async(e);
 }
 
@@ -2139,6 +2169,25 @@ int ekf_get_subpixel_counts(const EkfEngine *e, int *refined_axes, int *integer_
     if (!e) return EKF_ERR_INVALID_ARG;
     if (refined_axes) *refined_axes = e->subpix_counts[0];
     if (integer_axes) *integer_axes = e->subpix_counts[1];
+    return EKF_OK;
+}
+
+int ekf_set_ncc_wide_search(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) {
+        e->err = "wide search: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    e->wide_on = on != 0;
+    return EKF_OK;
+}
+
+int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candidates)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (wide_slots) *wide_slots = e->wide_counts[0];
+    if (wide_candidates) *wide_candidates = e->wide_counts[1];
     return EKF_OK;
 }
 

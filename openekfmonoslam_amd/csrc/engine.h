@@ -59,7 +59,9 @@ enum {
     CNT_WARP_OK = 29, // template warp: levels re-rendered for the last NCC match (k_ncc_warp)
     CNT_WARP_FB,      // ... and levels that fell back to the stored template
     CNT_SUBPIX_FIT,   // sub-pixel NCC matches: axes of valid matches moved by the parabola fit (the others: CNT_SUBPIX_INT)
-    CNT_COUNT = 32
+    CNT_WIDE_SLOTS,   // wide search: prediction slots whose gate exceeds the 43 x 43 window in the last NCC match (k_ncc_wide_classify)
+    CNT_WIDE_CANDS,   // ... and the coarse candidates evaluated for them, saturating at INT_MAX (k_ncc_wide_finish)
+    CNT_COUNT = 40    // (publish_counts_block / k_publish_counts copy with the lanes t < 64; the mirror page holds 64 ints)
 };
 constexpr int MAX_SHARD_WORLD = 16;
 
@@ -111,6 +113,9 @@ struct DeviceArrays {
     uint8_t *wsrc = nullptr;      // 3 levels x 41 x 41 source bytes per feature
     double *wpose = nullptr;      // 9 per feature: capture position r0, quaternion q0 (all zero: no source patch), capture pixel
     uint8_t *wtmpl = nullptr;     // the templates the match compares with the mode on: same layout as tmpl
+    // wide search (ekf_set_ncc_wide_search; allocated by its first match)
+    void *wide_list = nullptr;    // WideSlot per wide prediction slot, slot order (kernels_ncc.hip), cap records + one WideTotals
+    void *wide_part = nullptr;    // WidePartial per (wide slot, tile of the coarse level): cap x wide_tiles records
     double *gates = nullptr;      // new-feature detector: gate + centre + radius (8 doubles) per prediction of the last full prediction
     unsigned long long *kp_rowmask = nullptr; // keypoint detector: one bit per pixel of the frame, 64-pixel row segments
     EkfKeypoint *det_kps = nullptr;  // ekf_detect_keypoints / ekf_describe: output staging (det_cap entries)
@@ -275,6 +280,9 @@ struct EkfEngine {
     int warp_counts[2] = {0, 0};   // levels warped / fallen back in the last NCC match
     bool subpix_on = false;        // ekf_set_subpixel_matches: NCC matches carry the parabola-fitted position
     int subpix_counts[2] = {0, 0}; // axes fitted / left at the integer over the valid matches of the last NCC match
+    bool wide_on = false;          // ekf_set_ncc_wide_search: gates beyond the 43 x 43 coarse window are searched whole
+    int wide_counts[2] = {0, 0};   // wide slots / coarse candidates evaluated for them in the last NCC match
+    int wide_tiles = 0;            // tiles per slot d.wide_part was allocated for (the coarse level's tile count)
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -426,7 +434,14 @@ void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);
 // template warp: source patches + capture pose of the listed features (keep = false: marks them "no source patch")
 void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep);
-void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix); // subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7
+// subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7; wide: the slots whose gate exceeds the coarse window go
+// through the three kernels of DESIGN.md 4.8 instead (d.wide_list / d.wide_part sized for the current frame: engine.cpp)
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide);
+constexpr int NCC_WIDE_TILE = 32;          // coarse candidates per tile side
+constexpr int NCC_WIDE_SLOT_BYTES = 80;    // sizeof(WideSlot), kernels_ncc.hip
+constexpr int NCC_WIDE_PARTIAL_BYTES = 16; // sizeof(WidePartial)
+constexpr int NCC_WIDE_TOTALS_BYTES = 16;  // sizeof(WideTotals): one record behind the list
+inline int ncc_wide_tiles(int w2, int h2) { return ((w2 + NCC_WIDE_TILE - 1) / NCC_WIDE_TILE) * ((h2 + NCC_WIDE_TILE - 1) / NCC_WIDE_TILE); }
 void launch_gate_snapshot(EkfEngine *e, int n_pred);
 void launch_detect_cells(EkfEngine *e, int n_gates, int cells_x, int cells_y, long long *d_resp, int *d_xy);
 // keypoints of the current image (kernels_detect.hip): the first `cap` in raster order -> out, all of them -> *d_found;
@@ -437,7 +452,7 @@ size_t kp_rowmask_words(int w, int h);
 void launch_brief(EkfEngine *e, const EkfKeypoint *kps, const int *centres, int n, const int *d_n, uint8_t *desc);
 void launch_publish_counts(EkfEngine *e, int *d_mirror, int seq);
 // The same publication from inside a kernel that ends a stage (saves the separate launch): called by EVERY thread of a
-// block after the block's last write to `counts`; lanes 0..15 copy the counters to the GPU-writable host page, lane 0
+// block after the block's last write to `counts`; the lanes below CNT_COUNT copy the counters to the GPU-writable host page, lane 0
 // then releases the sequence number the host polls.
 __device__ __forceinline__ void publish_counts_block(const int *counts, int *mirror, int seq)
 {

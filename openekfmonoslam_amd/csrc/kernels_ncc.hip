@@ -5,6 +5,10 @@
 // score is num^2/den in fp64 (one multiply, one divide of identically rounded operands), so the result is
 // bit-identical to the CPU definition the tests check against.
 //
+// The coarse search of the default path is capped at a 33x33 candidate square (NCC_MAXRAD = 16 coarse pixels): "every pixel of
+// the ellipse" holds for gates whose major semi-axis is below 64 px; a larger gate is searched within about +-66 px of the
+// prediction only.  The wide search (ekf_set_ncc_wide_search) searches such gates whole.
+//
 // Byte work: a frame is ~1.6 MB of pyramid, a prediction touches a <= 43x43 window of the coarse level.  One
 // workgroup per prediction stages the window and the template in LDS; nothing here is GEMM-shaped.
 #include "engine.h"
@@ -251,78 +255,57 @@ __device__ inline double subpix_offset(double km, double k0, double kp, int *fit
     return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
 }
 
-// SUBPIX (ekf_set_subpixel_matches): after the search the keys of the best pixel's four level-0 neighbours are evaluated
-// and each axis of the reported position is moved by subpix_offset; counts then receives the fitted / integer axes of the
-// valid matches.  SUBPIX = false is the integer matcher as it was.
-template <bool SUBPIX>
-__global__ void __launch_bounds__(256)
-k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *tmpl,
-            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0, int *counts)
+// One level of the search by the whole workgroup (256 lanes): stages the (cw + 10)^2 window whose candidates start at (x0, y0) and the
+// level's template tl in LDS, evaluates the candidates inside the frame -- at the coarse level (l == 2) only the predicted pixel
+// (gcx, gcy) and those whose centre lies in the gate -- and leaves the best one in (bx, by), its key in bkey: -3 and an unchanged
+// position when the level had no candidate (position carried over, as the CPU loop does).  Shared by k_ncc_match and
+// k_ncc_wide_finish.
+__device__ __forceinline__ void ncc_search_level(const Pyr &pyr, int l, int x0, int y0, int cw, const uint8_t *tl, const Gate &g, int gcx,
+                                                 int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double *s_key, int *s_idx, int &bx,
+                                                 int &by, double &bkey)
 {
-    __shared__ Gate g;
-    __shared__ int s_geom[4]; // c2x, c2y, rad
-    __shared__ uint8_t s_win[NCC_WIN * NCC_WIN + 3];
-    __shared__ uint8_t s_t[NCC_TT + 3];
-    __shared__ int s_tsum[2];
-    __shared__ double s_key[4];
-    __shared__ int s_idx[4];
-
-    const int k = slot0 + (int)blockIdx.x, tid = threadIdx.x; // slot0: see launch_match_ncc_slots
-    const int fi = plist[k];
-    const double pu = uv_tab[2 * fi], pv = uv_tab[2 * fi + 1];
+    const int tid = threadIdx.x;
+    const int pitch = cw + 2 * NCC_R;
+    for (int i = tid; i < pitch * pitch; i += 256)
+        s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + i % pitch, y0 - NCC_R + i / pitch);
+    if (tid < NCC_TT) s_t[tid] = tl[tid];
+    __syncthreads();
     if (tid == 0) {
-        float axes[2];
-        double angle;
-        ellipse_from_cov(S_tab + 4 * fi, axes, &angle);
-        const int aw = (int)rintf(axes[0]), ah = (int)rintf(axes[1]);
-        // (always_inline: with two instantiations this is no longer the function's only call site and the compiler would
-        // stop inlining it, in the integer matcher too)
-        [[clang::always_inline]] gate_from_ellipse((float)pu, (float)pv, aw, ah, angle, &g);
-        const int major = aw > ah ? aw : ah;
-        s_geom[0] = to_level(pu, 2);
-        s_geom[1] = to_level(pv, 2);
-        s_geom[2] = min((major >> 2) + 1, NCC_MAXRAD);
+        int st = 0, stt = 0;
+        for (int i = 0; i < NCC_TT; ++i) { st += s_t[i]; stt += s_t[i] * s_t[i]; }
+        s_tsum[0] = st; s_tsum[1] = stt;
     }
     __syncthreads();
-
-    int bx = s_geom[0], by = s_geom[1];
-    double bkey = -3.0;
-    for (int l = 2; l >= 0; --l) {
-        // candidate window at this level: coarse = the gated square around the prediction, finer = 4x4 children
-        int x0, y0, cw;
-        if (l == 2) { x0 = s_geom[0] - s_geom[2]; y0 = s_geom[1] - s_geom[2]; cw = 2 * s_geom[2] + 1; }
-        else { x0 = 2 * bx - 1; y0 = 2 * by - 1; cw = 4; }
-        const int pitch = cw + 2 * NCC_R;
-        for (int i = tid; i < pitch * pitch; i += 256)
-            s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + i % pitch, y0 - NCC_R + i / pitch);
-        if (tid < NCC_TT) s_t[tid] = tmpl[((size_t)fi * 3 + l) * NCC_TT + tid];
-        __syncthreads();
-        if (tid == 0) {
-            int st = 0, stt = 0;
-            for (int i = 0; i < NCC_TT; ++i) { st += s_t[i]; stt += s_t[i] * s_t[i]; }
-            s_tsum[0] = st; s_tsum[1] = stt;
+    const int st = s_tsum[0], stt = s_tsum[1];
+    double key = -3.0;
+    int idx = 0x7fffffff;
+    for (int c = tid; c < cw * cw; c += 256) {
+        const int ox = c % cw, oy = c / cw, x = x0 + ox, y = y0 + oy;
+        if (x < 0 || y < 0 || x >= pyr.w[l] || y >= pyr.h[l]) continue;
+        if (l == 2 && !(x == gcx && y == gcy)) {
+            const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
+            if (!gate_contains(g, (double)fx, (double)fy)) continue;
         }
-        __syncthreads();
-        const int st = s_tsum[0], stt = s_tsum[1];
-        double key = -3.0;
-        int idx = 0x7fffffff;
-        for (int c = tid; c < cw * cw; c += 256) {
-            const int ox = c % cw, oy = c / cw, x = x0 + ox, y = y0 + oy;
-            if (x < 0 || y < 0 || x >= pyr.w[l] || y >= pyr.h[l]) continue;
-            if (l == 2 && !(x == s_geom[0] && y == s_geom[1])) {
-                const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
-                if (!gate_contains(g, (double)fx, (double)fy)) continue;
-            }
-            const double kk = ncc_key(s_win, pitch, ox, oy, s_t, st, stt);
-            if (kk > key) { key = kk; idx = c; } // c ascending per thread: first maximum kept
-        }
-        block_argmax(key, idx, s_key, s_idx);
-        if (idx != 0x7fffffff) { bx = x0 + idx % cw; by = y0 + idx / cw; }
-        bkey = key; // -3 when this level had no candidate (position carried over, as the CPU loop does)
+        const double kk = ncc_key(s_win, pitch, ox, oy, s_t, st, stt);
+        if (kk > key) { key = kk; idx = c; } // c ascending per thread: first maximum kept
     }
+    block_argmax(key, idx, s_key, s_idx);
+    if (idx != 0x7fffffff) { bx = x0 + idx % cw; by = y0 + idx / cw; }
+    bkey = key;
+}
+
+// What follows the level-0 search of prediction slot k, by the whole workgroup: the acceptance test and the slot's entries of the
+// match tables.  SUBPIX (ekf_set_subpixel_matches): the keys of the best pixel's four level-0 neighbours are evaluated first and
+// each axis of the reported position is moved by subpix_offset; counts then receives the fitted / integer axes of the valid
+// matches.  SUBPIX = false is the integer matcher as it was.  s_t and s_tsum still hold the level-0 template and its sums.
+template <bool SUBPIX>
+__device__ __forceinline__ void ncc_finish_slot(const Pyr &pyr, const Gate &g, int k, int bx, int by, double bkey, uint8_t *s_win,
+                                                const uint8_t *s_t, const int *s_tsum, double *s_key, int *mt_valid, EkfKeypoint *mt_xy,
+                                                float *mt_dist, int *counts)
+{
+    const int tid = threadIdx.x;
     if constexpr (SUBPIX) {
-        // bkey is uniform over the block.  s_t and s_tsum still hold the level-0 template and its sums; every read of s_win
-        // and s_key lies before the barrier that ends block_argmax.
+        // bkey is uniform over the block; every read of s_win and s_key lies before the barrier that ends block_argmax.
         if (bkey >= 0.0) {
             constexpr int SP = 3 + 2 * NCC_R; // 13: the 3x3 candidates around (bx, by) and their 5-pixel border
             if (tid < SP * SP) s_win[tid] = (uint8_t)pyr_at(pyr, 0, bx - 1 - NCC_R + tid % SP, by - 1 - NCC_R + tid / SP);
@@ -360,6 +343,239 @@ k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab
         mt_xy[k] = p;
         mt_dist[k] = ok ? (float)(1.0 - sqrt(bkey)) : 0.f;
     }
+}
+
+// gate, coarse centre and UNCAPPED coarse radius of a prediction (one lane)
+__device__ __forceinline__ void ncc_slot_geometry(double pu, double pv, const double *S, Gate *g, int *cx, int *cy, int *rad)
+{
+    float axes[2];
+    double angle;
+    ellipse_from_cov(S, axes, &angle);
+    const int aw = (int)rintf(axes[0]), ah = (int)rintf(axes[1]);
+    // (always_inline: with several call sites the compiler would stop inlining it, in the integer matcher too)
+    [[clang::always_inline]] gate_from_ellipse((float)pu, (float)pv, aw, ah, angle, g);
+    const int major = aw > ah ? aw : ah;
+    *cx = to_level(pu, 2);
+    *cy = to_level(pv, 2);
+    *rad = (major >> 2) + 1; // major <= INT_MAX: no overflow
+}
+
+// One workgroup per prediction slot.  The coarse level covers the square of radius min(rad, NCC_MAXRAD) around the prediction: a
+// gate whose major semi-axis is 64 px or more is searched within +-16 coarse pixels (about +-66 px) only.  skip_wide (wide search,
+// DESIGN.md 4.8): such a slot is left to k_ncc_wide_coarse / k_ncc_wide_finish and this workgroup returns without writing anything.
+template <bool SUBPIX>
+__global__ void __launch_bounds__(256)
+k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *tmpl,
+            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0, int *counts, int skip_wide)
+{
+    __shared__ Gate g;
+    __shared__ int s_geom[4]; // c2x, c2y, rad, skipped
+    __shared__ uint8_t s_win[NCC_WIN * NCC_WIN + 3];
+    __shared__ uint8_t s_t[NCC_TT + 3];
+    __shared__ int s_tsum[2];
+    __shared__ double s_key[4];
+    __shared__ int s_idx[4];
+
+    const int k = slot0 + (int)blockIdx.x, tid = threadIdx.x; // slot0: see launch_match_ncc_slots
+    const int fi = plist[k];
+    if (tid == 0) {
+        int rad;
+        ncc_slot_geometry(uv_tab[2 * fi], uv_tab[2 * fi + 1], S_tab + 4 * fi, &g, &s_geom[0], &s_geom[1], &rad);
+        s_geom[2] = min(rad, NCC_MAXRAD);
+        s_geom[3] = skip_wide && rad > NCC_MAXRAD;
+    }
+    __syncthreads();
+    if (s_geom[3]) return; // uniform
+
+    int bx = s_geom[0], by = s_geom[1];
+    double bkey = -3.0;
+    for (int l = 2; l >= 0; --l) {
+        // candidate window at this level: coarse = the gated square around the prediction, finer = 4x4 children
+        int x0, y0, cw;
+        if (l == 2) { x0 = s_geom[0] - s_geom[2]; y0 = s_geom[1] - s_geom[2]; cw = 2 * s_geom[2] + 1; }
+        else { x0 = 2 * bx - 1; y0 = 2 * by - 1; cw = 4; }
+        ncc_search_level(pyr, l, x0, y0, cw, tmpl + ((size_t)fi * 3 + l) * NCC_TT, g, s_geom[0], s_geom[1], s_win, s_t, s_tsum, s_key,
+                         s_idx, bx, by, bkey);
+    }
+    ncc_finish_slot<SUBPIX>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts);
+}
+
+// ---- wide search ----------------------------------------------------------------------------
+// A slot whose uncapped coarse radius exceeds NCC_MAXRAD has its coarse level searched over the whole gate within the frame: the
+// result is what k_ncc_match would give with NCC_MAXRAD unbounded.  Three launches: the wide slots are listed in slot order, every
+// 32 x 32 tile of a slot's candidate box is searched by a workgroup of its own, and one workgroup per slot reduces the tiles'
+// results and runs the two finer levels and the tail that k_ncc_match runs.
+struct WideSlot {
+    Gate g;
+    int slot, cx, cy;       // prediction slot, coarse pixel of the prediction
+    int x0, y0, x1, y1;     // candidate box at the coarse level, clamped to the frame, inclusive (empty: x1 < x0 or y1 < y0)
+    int tx, ty;             // tiles of the box
+    int pad;
+};
+struct WidePartial {
+    double key;             // best key of the tile (-3: no candidate)
+    int idx;                // its pixel as y * w2 + x (0x7fffffff: none): raster order over the whole level
+    int ncand;              // candidates evaluated
+};
+struct WideTotals {         // behind the cap records of d.wide_list
+    unsigned long long ncand; // candidates of the slots finished so far
+    unsigned done, pad;       // slots finished
+};
+static_assert(sizeof(WideTotals) == NCC_WIDE_TOTALS_BYTES, "engine.h sizes the tables");
+static_assert(sizeof(WideSlot) == NCC_WIDE_SLOT_BYTES && sizeof(WidePartial) == NCC_WIDE_PARTIAL_BYTES, "engine.h sizes the tables");
+constexpr int WIDE_WIN = NCC_WIDE_TILE + 2 * NCC_R; // 42
+
+// One lane per prediction slot, one workgroup: the wide slots are compacted in slot order by a block scan, 1024 slots per pass.
+__global__ void __launch_bounds__(1024)
+k_ncc_wide_classify(const int *plist, const int *d_npred, int n_pred, const double *uv_tab, const double *S_tab, int w2, int h2,
+                    WideSlot *list, WideTotals *totals, int *counts)
+{
+    __shared__ int s_wtot[16];
+    const int tid = threadIdx.x, n = min(n_pred, *d_npred);
+    int base = 0;
+    for (int k0 = 0; k0 < n; k0 += 1024) { // uniform
+        const int k = k0 + tid;
+        WideSlot ws;
+        int wide = 0;
+        if (k < n) {
+            const int fi = plist[k];
+            int rad;
+            ncc_slot_geometry(uv_tab[2 * fi], uv_tab[2 * fi + 1], S_tab + 4 * fi, &ws.g, &ws.cx, &ws.cy, &rad);
+            wide = rad > NCC_MAXRAD;
+            rad = min(rad, max(w2, h2)); // a huge or degenerate S: the box is the frame, and nothing below overflows
+            ws.slot = k;
+            ws.x0 = (int)max((long long)ws.cx - rad, 0LL);
+            ws.y0 = (int)max((long long)ws.cy - rad, 0LL);
+            ws.x1 = (int)min((long long)ws.cx + rad, (long long)w2 - 1);
+            ws.y1 = (int)min((long long)ws.cy + rad, (long long)h2 - 1);
+            const bool empty = ws.x1 < ws.x0 || ws.y1 < ws.y0;
+            ws.tx = empty ? 0 : (ws.x1 - ws.x0) / NCC_WIDE_TILE + 1;
+            ws.ty = empty ? 0 : (ws.y1 - ws.y0) / NCC_WIDE_TILE + 1;
+            ws.pad = 0;
+        }
+        int total;
+        const int pos = block_exclusive_scan_1024(wide, s_wtot, &total);
+        if (wide) list[base + pos] = ws;
+        base += total;
+        __syncthreads(); // s_wtot is written again by the next pass
+    }
+    if (tid == 0) {
+        counts[CNT_WIDE_SLOTS] = base;
+        counts[CNT_WIDE_CANDS] = 0;
+        totals->ncand = 0;
+        totals->done = 0;
+    }
+}
+
+// grid = (tiles of the coarse level, prediction slots): workgroup (t, j) searches tile t of the j-th wide slot's box and writes one
+// partial result.  The sums of ncc_key are integers, so the tile's candidates give the bits k_ncc_match would give.
+__global__ void __launch_bounds__(256)
+k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot *list, const int *counts, WidePartial *part, int max_tiles)
+{
+    __shared__ uint8_t s_win[WIDE_WIN * WIDE_WIN];
+    __shared__ uint8_t s_t[NCC_TT + 3];
+    __shared__ int s_tsum[2];
+    __shared__ double s_key[4];
+    __shared__ int s_idx[4];
+    __shared__ int s_cnt[4];
+
+    const int j = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    if (j >= counts[CNT_WIDE_SLOTS]) return;
+    const WideSlot &ws = list[j];
+    const int ntx = ws.tx;
+    if (tile >= ntx * ws.ty) return;
+    const int cx = ws.cx, cy = ws.cy;
+    const int tx0 = ws.x0 + (tile % ntx) * NCC_WIDE_TILE, ty0 = ws.y0 + (tile / ntx) * NCC_WIDE_TILE;
+    const int cwx = min(NCC_WIDE_TILE, ws.x1 - tx0 + 1), cwy = min(NCC_WIDE_TILE, ws.y1 - ty0 + 1); // inside the frame: the box is
+    const Gate g = ws.g;
+    const int fi = plist[ws.slot];
+    const int wr = cwx + 2 * NCC_R, hr = cwy + 2 * NCC_R;
+    for (int i = tid; i < WIDE_WIN * hr; i += 256) {
+        const int ix = i % WIDE_WIN, iy = i / WIDE_WIN;
+        if (ix < wr) s_win[i] = (uint8_t)pyr_at(pyr, 2, tx0 - NCC_R + ix, ty0 - NCC_R + iy);
+    }
+    if (tid < NCC_TT) s_t[tid] = tmpl[((size_t)fi * 3 + 2) * NCC_TT + tid];
+    __syncthreads();
+    if (tid == 0) {
+        int st = 0, stt = 0;
+        for (int i = 0; i < NCC_TT; ++i) { st += s_t[i]; stt += s_t[i] * s_t[i]; }
+        s_tsum[0] = st; s_tsum[1] = stt;
+    }
+    __syncthreads();
+    const int st = s_tsum[0], stt = s_tsum[1], w2 = pyr.w[2];
+    double key = -3.0;
+    int idx = 0x7fffffff, ncand = 0;
+    for (int c = tid; c < NCC_WIDE_TILE * NCC_WIDE_TILE; c += 256) {
+        const int ox = c % NCC_WIDE_TILE, oy = c / NCC_WIDE_TILE, x = tx0 + ox, y = ty0 + oy;
+        if (ox >= cwx || oy >= cwy) continue;
+        if (!(x == cx && y == cy)) {
+            const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
+            if (!gate_contains(g, (double)fx, (double)fy)) continue;
+        }
+        const double kk = ncc_key(s_win, WIDE_WIN, ox, oy, s_t, st, stt);
+        ++ncand;
+        if (kk > key) { key = kk; idx = y * w2 + x; } // (y, x) ascending per thread: first maximum kept
+    }
+    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = ncand;
+    block_argmax(key, idx, s_key, s_idx); // (its barriers order s_cnt too)
+    if (tid == 0) {
+        WidePartial p;
+        p.key = key;
+        p.idx = idx;
+        p.ncand = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        part[(size_t)j * max_tiles + tile] = p;
+    }
+}
+
+// One workgroup per wide slot: the best of its tiles (larger key, then the smaller (y, x): block_argmax's rule, whatever the order
+// of the tiles), then levels 1 and 0 and the tail of k_ncc_match.
+template <bool SUBPIX>
+__global__ void __launch_bounds__(256)
+k_ncc_wide_finish(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot *list, const WidePartial *part, int max_tiles,
+                  WideTotals *totals, int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int *counts)
+{
+    __shared__ Gate g;
+    __shared__ uint8_t s_win[14 * 14 + 4]; // 4 x 4 children and their border; the 13 x 13 window of the sub-pixel fit
+    __shared__ uint8_t s_t[NCC_TT + 3];
+    __shared__ int s_tsum[2];
+    __shared__ double s_key[4];
+    __shared__ int s_idx[4];
+    __shared__ int s_cnt[4];
+
+    const int j = blockIdx.x, tid = threadIdx.x;
+    if (j >= counts[CNT_WIDE_SLOTS]) return;
+    const WideSlot &ws = list[j];
+    const int k = ws.slot, fi = plist[k], ntiles = ws.tx * ws.ty;
+    if (tid == 0) g = ws.g;
+    double key = -3.0;
+    int idx = 0x7fffffff, ncand = 0;
+    for (int t = tid; t < ntiles; t += 256) {
+        const WidePartial p = part[(size_t)j * max_tiles + t];
+        ncand += p.ncand;
+        if (p.key > key || (p.key == key && p.idx < idx)) { key = p.key; idx = p.idx; }
+    }
+    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = ncand;
+    block_argmax(key, idx, s_key, s_idx); // (its barriers order g and s_cnt too)
+    if (tid == 0) {
+        // the candidates are summed in 64 bits by plain atomic adds (a compare-and-swap loop on one counter by a thousand workgroups
+        // took milliseconds); the slot that finishes last writes the saturated sum to the counter block
+        atomicAdd(&totals->ncand, (unsigned long long)(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]));
+        __threadfence();
+        if (atomicAdd(&totals->done, 1u) == (unsigned)counts[CNT_WIDE_SLOTS] - 1u) {
+            __threadfence();
+            const unsigned long long sum = atomicAdd(&totals->ncand, 0ull);
+            counts[CNT_WIDE_CANDS] = sum > 0x7fffffffull ? 0x7fffffff : (int)sum;
+        }
+    }
+    int bx = ws.cx, by = ws.cy;
+    if (idx != 0x7fffffff) { bx = idx % pyr.w[2]; by = idx / pyr.w[2]; }
+    double bkey = key;
+    for (int l = 1; l >= 0; --l)
+        ncc_search_level(pyr, l, 2 * bx - 1, 2 * by - 1, 4, tmpl + ((size_t)fi * 3 + l) * NCC_TT, g, 0, 0, s_win, s_t, s_tsum, s_key, s_idx,
+                         bx, by, bkey);
+    ncc_finish_slot<SUBPIX>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts);
 }
 
 static Pyr pyr_of(const EkfEngine *e)
@@ -410,7 +626,7 @@ static const uint8_t *match_templates(EkfEngine *e, int n_pred)
 }
 
 // the NCC search of the prediction slots [s_lo, s_hi); subpix: with the parabola fit, whose axis counters it zeroes first
-static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_hi, bool subpix)
+static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_hi, bool subpix, bool skip_wide = false)
 {
     if (subpix) {
         (void)hipMemsetAsync(e->d.counts + CNT_SUBPIX_FIT, 0, sizeof(int), e->stream);
@@ -419,16 +635,30 @@ static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_h
     if (s_hi <= s_lo) return;
     auto kern = subpix ? k_ncc_match<true> : k_ncc_match<false>;
     kern<<<s_hi - s_lo, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, tmpl, e->d.mt_valid, e->d.mt_xy,
-                                             e->d.mt_dist, s_lo, e->d.counts);
+                                             e->d.mt_dist, s_lo, e->d.counts, skip_wide ? 1 : 0);
 }
 
-void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix)
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide)
 {
     const uint8_t *tmpl = match_templates(e, n_pred);
-    match_ncc_slots(e, tmpl, 0, n_pred, subpix);
+    WideSlot *list = (WideSlot *)e->d.wide_list;
+    WideTotals *totals = (WideTotals *)((uint8_t *)e->d.wide_list + (size_t)e->cap * NCC_WIDE_SLOT_BYTES);
+    if (wide && n_pred > 0) // before k_ncc_match: it zeroes CNT_WIDE_CANDS, and nothing of the wide path depends on the narrow one
+        k_ncc_wide_classify<<<1, 1024, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, n_pred, e->d.pred_uv, e->d.pred_S, e->img.w[2],
+                                                       e->img.h[2], list, totals, e->d.counts);
+    match_ncc_slots(e, tmpl, 0, n_pred, subpix, wide);
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
+        if (wide) (void)hipMemsetAsync(e->d.counts + CNT_WIDE_SLOTS, 0, 2 * sizeof(int), e->stream);
         return;
+    }
+    if (wide) { // k_ncc_match has skipped the wide slots (and left their sub-pixel counts to k_ncc_wide_finish)
+        const int tiles = ncc_wide_tiles(e->img.w[2], e->img.h[2]);
+        WidePartial *part = (WidePartial *)e->d.wide_part;
+        k_ncc_wide_coarse<<<dim3(tiles, n_pred), 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, e->d.counts, part, e->wide_tiles);
+        auto fin = subpix ? k_ncc_wide_finish<true> : k_ncc_wide_finish<false>;
+        fin<<<n_pred, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, part, e->wide_tiles, totals, e->d.mt_valid, e->d.mt_xy, e->d.mt_dist,
+                                            e->d.counts);
     }
     launch_match_compact_slots(e, n_pred, e->d.mt_xy);
 }

@@ -98,6 +98,8 @@ ABI = {
     "ekf_get_match_templates": (_i, [_vp, _vp, _i, _vp]),
     "ekf_set_subpixel_matches": (_i, [_vp, _i]),
     "ekf_get_subpixel_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "ekf_set_ncc_wide_search": (_i, [_vp, _i]),
+    "ekf_get_ncc_wide_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_step_image": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(EkfStepInfo)]),
     "ekf_detect_new_features": (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, C.POINTER(_i)]),
     "ekf_images_upload": (_i, [_vp, _i, _vp, _i, _i, _i, _i]),
@@ -538,6 +540,17 @@ class EkfEngine:
         """(axes moved by the fit, axes left at the integer) over the matches of the last NCC match"""
         a, b = _i(0), _i(0)
         self._chk(self.L.ekf_get_subpixel_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def set_ncc_wide_search(self, on=True):
+        """NCC gates larger than the 43 x 43 coarse window (major semi-axis of 64 px or more) are searched whole (DESIGN.md 4.8);
+        off: within 16 coarse pixels of the prediction"""
+        self._chk(self.L.ekf_set_ncc_wide_search(self.h, 1 if on else 0))
+
+    def ncc_wide_counts(self):
+        """(predictions searched wide, coarse candidates evaluated for them) in the last NCC match"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_ncc_wide_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def step_image(self, image):

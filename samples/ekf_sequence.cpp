@@ -1,11 +1,12 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
 // the map as 3-D points with their standard deviations (ImageEKF::writeMapPly).  Matcher mode B (NCC templates), so no
 // OpenCV is needed.  --warp-templates (anywhere after imgdir/): the templates are re-rendered from the predicted viewpoint before
 // every search (ImageEKF::setTemplateWarp).  --subpixel (likewise): NCC matches at sub-pixel positions (ImageEKF::setSubpixelMatches).
+// --wide-search (likewise): gates larger than the coarse search window are searched whole (ImageEKF::setWideSearch).
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -16,16 +17,16 @@
 
 int main(int argc, const char *argv[])
 {
-    bool warp = false, subpix = false; // the flags are taken out of the argument list; the positional arguments keep their places
+    bool warp = false, subpix = false, wide = false; // the flags are taken out of the argument list; the positional arguments keep their places
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel") {
-            (std::string(argv[i]) == "--subpixel" ? subpix : warp) = true;
+        if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search") {
+            (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc;
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -40,7 +41,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -58,10 +59,11 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp or sub-pixel matches asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches or the wide search asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         extendedKalmanFilter.setSubpixelMatches(subpix);
+        extendedKalmanFilter.setWideSearch(wide);
         extendedKalmanFilter.init(image);
         std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
         image = generator.getNextImage();
@@ -81,6 +83,11 @@ int main(int argc, const char *argv[])
                 int refined = 0, integer = 0;
                 ekf_get_subpixel_counts(extendedKalmanFilter.engine(), &refined, &integer);
                 std::printf("        match axes refined %d, left at the integer %d\n", refined, integer);
+            }
+            if (wide) {
+                int slots = 0, cands = 0;
+                ekf_get_ncc_wide_counts(extendedKalmanFilter.engine(), &slots, &cands);
+                std::printf("        gates searched wide %d, coarse candidates %d\n", slots, cands);
             }
             image = generator.getNextImage();
         }

@@ -289,6 +289,32 @@ int ekf_set_ncc_wide_search(EkfEngine *e, int on);
 /* of the last NCC match: predictions searched wide, and the coarse candidates evaluated for them (saturating at
  * INT_MAX); 0 and 0 with the mode off */
 int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candidates);
+/* Patch normals (opt-in; off: the path above, bit for bit; needs the template warp).  The warp's patch plane faces the
+ * camera that captured the feature; with this mode on each feature's plane has a slope (p, q) in that camera's axes --
+ * normal n = R(q0) (p, q, -1) / |(p, q, -1)| in world axes -- estimated on the device by aligning the stored source
+ * patches to the current frame: ekf_step_image / ekf_step_staged_image run one estimator step per frame,
+ * after the frame's last update, for the features that ended it as inliers or rescued, and the warp renders a feature
+ * that has an estimate with it.  A feature without an estimate (updates = 0: fresh capture, re-capture, no step yet)
+ * warps exactly as with the template warp alone.  Allocates 48 + 32 bytes per feature of capacity on first use.
+ * EKF_ERR_INVALID_ARG on a sharded engine and while the template warp is off; ekf_set_template_warp(e, 0) turns this
+ * mode off too; EKF_IMAGE_MATCHER_KEYPOINTS ignores the mode. */
+typedef struct EkfPatchNormal {
+    double pq[2];     /* slope of the patch plane in the capture camera's axes */
+    double info[3];   /* its information matrix: (0,0), (0,1), (1,1) */
+    double normal[3]; /* unit normal in world axes */
+    int32_t updates;  /* estimator steps taken; 0: no estimate, pq / normal are the facing-the-camera rule, info the prior */
+    int32_t pad;
+} EkfPatchNormal;
+int ekf_set_patch_normals(EkfEngine *e, int on);
+/* one estimator step, as a stage of its own, on the current image and state: matches[i].imagePos (rounded to whole
+ * pixels) is where feature matches[i].featureIndex is seen; a feature may be listed once */
+int ekf_refine_patch_normals(EkfEngine *e, const EkfMatch *matches, int M);
+/* a feature without a source patch reports zeros */
+int ekf_get_patch_normals(EkfEngine *e, const int32_t *feat_idx, int count, EkfPatchNormal *out);
+/* sets a feature's estimate (tests; restoring a saved map); its update count becomes at least 1 */
+int ekf_set_patch_normal(EkfEngine *e, int feat, const double pq[2], const double info[3]);
+/* features updated / left alone by the last estimator run (a step with the mode on, or ekf_refine_patch_normals) */
+int ekf_get_patch_normal_counts(const EkfEngine *e, int *updated, int *skipped);
 int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, int stride, int channels,
                    EkfStepInfo *info); /* (matcher: ekf_set_image_matcher) */
 /* detectNewImageFeatures(image, featuresPrediction, newImageFeaturesMaxSize, newImageFeatures)

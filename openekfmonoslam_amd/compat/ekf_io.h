@@ -518,22 +518,33 @@ inline void mapPoints(EkfEngine *e, std::vector<EkfMapPoint> &points)
 
 // ASCII PLY: one vertex per feature in map order; x y z = world position, sx sy sz = square roots of the diagonal of its
 // covariance, inverse_depth = 1 while the feature is still in the inverse-depth parametrisation.  %.17g: the numbers
-// parse back to the same doubles.
-inline void writeMapPly(EkfEngine *e, const std::string &path)
+// parse back to the same doubles.  normals (the patch-normal mode is on, ekf_set_patch_normals): nx ny nz = the unit normal
+// of the feature's patch in world axes behind sz (zeros for a feature without a source patch).
+inline void writeMapPly(EkfEngine *e, const std::string &path, bool normals = false)
 {
     std::vector<EkfMapPoint> pts;
     mapPoints(e, pts);
+    std::vector<EkfPatchNormal> pn(pts.size());
+    if (normals && !pts.empty()) {
+        std::vector<int32_t> idx(pts.size());
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int32_t)i;
+        if (ekf_get_patch_normals(e, idx.data(), (int)idx.size(), pn.data()) != EKF_OK)
+            throw std::runtime_error(std::string("ekf_get_patch_normals: ") + ekf_last_error(e));
+    }
     std::FILE *f = std::fopen(path.c_str(), "w");
     if (!f) throw std::runtime_error("cannot write " + path);
     std::fprintf(f, "ply\nformat ascii 1.0\ncomment OpenEKFMonoSLAM map: position and standard deviation per landmark\n");
     std::fprintf(f, "element vertex %d\n", (int)pts.size());
     std::fprintf(f, "property double x\nproperty double y\nproperty double z\n");
     std::fprintf(f, "property double sx\nproperty double sy\nproperty double sz\n");
+    if (normals) std::fprintf(f, "property double nx\nproperty double ny\nproperty double nz\n");
     std::fprintf(f, "property uchar inverse_depth\nend_header\n");
     for (size_t i = 0; i < pts.size(); ++i) {
         const EkfMapPoint &p = pts[i];
-        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g %d\n", p.xyz[0], p.xyz[1], p.xyz[2], std::sqrt(p.cov[0]),
-                     std::sqrt(p.cov[4]), std::sqrt(p.cov[8]), p.type == EKF_FEATURE_INVERSE_DEPTH ? 1 : 0);
+        std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g ", p.xyz[0], p.xyz[1], p.xyz[2], std::sqrt(p.cov[0]), std::sqrt(p.cov[4]),
+                     std::sqrt(p.cov[8]));
+        if (normals) std::fprintf(f, "%.17g %.17g %.17g ", pn[i].normal[0], pn[i].normal[1], pn[i].normal[2]);
+        std::fprintf(f, "%d\n", p.type == EKF_FEATURE_INVERSE_DEPTH ? 1 : 0);
     }
     if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + path);
 }
@@ -549,7 +560,7 @@ public:
     ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
-          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS)
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -642,7 +653,26 @@ public:
     // NCC templates re-rendered from the predicted viewpoint before every search (ekf_set_template_warp); call it before
     // init() so that the first features keep their source patches.  A setter, not a config key: the reference's
     // config.yml schema has none.  Ignored by the keypoint matcher.
-    void setTemplateWarp(bool on) { chk(ekf_set_template_warp(e_, on ? 1 : 0), "ekf_set_template_warp"); }
+    void setTemplateWarp(bool on)
+    {
+        chk(ekf_set_template_warp(e_, on ? 1 : 0), "ekf_set_template_warp");
+        if (!on) patchNormals_ = false; // the engine turns them off with the warp
+    }
+    // Patch normals estimated from the images, one estimator step per frame, and used by the template warp
+    // (ekf_set_patch_normals; needs setTemplateWarp(true) first).  writeMapPly then adds nx ny nz.
+    void setPatchNormals(bool on)
+    {
+        chk(ekf_set_patch_normals(e_, on ? 1 : 0), "ekf_set_patch_normals");
+        patchNormals_ = on;
+    }
+    // slope, information, world normal and update count per feature in map order
+    void patchNormals(std::vector<EkfPatchNormal> &out)
+    {
+        out.resize((size_t)ekf_num_features(e_));
+        std::vector<int32_t> idx(out.size());
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int32_t)i;
+        if (!out.empty()) chk(ekf_get_patch_normals(e_, idx.data(), (int)idx.size(), out.data()), "ekf_get_patch_normals");
+    }
     // NCC matches at sub-pixel positions: a parabola through the best pixel's and its neighbours' scores, per axis
     // (ekf_set_subpixel_matches); at any time, it takes effect with the next step.  A setter for the same reason.
     void setSubpixelMatches(bool on) { chk(ekf_set_subpixel_matches(e_, on ? 1 : 0), "ekf_set_subpixel_matches"); }
@@ -651,7 +681,7 @@ public:
     void setWideSearch(bool on) { chk(ekf_set_ncc_wide_search(e_, on ? 1 : 0), "ekf_set_ncc_wide_search"); }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
-    void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path); }
+    void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path, patchNormals_); }
     EkfEngine *engine() { return e_; }
     int steps() const { return steps_; }
     const EkfCamera &camera() const { return cam_; }
@@ -752,6 +782,7 @@ private:
     std::string outputPath_;
     double detectorThreshold_;
     bool keypoints_; // EKF_IMAGE_MATCHER_KEYPOINTS: new features keep a BRIEF-32 descriptor, no templates
+    bool patchNormals_; // setPatchNormals(true): writeMapPly adds the normals
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

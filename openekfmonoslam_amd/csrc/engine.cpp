@@ -137,7 +137,7 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -654,6 +654,7 @@ int ekf_set_state(EkfEngine *e, const double x13[13], int n_features, const doub
     HIPCHK(hipMemset(e->d.feat_times_predicted, 0, (size_t)e->cap * sizeof(unsigned)));
     HIPCHK(hipMemset(e->d.feat_times_matched, 0, (size_t)e->cap * sizeof(unsigned)));
     if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * 9 * sizeof(double))); // template warp: no feature has a source patch
+    if (e->d.wnorm) HIPCHK(hipMemset(e->d.wnorm, 0, (size_t)e->cap * sizeof(PatchNormalRec))); // patch normals: no feature has an estimate
     e->last_match_warped = false; // d.wtmpl belongs to the map the last match saw
     return EKF_OK;
 }
@@ -817,6 +818,7 @@ int ekf_add_features(EkfEngine *e, const double *uv, const uint8_t *desc32, int 
     HIPCHK(hipMemsetAsync(e->d.feat_times_predicted + e->N, 0, (size_t)count * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->d.feat_times_matched + e->N, 0, (size_t)count * 4, e->stream));
     if (e->d.wpose) HIPCHK(hipMemsetAsync(e->d.wpose + 9 * (size_t)e->N, 0, (size_t)count * 9 * sizeof(double), e->stream));
+    if (e->d.wnorm) HIPCHK(hipMemsetAsync(e->d.wnorm + e->N, 0, (size_t)count * sizeof(PatchNormalRec), e->stream));
     launch_add_features(e, d_uv, count, d_Jpo, d_Jhr);
     for (int j = 0; j < count; ++j) {
         e->h_type.push_back(EKF_FEATURE_INVERSE_DEPTH);
@@ -861,6 +863,8 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
         HIPCHK(hipMemcpy(wsrc.data(), e->d.wsrc, wsrc.size(), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(wpose.data(), e->d.wpose, wpose.size() * 8, hipMemcpyDeviceToHost));
     }
+    std::vector<PatchNormalRec> wnorm(e->d.wnorm ? (size_t)N : 0); // patch normals follow their features too
+    if (!wnorm.empty()) HIPCHK(hipMemcpy(wnorm.data(), e->d.wnorm, wnorm.size() * sizeof(PatchNormalRec), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(pos.data(), e->d.feat_pos, pos.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(desc.data(), e->d.feat_desc, desc.size(), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tp.data(), e->d.feat_times_predicted, (size_t)N * 4, hipMemcpyDeviceToHost));
@@ -876,6 +880,7 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
             std::memmove(&wsrc[(size_t)w * WSRC], &wsrc[(size_t)i * WSRC], WSRC);
             std::memmove(&wpose[(size_t)w * 9], &wpose[(size_t)i * 9], 9 * sizeof(double));
         }
+        if (!wnorm.empty()) wnorm[w] = wnorm[i];
         tp[w] = tp[i];
         tm[w] = tm[i];
         e->h_type[w] = e->h_type[i];
@@ -897,6 +902,7 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
             HIPCHK(hipMemcpy(e->d.wsrc, wsrc.data(), (size_t)w * WSRC, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(e->d.wpose, wpose.data(), (size_t)w * 9 * 8, hipMemcpyHostToDevice));
         }
+        if (!wnorm.empty()) HIPCHK(hipMemcpy(e->d.wnorm, wnorm.data(), (size_t)w * sizeof(PatchNormalRec), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_times_predicted, tp.data(), (size_t)w * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_times_matched, tm.data(), (size_t)w * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_type, e->h_type.data(), (size_t)w * 4, hipMemcpyHostToDevice));
@@ -1613,6 +1619,11 @@ restart:
         // + updateMapFeatures for the low-innovation inliers (MapManagement.cpp:88-113), same launch
         launch_partition(e, e->d.matches, M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx);
     }
+    // patch normals: the estimator runs behind the frame's last update on the inliers and the rescued; d.msel is
+    // overwritten by the rescue, so each list is copied behind its partition
+    const bool normals = use_ncc && e->pn_on;
+    if (normals && ni > 0)
+        HIPCHK(hipMemcpyAsync(e->d.pn_list, e->d.msel, (size_t)ni * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     li.n_inliers = ni;
     li.n_outliers = no;
     tm.mark();
@@ -1652,13 +1663,20 @@ restart:
     }
     li.n_rescued = nr;
     tm.mark();
+    if (normals && nr > 0)
+        HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     // 10. high-innovation update (:529-532)
     if ((rc = update_dev(e, nr, true, lean))) return rc;
     tm.mark();
+    if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
     if (dev_counts && e->async_errors) {
         e->err_unread = true; // reported by the next step, ekf_synchronize or ekf_get_state
     } else {
         if ((rc = read_counts(e))) return rc;
+        if (normals) {
+            e->pn_counts[0] = e->h_counts[CNT_PN_UPD];
+            e->pn_counts[1] = e->h_counts[CNT_PN_SKIP];
+        }
         if (detect) {
             e->step_kp_detected = e->h_counts[CNT_KP_FOUND];
             e->step_kp_kept = std::min(e->step_kp_detected, e->kcap);
@@ -2142,6 +2160,147 @@ int ekf_set_template_warp(EkfEngine *e, int on)
         }
     }
     e->warp_on = on != 0;
+    if (!e->warp_on) e->pn_on = false; // the patch normals live in the warp
+    return EKF_OK;
+}
+
+int ekf_set_patch_normals(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) {
+        e->err = "patch normals: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (!e->warp_on) {
+        e->err = "patch normals: the template warp is off (ekf_set_template_warp)";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (on && !e->d.wnorm) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        hipError_t st = dalloc(&e->d.wnorm, (size_t)e->cap); // zeroed: no feature has an estimate yet
+        if (st == hipSuccess) st = dalloc(&e->d.pn_list, (size_t)e->cap);
+        if (st != hipSuccess) {
+            if (e->d.wnorm) (void)hipFree(e->d.wnorm);
+            e->d.wnorm = nullptr;
+            e->err = std::string("patch normal tables: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    e->pn_on = on != 0;
+    return EKF_OK;
+}
+
+int ekf_refine_patch_normals(EkfEngine *e, const EkfMatch *matches, int M)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (!e->pn_on || !e->img.valid) {
+        e->err = "ekf_refine_patch_normals: the mode is off, or no image uploaded";
+        return EKF_ERR_INVALID_ARG;
+    }
+    int rc = validate_matches(e, matches, M);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if (M > 0) HIPCHK(hipMemcpyAsync(e->d.pn_list, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
+    launch_ncc_normal(e, M);
+    if ((rc = read_counts(e))) return rc; // (synchronises: the caller's list has been read)
+    e->pn_counts[0] = e->h_counts[CNT_PN_UPD];
+    e->pn_counts[1] = e->h_counts[CNT_PN_SKIP];
+    return check_async(e);
+}
+
+// R(q) as device_math.h's quat_to_rot
+static void host_quat_to_rot(const double *q, double *M)
+{
+    const double r = q[0], x = q[1], y = q[2], z = q[3];
+    const double r2 = r * r, x2 = x * x, y2 = y * y, z2 = z * z;
+    M[0] = r2 + x2 - y2 - z2; M[1] = 2 * (x * y - r * z); M[2] = 2 * (z * x + r * y);
+    M[3] = 2 * (x * y + r * z); M[4] = r2 - x2 + y2 - z2; M[5] = 2 * (y * z - r * x);
+    M[6] = 2 * (z * x - r * y); M[7] = 2 * (y * z + r * x); M[8] = r2 - x2 - y2 + z2;
+}
+
+int ekf_get_patch_normals(EkfEngine *e, const int32_t *feat_idx, int count, EkfPatchNormal *out)
+{
+    if (!e || count < 0 || (count > 0 && (!feat_idx || !out))) return EKF_ERR_INVALID_ARG;
+    for (int i = 0; i < count; ++i)
+        if (feat_idx[i] < 0 || feat_idx[i] >= e->N) return EKF_ERR_INVALID_ARG;
+    if (!e->d.wnorm) {
+        e->err = "ekf_get_patch_normals: the mode has never been on";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (count == 0) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const size_t N = (size_t)e->N;
+    std::vector<PatchNormalRec> rec(N);
+    std::vector<double> pose(9 * N), pos(6 * N);
+    std::vector<int> type(N);
+    HIPCHK(hipMemcpy(rec.data(), e->d.wnorm, N * sizeof(PatchNormalRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pose.data(), e->d.wpose, 9 * N * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos.data(), e->d.feat_pos, 6 * N * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(type.data(), e->d.feat_type, N * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < count; ++i) {
+        const size_t f = (size_t)feat_idx[i];
+        const double *ps = &pose[9 * f], *y = &pos[6 * f];
+        EkfPatchNormal o;
+        std::memset(&o, 0, sizeof(o));
+        if (ps[3] != 0.0 || ps[4] != 0.0 || ps[5] != 0.0 || ps[6] != 0.0) {
+            double R0[9];
+            host_quat_to_rot(ps + 3, R0);
+            if (rec[f].updates > 0) {
+                o.pq[0] = rec[f].pq[0];
+                o.pq[1] = rec[f].pq[1];
+                for (int k = 0; k < 3; ++k) o.info[k] = rec[f].info[k];
+                o.updates = rec[f].updates;
+            } else { // the rule of DESIGN.md 4.6 as a slope, and the first update's prior
+                double X[3] = {y[0], y[1], y[2]};
+                if (type[f] == EKF_FEATURE_INVERSE_DEPTH) {
+                    const double cp = std::cos(y[4]);
+                    X[0] += cp * std::sin(y[3]) / y[5];
+                    X[1] += -std::sin(y[4]) / y[5];
+                    X[2] += cp * std::cos(y[3]) / y[5];
+                }
+                const double w[3] = {X[0] - ps[0], X[1] - ps[1], X[2] - ps[2]};
+                const double h0 = R0[0] * w[0] + R0[3] * w[1] + R0[6] * w[2];
+                const double h1 = R0[1] * w[0] + R0[4] * w[1] + R0[7] * w[2];
+                const double h2 = R0[2] * w[0] + R0[5] * w[1] + R0[8] * w[2];
+                o.pq[0] = -h0 / h2;
+                o.pq[1] = -h1 / h2;
+                o.info[0] = o.info[2] = PN_PRIOR_INFO;
+            }
+            const double p = o.pq[0], q = o.pq[1], nrm = std::sqrt(p * p + q * q + 1.0);
+            for (int k = 0; k < 3; ++k) o.normal[k] = (R0[3 * k] * p + R0[3 * k + 1] * q - R0[3 * k + 2]) / nrm;
+        }
+        out[i] = o;
+    }
+    return EKF_OK;
+}
+
+int ekf_set_patch_normal(EkfEngine *e, int feat, const double pq[2], const double info[3])
+{
+    if (!e || !pq || !info || feat < 0 || feat >= e->N || !e->d.wnorm) return EKF_ERR_INVALID_ARG;
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(pq[k])) return EKF_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(info[k])) return EKF_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    PatchNormalRec rec;
+    HIPCHK(hipMemcpy(&rec, e->d.wnorm + feat, sizeof(rec), hipMemcpyDeviceToHost));
+    rec.pq[0] = pq[0];
+    rec.pq[1] = pq[1];
+    for (int k = 0; k < 3; ++k) rec.info[k] = info[k];
+    rec.updates = std::max(rec.updates, 1);
+    rec.pad = 0;
+    HIPCHK(hipMemcpy(e->d.wnorm + feat, &rec, sizeof(rec), hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+int ekf_get_patch_normal_counts(const EkfEngine *e, int *updated, int *skipped)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (updated) *updated = e->pn_counts[0];
+    if (skipped) *skipped = e->pn_counts[1];
     return EKF_OK;
 }
 

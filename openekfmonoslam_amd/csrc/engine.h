@@ -12,6 +12,7 @@
 
 #include "../../include/ekf_engine.h"
 #include "device_math.h"
+#include "patch_normal.h"
 
 namespace ekf {
 
@@ -61,6 +62,8 @@ enum {
     CNT_SUBPIX_FIT,   // sub-pixel NCC matches: axes of valid matches moved by the parabola fit (the others: CNT_SUBPIX_INT)
     CNT_WIDE_SLOTS,   // wide search: prediction slots whose gate exceeds the 43 x 43 window in the last NCC match (k_ncc_wide_classify)
     CNT_WIDE_CANDS,   // ... and the coarse candidates evaluated for them, saturating at INT_MAX (k_ncc_wide_finish)
+    CNT_PN_UPD,       // patch normals: features whose estimate the last estimator launch updated (k_ncc_normal)
+    CNT_PN_SKIP,      // ... and listed features it left alone (no source patch, no usable level, solve not finite)
     CNT_COUNT = 40    // (publish_counts_block / k_publish_counts copy with the lanes t < 64; the mirror page holds 64 ints)
 };
 constexpr int MAX_SHARD_WORLD = 16;
@@ -113,6 +116,9 @@ struct DeviceArrays {
     uint8_t *wsrc = nullptr;      // 3 levels x 41 x 41 source bytes per feature
     double *wpose = nullptr;      // 9 per feature: capture position r0, quaternion q0 (all zero: no source patch), capture pixel
     uint8_t *wtmpl = nullptr;     // the templates the match compares with the mode on: same layout as tmpl
+    // patch normals (ekf_set_patch_normals; allocated by its first call)
+    PatchNormalRec *wnorm = nullptr; // one record per feature, beside wpose (all zero: no estimate)
+    EkfMatch *pn_list = nullptr;     // the matches the estimator is handed: a frame's inliers, then its rescued (cap records)
     // wide search (ekf_set_ncc_wide_search; allocated by its first match)
     void *wide_list = nullptr;    // WideSlot per wide prediction slot, slot order (kernels_ncc.hip), cap records + one WideTotals
     void *wide_part = nullptr;    // WidePartial per (wide slot, tile of the coarse level): cap x wide_tiles records
@@ -282,6 +288,8 @@ struct EkfEngine {
     int subpix_counts[2] = {0, 0}; // axes fitted / left at the integer over the valid matches of the last NCC match
     bool wide_on = false;          // ekf_set_ncc_wide_search: gates beyond the 43 x 43 coarse window are searched whole
     int wide_counts[2] = {0, 0};   // wide slots / coarse candidates evaluated for them in the last NCC match
+    bool pn_on = false;            // ekf_set_patch_normals: patch normals estimated per frame and used by the warp
+    int pn_counts[2] = {0, 0};     // features updated / skipped by the last estimator launch
     int wide_tiles = 0;            // tiles per slot d.wide_part was allocated for (the coarse level's tile count)
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
@@ -434,6 +442,9 @@ void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);
 // template warp: source patches + capture pose of the listed features (keep = false: marks them "no source patch")
 void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep);
+// patch normals: one estimator step for the features of the M matches in d.pn_list against the current image and state; zeroes and
+// then counts CNT_PN_UPD / CNT_PN_SKIP
+void launch_ncc_normal(EkfEngine *e, int M);
 // subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7; wide: the slots whose gate exceeds the coarse window go
 // through the three kernels of DESIGN.md 4.8 instead (d.wide_list / d.wide_part sized for the current frame: engine.cpp)
 void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide);

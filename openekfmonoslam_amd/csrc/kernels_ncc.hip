@@ -78,9 +78,11 @@ constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S, WARP_R = WARP_S / 2;
 
 // block = (item, level): source patch; the level-0 block also writes the pose record (keep = 0: zeros = "no source patch")
 __global__ void __launch_bounds__(256)
-k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double *st, uint8_t *wsrc, double *wpose, int keep)
+k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double *st, uint8_t *wsrc, double *wpose, int keep,
+                   PatchNormalRec *wnorm)
 {
     const int i = blockIdx.x, l = blockIdx.y, fi = feat_idx[i];
+    if (l == 0 && threadIdx.x == 9 && wnorm) wnorm[fi] = PatchNormalRec{}; // patch normals: a capture resets the estimate
     if (l == 0 && threadIdx.x < 9) {
         const int t = threadIdx.x;
         wpose[9 * (size_t)fi + t] = !keep ? 0.0 : (t < 7 ? st[ST_X + t] : uv[2 * i + t - 7]);
@@ -91,12 +93,19 @@ k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double 
         wsrc[((size_t)fi * 3 + l) * WARP_SS + t] = (uint8_t)pyr_at(pyr, l, cx + t % WARP_S - WARP_R, cy + t / WARP_S - WARP_R);
 }
 
+// unit normal in world axes of the slope (p, q) in the capture camera's axes: R0 (p, q, -1) / |(p, q, -1)|
+__device__ __forceinline__ void pn_normal(const double *R0, double p, double q, double *n)
+{
+    const double nrm = sqrt(p * p + q * q + 1.0);
+    for (int i = 0; i < 3; ++i) n[i] = (R0[3 * i] * p + R0[3 * i + 1] * q - R0[3 * i + 2]) / nrm;
+}
+
 // One workgroup per prediction slot, 128 lanes per level (121 active): fp64, everything a lane touches after the staging
 // is in LDS (5 KB of source bytes, 30 doubles of constants).  Latency-bound like k_ncc_match: ~0.4 KFLOP and one 10-step
 // Newton solve per lane.  out already holds a copy of the stored templates; only whole warped levels are written.
 __global__ void __launch_bounds__(384)
 k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const double *st, CamD c, const double *feat_pos,
-           const int *feat_type, const uint8_t *wsrc, const double *wpose, uint8_t *out, int *counts)
+           const int *feat_type, const uint8_t *wsrc, const double *wpose, uint8_t *out, int *counts, const PatchNormalRec *wnorm)
 {
     __shared__ uint8_t s_src[3 * WARP_SS + 1];
     __shared__ double s_R[9], s_R0[9], s_n[3], s_r[3], s_r0[3], s_nXr, s_uv0[2];
@@ -125,9 +134,12 @@ k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const dou
         quat_to_rot(pose + 3, s_R0);
         const double a[3] = {pose[0] - X[0], pose[1] - X[1], pose[2] - X[2]};
         const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        const bool estimated = wnorm && wnorm[fi].updates > 0; // patch normals: n(p, q) instead of the rule
+        double pqn[3] = {0.0, 0.0, 1.0};
+        if (estimated) pn_normal(s_R0, wnorm[fi].pq[0], wnorm[fi].pq[1], pqn);
         double nXr = 0.0;
         for (int i = 0; i < 3; ++i) {
-            s_n[i] = a[i] / an;
+            s_n[i] = estimated ? pqn[i] : a[i] / an;
             s_r[i] = x[i];
             s_r0[i] = pose[i];
             nXr += s_n[i] * (X[i] - x[i]);
@@ -191,6 +203,241 @@ k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const dou
         const int nfb = s_bad[0] + s_bad[1] + s_bad[2];
         if (nfb) atomicAdd(counts + CNT_WARP_FB, nfb);
         if (nfb < 3) atomicAdd(counts + CNT_WARP_OK, 3 - nfb);
+    }
+}
+
+// ---- patch normals ---------------------------------------------------------------------------
+// One estimator step per listed match: the feature's source patches are aligned to the current frame around the match's pixel
+// and the slope (p, q) of its patch plane takes one information-filter step.  tests/patch_normal_ref.py is the definition; every
+// operation below is in its order (fp64, no contraction, sums in pixel order, then levels 0, 1, 2).
+
+// steps 2-4 of k_ncc_warp for one ray d (world axes) and one plane: level-0 position in the capture frame; false: not valid
+__device__ __forceinline__ bool pn_to_source(const CamD &c, const double *d, const double *n, double nXr, const double *r, const double *r0,
+                                             const double *R0, double *s)
+{
+    const double nd = n[0] * d[0] + n[1] * d[1] + n[2] * d[2];
+    if (!(nd < 0.0)) return false;
+    const double lam = nXr / nd;
+    if (!(lam > 0.0)) return false;
+    const double w[3] = {r[0] + lam * d[0] - r0[0], r[1] + lam * d[1] - r0[1], r[2] + lam * d[2] - r0[2]};
+    const double h0 = R0[0] * w[0] + R0[3] * w[1] + R0[6] * w[2];
+    const double h1 = R0[1] * w[0] + R0[4] * w[1] + R0[7] * w[2];
+    const double h2 = R0[2] * w[0] + R0[5] * w[1] + R0[8] * w[2];
+    if (!(h2 > 0.0)) return false;
+    distort(c, c.cx + c.fx * h0 / h2, c.cy + c.fy * h1 / h2, s);
+    return true;
+}
+
+// ray of the level-0 position (px, py) in world axes (step 2 of k_ncc_warp)
+__device__ __forceinline__ void pn_ray(const CamD &c, const double *R, double px, double py, double *d)
+{
+    const double pdx = px - c.cx, pdy = py - c.cy;
+    const double mx = c.dx * pdx, my = c.dy * pdy;
+    const double rd2 = mx * mx + my * my;
+    const double f = 1.0 + c.k1 * rd2 + c.k2 * rd2 * rd2;
+    const double hc[3] = {pdx * f / c.fx, pdy * f / c.fy, 1.0};
+    mat3_vec(R, hc, d);
+}
+
+constexpr int PN_VEC = 6; // vectors per level: the prediction at the five slopes, the measurement
+
+// One workgroup per match, 128 lanes per level (121 active, lanes 121..125 of level 0 carry the anchor at the five slopes).
+// Latency-bound: five plane intersections and Newton solves per lane, six barriers-separated serial sums of 121 terms by six lanes
+// per level (the order of the restatement), 18 KB of vectors and 5 KB of source bytes in LDS.
+__global__ void __launch_bounds__(384)
+k_ncc_normal(Pyr pyr, const EkfMatch *list, int M, int N, const double *st, CamD c, const double *feat_pos, const int *feat_type,
+             const uint8_t *wsrc, const double *wpose, PatchNormalRec *wnorm, int *counts)
+{
+    __shared__ uint8_t s_src[3 * WARP_SS + 1];
+    __shared__ double s_vec[3][PN_VEC][128];
+    __shared__ double s_sum[3][PN_VEC];
+    __shared__ double s_R[9], s_R0[9], s_n[5][3], s_nXr[5], s_r[3], s_r0[3], s_anc[5][2], s_pq[2];
+    __shared__ int s_bad[3], s_anchor[2], s_uv0l[3][2], s_ctr0[2];
+
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k >= M) return;
+    const int fi = list[k].featureIndex;
+    if (fi < 0 || fi >= N) return; // (the host validates the list)
+    const double *pose = wpose + 9 * (size_t)fi;
+    const bool has_src = pose[3] != 0.0 || pose[4] != 0.0 || pose[5] != 0.0 || pose[6] != 0.0; // uniform over the block
+    if (!has_src) {
+        if (tid == 0) atomicAdd(counts + CNT_PN_SKIP, 1);
+        return;
+    }
+    for (int i = tid; i < 3 * WARP_SS; i += 384) s_src[i] = wsrc[(size_t)fi * 3 * WARP_SS + i];
+    if (tid < 3) s_bad[tid] = 0;
+    if (tid == 0) {
+        const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)fi;
+        double X[3] = {y[0], y[1], y[2]};
+        if (feat_type[fi] == EKF_FEATURE_INVERSE_DEPTH) {
+            double m[3];
+            dir_vec(y[3], y[4], m);
+            X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
+        }
+        quat_to_rot(x + 3, s_R);
+        quat_to_rot(pose + 3, s_R0);
+        double p, q;
+        if (wnorm[fi].updates > 0) {
+            p = wnorm[fi].pq[0];
+            q = wnorm[fi].pq[1];
+        } else { // first update: the rule of 4.6 as a slope
+            const double w[3] = {X[0] - pose[0], X[1] - pose[1], X[2] - pose[2]};
+            const double h0 = s_R0[0] * w[0] + s_R0[3] * w[1] + s_R0[6] * w[2];
+            const double h1 = s_R0[1] * w[0] + s_R0[4] * w[1] + s_R0[7] * w[2];
+            const double h2 = s_R0[2] * w[0] + s_R0[5] * w[1] + s_R0[8] * w[2];
+            p = -h0 / h2;
+            q = -h1 / h2;
+        }
+        s_pq[0] = p;
+        s_pq[1] = q;
+        for (int j = 0; j < 5; ++j) { // the slope, p + h, p - h, q + h, q - h
+            const double dp = j == 1 ? PN_FD_STEP : (j == 2 ? -PN_FD_STEP : 0.0), dq = j == 3 ? PN_FD_STEP : (j == 4 ? -PN_FD_STEP : 0.0);
+            double n[3];
+            pn_normal(s_R0, p + dp, q + dq, n);
+            double nXr = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                s_n[j][i] = n[i];
+                nXr += n[i] * (X[i] - x[i]);
+            }
+            s_nXr[j] = nXr;
+        }
+        for (int i = 0; i < 3; ++i) {
+            s_r[i] = x[i];
+            s_r0[i] = pose[i];
+        }
+        s_anchor[0] = to_level(list[k].imagePos[0], 0);
+        s_anchor[1] = to_level(list[k].imagePos[1], 0);
+        for (int l = 0; l < 3; ++l) {
+            s_uv0l[l][0] = to_level(pose[7], l);
+            s_uv0l[l][1] = to_level(pose[8], l);
+        }
+    }
+    __syncthreads();
+
+    const int l = tid >> 7, t = tid & 127;
+    const bool live = t < NCC_TT;
+    const bool anchor_lane = l == 0 && t >= NCC_TT && t < NCC_TT + 5;
+    const double sc = (double)(1 << l);
+    const int cxl = to_level((double)s_anchor[0], l), cyl = to_level((double)s_anchor[1], l);
+    double s5[5][2];
+    bool bad = false;
+    if (live) {
+        double d[3];
+        pn_ray(c, s_R, ((double)(cxl + t % NCC_T - NCC_R) + 0.5) * sc - 0.5, ((double)(cyl + t / NCC_T - NCC_R) + 0.5) * sc - 0.5, d);
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            if (!pn_to_source(c, d, s_n[j], s_nXr[j], s_r, s_r0, s_R0, s5[j])) bad = true;
+    } else if (anchor_lane) { // where the anchor itself lands at slope j
+        const int j = t - NCC_TT;
+        double d[3], s[2] = {0.0, 0.0};
+        pn_ray(c, s_R, (double)s_anchor[0], (double)s_anchor[1], d);
+        if (!pn_to_source(c, d, s_n[j], s_nXr[j], s_r, s_r0, s_R0, s)) s_bad[0] = s_bad[1] = s_bad[2] = 1;
+        s_anc[j][0] = s[0];
+        s_anc[j][1] = s[1];
+    }
+    __syncthreads();
+    if (live) {
+        const double offx = (double)(s_uv0l[l][0] - WARP_R), offy = (double)(s_uv0l[l][1] - WARP_R);
+        // the source's centre pixel (level 0) in this level's source coordinates: the anchor is moved onto it
+        const double ctrx = ((double)s_uv0l[0][0] + 0.5) / sc - 0.5 - offx, ctry = ((double)s_uv0l[0][1] + 0.5) / sc - 0.5 - offy;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            double b = 0.0;
+            if (!bad) {
+                const double sx = ((s5[j][0] + 0.5) / sc - 0.5 - offx) - (((s_anc[j][0] + 0.5) / sc - 0.5 - offx) - ctrx);
+                const double sy = ((s5[j][1] + 0.5) / sc - 0.5 - offy) - (((s_anc[j][1] + 0.5) / sc - 0.5 - offy) - ctry);
+                if (sx >= 0.0 && sx <= (double)(WARP_S - 1) && sy >= 0.0 && sy <= (double)(WARP_S - 1)) {
+                    const int x0 = min((int)floor(sx), WARP_S - 2), y0 = min((int)floor(sy), WARP_S - 2);
+                    const double ax = sx - (double)x0, ay = sy - (double)y0;
+                    const uint8_t *p = s_src + l * WARP_SS + y0 * WARP_S + x0;
+                    const double top = (1.0 - ax) * (double)p[0] + ax * (double)p[1];
+                    const double bot = (1.0 - ax) * (double)p[WARP_S] + ax * (double)p[WARP_S + 1];
+                    b = (1.0 - ay) * top + ay * bot;
+                } else {
+                    bad = true;
+                }
+            }
+            s_vec[l][j][t] = b;
+        }
+        s_vec[l][5][t] = (double)pyr_at(pyr, l, cxl + t % NCC_T - NCC_R, cyl + t / NCC_T - NCC_R);
+        if (bad) s_bad[l] = 1; // any lane of the level: the level is left out
+    }
+    __syncthreads();
+    // zero mean, unit norm per vector; a level that failed above goes through the same steps on zeros and is dropped at the end
+    if (t < PN_VEC) {
+        double s = 0.0;
+        for (int i = 0; i < NCC_TT; ++i) s += s_vec[l][t][i];
+        s_sum[l][t] = s / (double)NCC_TT;
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int v = 0; v < PN_VEC; ++v) s_vec[l][v][t] = s_vec[l][v][t] - s_sum[l][v];
+    }
+    __syncthreads();
+    if (t < PN_VEC) {
+        double ss = 0.0;
+        for (int i = 0; i < NCC_TT; ++i) ss += s_vec[l][t][i] * s_vec[l][t][i];
+        if (!(ss > PN_MIN_SS)) s_bad[l] = 1; // a constant vector
+        s_sum[l][t] = sqrt(ss);
+    }
+    __syncthreads();
+    if (live) {
+        double hat[PN_VEC];
+#pragma unroll
+        for (int v = 0; v < PN_VEC; ++v) hat[v] = s_vec[l][v][t] / s_sum[l][v];
+        s_vec[l][0][t] = (hat[1] - hat[2]) * (0.5 / PN_FD_STEP); // d prediction / dp
+        s_vec[l][1][t] = (hat[3] - hat[4]) * (0.5 / PN_FD_STEP); // d prediction / dq
+        s_vec[l][2][t] = hat[5] - hat[0];                        // residual: measurement - prediction
+    }
+    __syncthreads();
+    if (t < PN_VEC) { // Jp Jp, Jp Jq, Jq Jq, Jp r, Jq r, r r
+        const double *a = s_vec[l][t == 0 || t == 1 || t == 3 ? 0 : (t == 2 || t == 4 ? 1 : 2)];
+        const double *b = s_vec[l][t == 0 ? 0 : (t == 1 || t == 2 ? 1 : 2)];
+        double s = 0.0;
+        for (int i = 0; i < NCC_TT; ++i) s += a[i] * b[i];
+        s_sum[l][t] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double A[PN_VEC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        int used = 0;
+        for (int lv = 0; lv < 3; ++lv)
+            if (!s_bad[lv]) {
+                for (int v = 0; v < PN_VEC; ++v) A[v] += s_sum[lv][v];
+                ++used;
+            }
+        bool done = false;
+        if (used > 0) {
+            const PatchNormalRec old = wnorm[fi];
+            const bool first = old.updates <= 0;
+            const double i00 = first ? PN_PRIOR_INFO : old.info[0], i01 = first ? 0.0 : old.info[1], i11 = first ? PN_PRIOR_INFO : old.info[2];
+            const double m = (double)(NCC_TT * used);
+            const double s2 = fmax(A[5] / (m - 2.0), PN_S_MIN * PN_S_MIN);
+            const double l00 = i00 + A[0] / s2, l01 = i01 + A[1] / s2, l11 = i11 + A[2] / s2;
+            const double b0 = A[3] / s2, b1 = A[4] / s2;
+            const double det = l00 * l11 - l01 * l01;
+            double d0 = (l11 * b0 - l01 * b1) / det, d1 = (l00 * b1 - l01 * b0) / det;
+            const double len = sqrt(d0 * d0 + d1 * d1);
+            if (len > PN_STEP_MAX) {
+                const double f = PN_STEP_MAX / len;
+                d0 = d0 * f;
+                d1 = d1 * f;
+            }
+            PatchNormalRec rec;
+            rec.pq[0] = s_pq[0] + d0;
+            rec.pq[1] = s_pq[1] + d1;
+            rec.info[0] = l00;
+            rec.info[1] = l01;
+            rec.info[2] = l11;
+            rec.updates = first ? 1 : (old.updates < 0x7fffffff ? old.updates + 1 : old.updates);
+            rec.pad = 0;
+            if (det > 0.0 && isfinite(rec.pq[0]) && isfinite(rec.pq[1]) && isfinite(l00) && isfinite(l01) && isfinite(l11)) {
+                wnorm[fi] = rec;
+                done = true;
+            }
+        }
+        atomicAdd(counts + (done ? CNT_PN_UPD : CNT_PN_SKIP), 1);
     }
 }
 
@@ -608,7 +855,16 @@ void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int 
 void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count, bool keep)
 {
     if (count > 0)
-        k_ncc_warp_capture<<<dim3(count, 3), 256, 0, e->stream>>>(pyr_of(e), d_idx, d_uv, e->d.state, e->d.wsrc, e->d.wpose, keep ? 1 : 0);
+        k_ncc_warp_capture<<<dim3(count, 3), 256, 0, e->stream>>>(pyr_of(e), d_idx, d_uv, e->d.state, e->d.wsrc, e->d.wpose, keep ? 1 : 0,
+                                                                  e->d.wnorm);
+}
+
+void launch_ncc_normal(EkfEngine *e, int M)
+{
+    (void)hipMemsetAsync(e->d.counts + CNT_PN_UPD, 0, 2 * sizeof(int), e->stream);
+    if (M > 0)
+        k_ncc_normal<<<M, 384, 0, e->stream>>>(pyr_of(e), e->d.pn_list, M, e->N, e->d.state, e->cam, e->d.feat_pos, e->d.feat_type, e->d.wsrc,
+                                               e->d.wpose, e->d.wnorm, e->d.counts);
 }
 
 void launch_match_compact_slots(EkfEngine *e, int n_pred, const EkfKeypoint *d_slot_xy);
@@ -621,7 +877,8 @@ static const uint8_t *match_templates(EkfEngine *e, int n_pred)
     (void)hipMemcpyAsync(e->d.wtmpl, e->d.tmpl, (size_t)e->N * 3 * NCC_TT, hipMemcpyDeviceToDevice, e->stream);
     if (n_pred > 0)
         k_ncc_warp<<<n_pred, 384, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, e->d.pred_uv, e->d.state, e->cam, e->d.feat_pos,
-                                                  e->d.feat_type, e->d.wsrc, e->d.wpose, e->d.wtmpl, e->d.counts);
+                                                  e->d.feat_type, e->d.wsrc, e->d.wpose, e->d.wtmpl, e->d.counts,
+                                                  e->pn_on ? e->d.wnorm : nullptr);
     return e->d.wtmpl;
 }
 

@@ -49,6 +49,21 @@ class EkfStageTimes(C.Structure):
     ]
 
 
+class EkfPatchNormal(C.Structure):
+    """ekf_get_patch_normals: slope, information (00, 01, 11), world normal, update count; 72 bytes"""
+
+    _fields_ = [
+        ("pq", C.c_double * 2),
+        ("info", C.c_double * 3),
+        ("normal", C.c_double * 3),
+        ("updates", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
+PATCH_NORMAL_DTYPE = np.dtype([("pq", "<f8", (2,)), ("info", "<f8", (3,)), ("normal", "<f8", (3,)), ("updates", "<i4"), ("_pad", "<i4")])
+assert PATCH_NORMAL_DTYPE.itemsize == C.sizeof(EkfPatchNormal) == 72
+
 # every symbol include/ekf_engine.h declares: name -> (restype, argtypes)
 _vp, _i = C.c_void_p, C.c_int
 ABI = {
@@ -100,6 +115,11 @@ ABI = {
     "ekf_get_subpixel_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_set_ncc_wide_search": (_i, [_vp, _i]),
     "ekf_get_ncc_wide_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "ekf_set_patch_normals": (_i, [_vp, _i]),
+    "ekf_refine_patch_normals": (_i, [_vp, _vp, _i]),
+    "ekf_get_patch_normals": (_i, [_vp, _vp, _i, _vp]),
+    "ekf_set_patch_normal": (_i, [_vp, _i, _vp, _vp]),
+    "ekf_get_patch_normal_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_step_image": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(EkfStepInfo)]),
     "ekf_detect_new_features": (_i, [_vp, _i, _i, C.c_double, C.c_double, _vp, C.POINTER(_i)]),
     "ekf_images_upload": (_i, [_vp, _i, _vp, _i, _i, _i, _i]),
@@ -551,6 +571,35 @@ class EkfEngine:
         """(predictions searched wide, coarse candidates evaluated for them) in the last NCC match"""
         a, b = _i(0), _i(0)
         self._chk(self.L.ekf_get_ncc_wide_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def set_patch_normals(self, on=True):
+        """the warp's patch planes get a normal estimated from the images, one estimator step per image step (DESIGN.md 4.9);
+        needs set_template_warp(True); off: every plane faces the camera that captured it"""
+        self._chk(self.L.ekf_set_patch_normals(self.h, 1 if on else 0))
+
+    def refine_patch_normals(self, matches):
+        """one estimator step on the current image and state for the features of `matches` (MATCH_DTYPE: featureIndex and the
+        pixel the feature is seen at)"""
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        self._chk(self.L.ekf_refine_patch_normals(self.h, _p(m), len(m)))
+
+    def patch_normals(self, feat_idx=None):
+        """PATCH_NORMAL_DTYPE [k]: slope, information, world normal and update count of the listed features (default: all)"""
+        idx = np.ascontiguousarray(np.arange(self.N) if feat_idx is None else feat_idx, dtype=np.int32)
+        out = np.zeros(max(len(idx), 1), dtype=PATCH_NORMAL_DTYPE)
+        self._chk(self.L.ekf_get_patch_normals(self.h, _p(idx), len(idx), _p(out)))
+        return out[: len(idx)]
+
+    def set_patch_normal(self, feat, pq, info=(1.0, 0.0, 1.0)):
+        pq = np.ascontiguousarray(pq, dtype=np.float64).reshape(2)
+        info = np.ascontiguousarray(info, dtype=np.float64).reshape(3)
+        self._chk(self.L.ekf_set_patch_normal(self.h, int(feat), _p(pq), _p(info)))
+
+    def patch_normal_counts(self):
+        """(features updated, features left alone) by the last estimator run"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_patch_normal_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def step_image(self, image):

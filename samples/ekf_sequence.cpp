@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -7,6 +7,8 @@
 // OpenCV is needed.  --warp-templates (anywhere after imgdir/): the templates are re-rendered from the predicted viewpoint before
 // every search (ImageEKF::setTemplateWarp).  --subpixel (likewise): NCC matches at sub-pixel positions (ImageEKF::setSubpixelMatches).
 // --wide-search (likewise): gates larger than the coarse search window are searched whole (ImageEKF::setWideSearch).
+// --patch-normals (likewise; implies --warp-templates): the normals of the warp's patches are estimated from the images
+// (ImageEKF::setPatchNormals) and map.ply carries them as nx ny nz.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -17,16 +19,18 @@
 
 int main(int argc, const char *argv[])
 {
-    bool warp = false, subpix = false, wide = false; // the flags are taken out of the argument list; the positional arguments keep their places
+    bool warp = false, subpix = false, wide = false, normals = false; // the flags are taken out of the argument list; the positional arguments keep their places
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search") {
+        if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search" ||
+            std::string(argv[i]) == "--patch-normals") {
+            if (std::string(argv[i]) == "--patch-normals") normals = true;
             (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc;
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -62,6 +66,7 @@ int main(int argc, const char *argv[])
         // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches or the wide search asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
+        if (normals) extendedKalmanFilter.setPatchNormals(true);
         extendedKalmanFilter.setSubpixelMatches(subpix);
         extendedKalmanFilter.setWideSearch(wide);
         extendedKalmanFilter.init(image);
@@ -78,6 +83,11 @@ int main(int argc, const char *argv[])
                 int warped = 0, fallback = 0;
                 ekf_get_template_warp_counts(extendedKalmanFilter.engine(), &warped, &fallback);
                 std::printf("        template levels warped %d, fallen back %d\n", warped, fallback);
+            }
+            if (normals) {
+                int updated = 0, skipped = 0;
+                ekf_get_patch_normal_counts(extendedKalmanFilter.engine(), &updated, &skipped);
+                std::printf("        patch normals updated %d, skipped %d\n", updated, skipped);
             }
             if (subpix) {
                 int refined = 0, integer = 0;

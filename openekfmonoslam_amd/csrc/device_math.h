@@ -21,7 +21,7 @@ struct ParD {
 };
 
 // R(q): Core/EKFMath.cpp:133-155
-__device__ __forceinline__ void quat_to_rot(const double *q, double *M)
+__host__ __device__ __forceinline__ void quat_to_rot(const double *q, double *M)
 {
     const double r = q[0], x = q[1], y = q[2], z = q[3];
     const double r2 = r * r, x2 = x * x, y2 = y * y, z2 = z * z;
@@ -83,7 +83,7 @@ __device__ __forceinline__ void mat3_vec(const double *M, const double *v, doubl
 }
 
 // m(theta, phi): Core/EKFMath.cpp:159-166
-__device__ __forceinline__ void dir_vec(double theta, double phi, double *m)
+__host__ __device__ __forceinline__ void dir_vec(double theta, double phi, double *m)
 {
     const double cp = cos(phi);
     m[0] = cp * sin(theta);

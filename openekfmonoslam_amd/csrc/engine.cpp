@@ -653,7 +653,7 @@ int ekf_set_state(EkfEngine *e, const double x13[13], int n_features, const doub
     e->n_step_preds = 0;
     HIPCHK(hipMemset(e->d.feat_times_predicted, 0, (size_t)e->cap * sizeof(unsigned)));
     HIPCHK(hipMemset(e->d.feat_times_matched, 0, (size_t)e->cap * sizeof(unsigned)));
-    if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * 9 * sizeof(double))); // template warp: no feature has a source patch
+    if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * WPOSE_DOUBLES * sizeof(double))); // template warp: no feature has a source patch
     if (e->d.wnorm) HIPCHK(hipMemset(e->d.wnorm, 0, (size_t)e->cap * sizeof(PatchNormalRec))); // patch normals: no feature has an estimate
     e->last_match_warped = false; // d.wtmpl belongs to the map the last match saw
     return EKF_OK;
@@ -817,7 +817,7 @@ int ekf_add_features(EkfEngine *e, const double *uv, const uint8_t *desc32, int 
     else HIPCHK(hipMemsetAsync(dd, 0, (size_t)count * e->desc_bytes, e->stream));
     HIPCHK(hipMemsetAsync(e->d.feat_times_predicted + e->N, 0, (size_t)count * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->d.feat_times_matched + e->N, 0, (size_t)count * 4, e->stream));
-    if (e->d.wpose) HIPCHK(hipMemsetAsync(e->d.wpose + 9 * (size_t)e->N, 0, (size_t)count * 9 * sizeof(double), e->stream));
+    if (e->d.wpose) HIPCHK(hipMemsetAsync(e->d.wpose + WPOSE_DOUBLES * (size_t)e->N, 0, (size_t)count * WPOSE_DOUBLES * sizeof(double), e->stream));
     if (e->d.wnorm) HIPCHK(hipMemsetAsync(e->d.wnorm + e->N, 0, (size_t)count * sizeof(PatchNormalRec), e->stream));
     launch_add_features(e, d_uv, count, d_Jpo, d_Jhr);
     for (int j = 0; j < count; ++j) {
@@ -853,12 +853,13 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     std::vector<double> pos(6 * (size_t)N);
     std::vector<uint8_t> desc((size_t)N * e->desc_bytes);
     std::vector<unsigned> tp(N), tm(N);
-    std::vector<uint8_t> tmpl((size_t)N * 363);
+    constexpr size_t TMPL = 3 * NCC_TT, WSRC = 3 * WARP_SS; // per feature: templates; template warp: source patches
+    std::vector<uint8_t> tmpl((size_t)N * TMPL);
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(tmpl.data(), e->d.tmpl, tmpl.size(), hipMemcpyDeviceToHost));
-    constexpr size_t WSRC = 3 * 41 * 41; // template warp: source patches and capture poses follow their features
+    // template warp: source patches and capture poses follow their features
     std::vector<uint8_t> wsrc(e->d.wsrc ? (size_t)N * WSRC : 0);
-    std::vector<double> wpose(e->d.wpose ? (size_t)N * 9 : 0);
+    std::vector<double> wpose(e->d.wpose ? (size_t)N * WPOSE_DOUBLES : 0);
     if (!wsrc.empty()) {
         HIPCHK(hipMemcpy(wsrc.data(), e->d.wsrc, wsrc.size(), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(wpose.data(), e->d.wpose, wpose.size() * 8, hipMemcpyDeviceToHost));
@@ -875,10 +876,10 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
         if (drop_feature[i]) continue;
         std::memmove(&pos[6 * (size_t)w], &pos[6 * (size_t)i], 6 * sizeof(double));
         std::memmove(&desc[(size_t)w * e->desc_bytes], &desc[(size_t)i * e->desc_bytes], e->desc_bytes);
-        std::memmove(&tmpl[(size_t)w * 363], &tmpl[(size_t)i * 363], 363);
+        std::memmove(&tmpl[(size_t)w * TMPL], &tmpl[(size_t)i * TMPL], TMPL);
         if (!wsrc.empty()) {
             std::memmove(&wsrc[(size_t)w * WSRC], &wsrc[(size_t)i * WSRC], WSRC);
-            std::memmove(&wpose[(size_t)w * 9], &wpose[(size_t)i * 9], 9 * sizeof(double));
+            std::memmove(&wpose[(size_t)w * WPOSE_DOUBLES], &wpose[(size_t)i * WPOSE_DOUBLES], WPOSE_DOUBLES * sizeof(double));
         }
         if (!wnorm.empty()) wnorm[w] = wnorm[i];
         tp[w] = tp[i];
@@ -897,10 +898,10 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     if (w > 0) {
         HIPCHK(hipMemcpy(e->d.feat_pos, pos.data(), (size_t)6 * w * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_desc, desc.data(), (size_t)w * e->desc_bytes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d.tmpl, tmpl.data(), (size_t)w * 363, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(e->d.tmpl, tmpl.data(), (size_t)w * TMPL, hipMemcpyHostToDevice));
         if (!wsrc.empty()) {
             HIPCHK(hipMemcpy(e->d.wsrc, wsrc.data(), (size_t)w * WSRC, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(e->d.wpose, wpose.data(), (size_t)w * 9 * 8, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(e->d.wpose, wpose.data(), (size_t)w * WPOSE_DOUBLES * 8, hipMemcpyHostToDevice));
         }
         if (!wnorm.empty()) HIPCHK(hipMemcpy(e->d.wnorm, wnorm.data(), (size_t)w * sizeof(PatchNormalRec), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(e->d.feat_times_predicted, tp.data(), (size_t)w * 4, hipMemcpyHostToDevice));
@@ -2147,9 +2148,9 @@ int ekf_set_template_warp(EkfEngine *e, int on)
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
         const size_t cap = (size_t)e->cap;
-        hipError_t st = dalloc(&e->d.wsrc, cap * 3 * 41 * 41);
-        if (st == hipSuccess) st = dalloc(&e->d.wtmpl, cap * 363);
-        if (st == hipSuccess) st = dalloc(&e->d.wpose, cap * 9); // zeroed: no feature has a source patch yet
+        hipError_t st = dalloc(&e->d.wsrc, cap * 3 * WARP_SS);
+        if (st == hipSuccess) st = dalloc(&e->d.wtmpl, cap * 3 * NCC_TT);
+        if (st == hipSuccess) st = dalloc(&e->d.wpose, cap * WPOSE_DOUBLES); // zeroed: no feature has a source patch yet
         if (st != hipSuccess) {
             for (void *p : {(void *)e->d.wsrc, (void *)e->d.wtmpl, (void *)e->d.wpose})
                 if (p) (void)hipFree(p);
@@ -2209,16 +2210,6 @@ int ekf_refine_patch_normals(EkfEngine *e, const EkfMatch *matches, int M)
     return check_async(e);
 }
 
-// R(q) as device_math.h's quat_to_rot
-static void host_quat_to_rot(const double *q, double *M)
-{
-    const double r = q[0], x = q[1], y = q[2], z = q[3];
-    const double r2 = r * r, x2 = x * x, y2 = y * y, z2 = z * z;
-    M[0] = r2 + x2 - y2 - z2; M[1] = 2 * (x * y - r * z); M[2] = 2 * (z * x + r * y);
-    M[3] = 2 * (x * y + r * z); M[4] = r2 - x2 + y2 - z2; M[5] = 2 * (y * z - r * x);
-    M[6] = 2 * (z * x - r * y); M[7] = 2 * (y * z + r * x); M[8] = r2 - x2 - y2 + z2;
-}
-
 int ekf_get_patch_normals(EkfEngine *e, const int32_t *feat_idx, int count, EkfPatchNormal *out)
 {
     if (!e || count < 0 || (count > 0 && (!feat_idx || !out))) return EKF_ERR_INVALID_ARG;
@@ -2233,43 +2224,32 @@ int ekf_get_patch_normals(EkfEngine *e, const int32_t *feat_idx, int count, EkfP
     HIPCHK(hipStreamSynchronize(e->stream));
     const size_t N = (size_t)e->N;
     std::vector<PatchNormalRec> rec(N);
-    std::vector<double> pose(9 * N), pos(6 * N);
+    std::vector<double> pose(WPOSE_DOUBLES * N), pos(6 * N);
     std::vector<int> type(N);
     HIPCHK(hipMemcpy(rec.data(), e->d.wnorm, N * sizeof(PatchNormalRec), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pose.data(), e->d.wpose, 9 * N * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pose.data(), e->d.wpose, WPOSE_DOUBLES * N * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(pos.data(), e->d.feat_pos, 6 * N * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(type.data(), e->d.feat_type, N * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < count; ++i) {
         const size_t f = (size_t)feat_idx[i];
-        const double *ps = &pose[9 * f], *y = &pos[6 * f];
+        const double *ps = &pose[WPOSE_DOUBLES * f];
         EkfPatchNormal o;
         std::memset(&o, 0, sizeof(o));
-        if (ps[3] != 0.0 || ps[4] != 0.0 || ps[5] != 0.0 || ps[6] != 0.0) {
+        if (patch_has_source(ps)) {
             double R0[9];
-            host_quat_to_rot(ps + 3, R0);
+            quat_to_rot(ps + 3, R0);
             if (rec[f].updates > 0) {
                 o.pq[0] = rec[f].pq[0];
                 o.pq[1] = rec[f].pq[1];
                 for (int k = 0; k < 3; ++k) o.info[k] = rec[f].info[k];
                 o.updates = rec[f].updates;
             } else { // the rule of DESIGN.md 4.6 as a slope, and the first update's prior
-                double X[3] = {y[0], y[1], y[2]};
-                if (type[f] == EKF_FEATURE_INVERSE_DEPTH) {
-                    const double cp = std::cos(y[4]);
-                    X[0] += cp * std::sin(y[3]) / y[5];
-                    X[1] += -std::sin(y[4]) / y[5];
-                    X[2] += cp * std::cos(y[3]) / y[5];
-                }
-                const double w[3] = {X[0] - ps[0], X[1] - ps[1], X[2] - ps[2]};
-                const double h0 = R0[0] * w[0] + R0[3] * w[1] + R0[6] * w[2];
-                const double h1 = R0[1] * w[0] + R0[4] * w[1] + R0[7] * w[2];
-                const double h2 = R0[2] * w[0] + R0[5] * w[1] + R0[8] * w[2];
-                o.pq[0] = -h0 / h2;
-                o.pq[1] = -h1 / h2;
+                double X[3];
+                patch_world_point(&pos[6 * f], type[f], X);
+                pn_rule_slope(R0, X, ps, o.pq);
                 o.info[0] = o.info[2] = PN_PRIOR_INFO;
             }
-            const double p = o.pq[0], q = o.pq[1], nrm = std::sqrt(p * p + q * q + 1.0);
-            for (int k = 0; k < 3; ++k) o.normal[k] = (R0[3 * k] * p + R0[3 * k + 1] * q - R0[3 * k + 2]) / nrm;
+            pn_normal(R0, o.pq[0], o.pq[1], o.normal);
         }
         out[i] = o;
     }
@@ -2350,18 +2330,19 @@ int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candi
     return EKF_OK;
 }
 
-int ekf_get_match_templates(EkfEngine *e, const int32_t *feat_idx, int count, uint8_t *tmpl363)
+int ekf_get_match_templates(EkfEngine *e, const int32_t *feat_idx, int count, uint8_t *out)
 {
-    if (!e || count < 0 || (count > 0 && (!feat_idx || !tmpl363))) return EKF_ERR_INVALID_ARG;
+    if (!e || count < 0 || (count > 0 && (!feat_idx || !out))) return EKF_ERR_INVALID_ARG;
     for (int i = 0; i < count; ++i)
         if (feat_idx[i] < 0 || feat_idx[i] >= e->N) return EKF_ERR_INVALID_ARG;
     if (count == 0) return EKF_OK;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const uint8_t *src = e->last_match_warped ? e->d.wtmpl : e->d.tmpl;
-    std::vector<uint8_t> all((size_t)e->N * 363);
+    constexpr size_t TMPL = 3 * NCC_TT;
+    std::vector<uint8_t> all((size_t)e->N * TMPL);
     HIPCHK(hipMemcpy(all.data(), src, all.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; ++i) std::memcpy(tmpl363 + (size_t)i * 363, &all[(size_t)feat_idx[i] * 363], 363);
+    for (int i = 0; i < count; ++i) std::memcpy(out + i * TMPL, &all[feat_idx[i] * TMPL], TMPL);
     return EKF_OK;
 }
 

@@ -448,6 +448,9 @@ void launch_ncc_normal(EkfEngine *e, int M);
 // subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7; wide: the slots whose gate exceeds the coarse window go
 // through the three kernels of DESIGN.md 4.8 instead (d.wide_list / d.wide_part sized for the current frame: engine.cpp)
 void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide);
+constexpr int NCC_TT = 121;                // bytes of one 11 x 11 template; d.tmpl / d.wtmpl hold 3 levels per feature
+constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S; // template warp: side and bytes of one source patch; d.wsrc holds 3 per feature
+constexpr int WPOSE_DOUBLES = 9;           // ... and its capture pose record in d.wpose: r0 (3), q0 (4), capture pixel (2)
 constexpr int NCC_WIDE_TILE = 32;          // coarse candidates per tile side
 constexpr int NCC_WIDE_SLOT_BYTES = 80;    // sizeof(WideSlot), kernels_ncc.hip
 constexpr int NCC_WIDE_PARTIAL_BYTES = 16; // sizeof(WidePartial)

@@ -16,7 +16,10 @@
 
 namespace ekf {
 
-constexpr int NCC_R = 5, NCC_T = 11, NCC_TT = 121, NCC_MAXRAD = 16;
+constexpr int NCC_R = 5, NCC_T = 11, NCC_MAXRAD = 16; // (NCC_TT = NCC_T * NCC_T: engine.h)
+constexpr int NCC_BLOCK = 256;   // lanes of the matching kernels' workgroups (k_ncc_match, k_ncc_wide_coarse, k_ncc_wide_finish)
+constexpr int PATCH_BLOCK = 384; // ... and of k_ncc_warp / k_ncc_normal: 128 per pyramid level
+static_assert(NCC_TT == NCC_T * NCC_T, "engine.h sizes the template tables");
 constexpr int NCC_WIN = 2 * NCC_MAXRAD + 1 + 2 * NCC_R; // 43
 
 // ---- pyramid -----------------------------------------------------------------------------------------------
@@ -68,13 +71,14 @@ k_ncc_capture(Pyr pyr, const int *feat_idx, const double *uv, uint8_t *tmpl)
     tmpl[((size_t)feat_idx[i] * 3 + l) * NCC_TT + t] = (uint8_t)pyr_at(pyr, l, cx + dx, cy + dy);
 }
 
-// ---- template warp (DESIGN.md 4.6) -------------------------------------------------------------------------
-// A template is the image of a small plane through the feature's world point X that faces the camera which first saw it.
-// k_ncc_warp_capture keeps, per feature and level, the 41 x 41 pixels around the capture pixel and the capture pose;
-// k_ncc_warp re-renders the 11 x 11 template of every prediction slot from the current pose estimate before the search:
-// template pixel -> ray of the current camera -> plane -> pixel of the capture camera -> bilinear sample of the source.
-// A level whose samples leave the source (or whose geometry is degenerate) keeps the stored template, whole.
-constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S, WARP_R = WARP_S / 2;
+// ---- patch-plane geometry --------------------------------------------------------------
+// A template is the image of a small plane through the feature's world point X.  k_ncc_warp_capture keeps, per feature and
+// level, the 41 x 41 pixels around the capture pixel and the capture pose; k_ncc_warp and k_ncc_normal re-render template
+// pixels from them through one chain, the functions of this block: position of the template pixel at level 0 (tmpl_pos) ->
+// ray of the current camera (patch_ray) -> plane -> level-0 position in the capture camera (patch_to_source) -> the level's
+// source coordinates (src_coord) -> bilinear sample of the staged source (patch_sample).  The numpy restatements
+// (tests/template_warp_ref.py, tests/patch_normal_ref.py) define every result to the bit: fp64, no contraction, this order.
+constexpr int WARP_R = WARP_S / 2;
 
 // block = (item, level): source patch; the level-0 block also writes the pose record (keep = 0: zeros = "no source patch")
 __global__ void __launch_bounds__(256)
@@ -82,10 +86,10 @@ k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double 
                    PatchNormalRec *wnorm)
 {
     const int i = blockIdx.x, l = blockIdx.y, fi = feat_idx[i];
-    if (l == 0 && threadIdx.x == 9 && wnorm) wnorm[fi] = PatchNormalRec{}; // patch normals: a capture resets the estimate
-    if (l == 0 && threadIdx.x < 9) {
+    if (l == 0 && threadIdx.x == WPOSE_DOUBLES && wnorm) wnorm[fi] = PatchNormalRec{}; // patch normals: a capture resets the estimate
+    if (l == 0 && threadIdx.x < WPOSE_DOUBLES) {
         const int t = threadIdx.x;
-        wpose[9 * (size_t)fi + t] = !keep ? 0.0 : (t < 7 ? st[ST_X + t] : uv[2 * i + t - 7]);
+        wpose[WPOSE_DOUBLES * (size_t)fi + t] = !keep ? 0.0 : (t < 7 ? st[ST_X + t] : uv[2 * i + t - 7]);
     }
     if (!keep) return;
     const int cx = to_level(uv[2 * i], l), cy = to_level(uv[2 * i + 1], l);
@@ -93,109 +97,151 @@ k_ncc_warp_capture(Pyr pyr, const int *feat_idx, const double *uv, const double 
         wsrc[((size_t)fi * 3 + l) * WARP_SS + t] = (uint8_t)pyr_at(pyr, l, cx + t % WARP_S - WARP_R, cy + t / WARP_S - WARP_R);
 }
 
-// unit normal in world axes of the slope (p, q) in the capture camera's axes: R0 (p, q, -1) / |(p, q, -1)|
-__device__ __forceinline__ void pn_normal(const double *R0, double p, double q, double *n)
+// what the chain needs of one feature, in LDS: world point, rotation and position of the current camera (R, r) and of the
+// capture camera (R0, r0), capture pixel per level
+struct PatchView {
+    double X[3], R[9], R0[9], r[3], r0[3];
+    int uv0[3][2];
+};
+// a plane through X: unit normal in world axes, pointing to the side the capture camera saw, and n . (X - r)
+struct PatchPlane {
+    double n[3], nXr;
+};
+
+// one lane: the view of feature fi from the filter state st, the map tables and the feature's capture pose record
+__device__ __forceinline__ void patch_view_fill(PatchView &v, const double *st, const double *feat_pos, const int *feat_type, int fi,
+                                                const double *pose)
 {
-    const double nrm = sqrt(p * p + q * q + 1.0);
-    for (int i = 0; i < 3; ++i) n[i] = (R0[3 * i] * p + R0[3 * i + 1] * q - R0[3 * i + 2]) / nrm;
+    const double *x = st + ST_X;
+    patch_world_point(feat_pos + 6 * (size_t)fi, feat_type[fi], v.X);
+    quat_to_rot(x + 3, v.R);
+    quat_to_rot(pose + 3, v.R0);
+    for (int i = 0; i < 3; ++i) {
+        v.r[i] = x[i];
+        v.r0[i] = pose[i];
+    }
+    for (int l = 0; l < 3; ++l) {
+        v.uv0[l][0] = to_level(pose[7], l);
+        v.uv0[l][1] = to_level(pose[8], l);
+    }
 }
 
+__device__ __forceinline__ void patch_plane_set(PatchPlane &pl, const PatchView &v, const double *n)
+{
+    double nXr = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        pl.n[i] = n[i];
+        nXr += n[i] * (v.X[i] - v.r[i]);
+    }
+    pl.nXr = nXr;
+}
+
+// the three source levels of feature fi into LDS, by the whole workgroup (the caller's barrier follows)
+__device__ __forceinline__ void patch_stage_source(uint8_t *s_src, const uint8_t *wsrc, int fi)
+{
+    for (int i = threadIdx.x; i < 3 * WARP_SS; i += PATCH_BLOCK) s_src[i] = wsrc[(size_t)fi * 3 * WARP_SS + i];
+}
+
+// level-0 position of the centre of template pixel o (0..10 along one axis) of the template centred on pixel cl of the level of scale sc
+__device__ __forceinline__ double tmpl_pos(int cl, int o, double sc) { return ((double)(cl + o - NCC_R) + 0.5) * sc - 0.5; }
+
+// ray of the level-0 position (px, py) in world axes: undistortPoint (closed form), then R
+__device__ __forceinline__ void patch_ray(const CamD &c, const double *R, double px, double py, double *d)
+{
+    const double pdx = px - c.cx, pdy = py - c.cy;
+    const double mx = c.dx * pdx, my = c.dy * pdy;
+    const double rd2 = mx * mx + my * my;
+    const double f = 1.0 + c.k1 * rd2 + c.k2 * rd2 * rd2;
+    const double hc[3] = {pdx * f / c.fx, pdy * f / c.fy, 1.0};
+    mat3_vec(R, hc, d);
+}
+
+// where the ray d from r meets the plane, projected into the capture camera and distorted: level-0 position s; false: the ray
+// does not meet the plane's front (n . d < 0 does), or meets it behind one of the two cameras
+__device__ __forceinline__ bool patch_to_source(const CamD &c, const PatchView &v, const PatchPlane &pl, const double *d, double *s)
+{
+    const double nd = pl.n[0] * d[0] + pl.n[1] * d[1] + pl.n[2] * d[2];
+    if (!(nd < 0.0)) return false;
+    const double lam = pl.nXr / nd;
+    if (!(lam > 0.0)) return false;
+    const double w[3] = {v.r[0] + lam * d[0] - v.r0[0], v.r[1] + lam * d[1] - v.r0[1], v.r[2] + lam * d[2] - v.r0[2]};
+    const double h0 = v.R0[0] * w[0] + v.R0[3] * w[1] + v.R0[6] * w[2];
+    const double h1 = v.R0[1] * w[0] + v.R0[4] * w[1] + v.R0[7] * w[2];
+    const double h2 = v.R0[2] * w[0] + v.R0[5] * w[1] + v.R0[8] * w[2];
+    if (!(h2 > 0.0)) return false;
+    distort(c, c.cx + c.fx * h0 / h2, c.cy + c.fy * h1 / h2, s);
+    return true;
+}
+
+// one axis of the level-0 position s in the coordinates of the source patch of the level of scale sc, whose centre is pixel uv0l
+__device__ __forceinline__ double src_coord(double s, double sc, int uv0l) { return (s + 0.5) / sc - 0.5 - (double)(uv0l - WARP_R); }
+
+// bilinear sample of the staged source of level l at (sx, sy); false outside [0, WARP_S - 1]^2
+__device__ __forceinline__ bool patch_sample(const uint8_t *s_src, int l, double sx, double sy, double *b)
+{
+    if (!(sx >= 0.0 && sx <= (double)(WARP_S - 1) && sy >= 0.0 && sy <= (double)(WARP_S - 1))) return false;
+    const int x0 = min((int)floor(sx), WARP_S - 2), y0 = min((int)floor(sy), WARP_S - 2);
+    const double ax = sx - (double)x0, ay = sy - (double)y0;
+    const uint8_t *p = s_src + l * WARP_SS + y0 * WARP_S + x0;
+    const double top = (1.0 - ax) * (double)p[0] + ax * (double)p[1];
+    const double bot = (1.0 - ax) * (double)p[WARP_S] + ax * (double)p[WARP_S + 1];
+    *b = (1.0 - ay) * top + ay * bot;
+    return true;
+}
+
+// ---- template warp (DESIGN.md 4.6) -------------------------------------------------------------------------
+// k_ncc_warp re-renders the 11 x 11 template of every prediction slot from the current pose estimate before the search.  The
+// plane faces the camera which first saw the feature (n = a / |a|, a = r0 - X) or, with patch normals on, has the estimated
+// slope.  A level whose samples leave the source (or whose geometry is degenerate) keeps the stored template, whole.
 // One workgroup per prediction slot, 128 lanes per level (121 active): fp64, everything a lane touches after the staging
-// is in LDS (5 KB of source bytes, 30 doubles of constants).  Latency-bound like k_ncc_match: ~0.4 KFLOP and one 10-step
+// is in LDS (5 KB of source bytes, 34 doubles of constants).  Latency-bound like k_ncc_match: ~0.4 KFLOP and one 10-step
 // Newton solve per lane.  out already holds a copy of the stored templates; only whole warped levels are written.
-__global__ void __launch_bounds__(384)
+__global__ void __launch_bounds__(PATCH_BLOCK)
 k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const double *st, CamD c, const double *feat_pos,
            const int *feat_type, const uint8_t *wsrc, const double *wpose, uint8_t *out, int *counts, const PatchNormalRec *wnorm)
 {
     __shared__ uint8_t s_src[3 * WARP_SS + 1];
-    __shared__ double s_R[9], s_R0[9], s_n[3], s_r[3], s_r0[3], s_nXr, s_uv0[2];
+    __shared__ PatchView s_v;
+    __shared__ PatchPlane s_pl;
     __shared__ int s_bad[3];
 
     const int k = blockIdx.x, tid = threadIdx.x;
     if (k >= *d_npred) return;
     const int fi = plist[k];
-    const double *pose = wpose + 9 * (size_t)fi;
-    const bool has_src = pose[3] != 0.0 || pose[4] != 0.0 || pose[5] != 0.0 || pose[6] != 0.0; // uniform over the block
-    if (!has_src) {
+    const double *pose = wpose + WPOSE_DOUBLES * (size_t)fi;
+    if (!patch_has_source(pose)) { // uniform over the block
         if (tid == 0) atomicAdd(counts + CNT_WARP_FB, 3);
         return;
     }
-    for (int i = tid; i < 3 * WARP_SS; i += 384) s_src[i] = wsrc[(size_t)fi * 3 * WARP_SS + i];
+    patch_stage_source(s_src, wsrc, fi);
     if (tid < 3) s_bad[tid] = 0;
     if (tid == 0) {
-        const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)fi;
-        double X[3] = {y[0], y[1], y[2]};
-        if (feat_type[fi] == EKF_FEATURE_INVERSE_DEPTH) {
-            double m[3];
-            dir_vec(y[3], y[4], m);
-            X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
+        patch_view_fill(s_v, st, feat_pos, feat_type, fi, pose);
+        double n[3];
+        if (wnorm && wnorm[fi].updates > 0) { // patch normals: n(p, q) instead of the rule
+            pn_normal(s_v.R0, wnorm[fi].pq[0], wnorm[fi].pq[1], n);
+        } else {
+            const double a[3] = {s_v.r0[0] - s_v.X[0], s_v.r0[1] - s_v.X[1], s_v.r0[2] - s_v.X[2]};
+            const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+            for (int i = 0; i < 3; ++i) n[i] = a[i] / an;
         }
-        quat_to_rot(x + 3, s_R);
-        quat_to_rot(pose + 3, s_R0);
-        const double a[3] = {pose[0] - X[0], pose[1] - X[1], pose[2] - X[2]};
-        const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-        const bool estimated = wnorm && wnorm[fi].updates > 0; // patch normals: n(p, q) instead of the rule
-        double pqn[3] = {0.0, 0.0, 1.0};
-        if (estimated) pn_normal(s_R0, wnorm[fi].pq[0], wnorm[fi].pq[1], pqn);
-        double nXr = 0.0;
-        for (int i = 0; i < 3; ++i) {
-            s_n[i] = estimated ? pqn[i] : a[i] / an;
-            s_r[i] = x[i];
-            s_r0[i] = pose[i];
-            nXr += s_n[i] * (X[i] - x[i]);
-        }
-        s_nXr = nXr;
-        s_uv0[0] = pose[7];
-        s_uv0[1] = pose[8];
+        patch_plane_set(s_pl, s_v, n);
     }
     __syncthreads();
 
     const int l = tid >> 7, t = tid & 127;
     const bool live = t < NCC_TT;
     const double sc = (double)(1 << l);
-    bool bad = false;
     int val = 0;
     if (live) {
         const int cxl = to_level(uv_tab[2 * fi], l), cyl = to_level(uv_tab[2 * fi + 1], l);
-        const double px = ((double)(cxl + t % NCC_T - NCC_R) + 0.5) * sc - 0.5, py = ((double)(cyl + t / NCC_T - NCC_R) + 0.5) * sc - 0.5;
-        // undistortPoint (closed form), then the ray in world axes
-        const double pdx = px - c.cx, pdy = py - c.cy;
-        const double mx = c.dx * pdx, my = c.dy * pdy;
-        const double rd2 = mx * mx + my * my;
-        const double f = 1.0 + c.k1 * rd2 + c.k2 * rd2 * rd2;
-        const double hc[3] = {pdx * f / c.fx, pdy * f / c.fy, 1.0};
-        double d[3];
-        mat3_vec(s_R, hc, d);
-        const double nd = s_n[0] * d[0] + s_n[1] * d[1] + s_n[2] * d[2];
-        bad = !(nd < 0.0); // n points from the plane to the capturing camera: a ray that meets its front has n . d < 0
-        if (!bad) {
-            const double lam = s_nXr / nd;
-            bad = !(lam > 0.0);
-            if (!bad) {
-                const double w[3] = {s_r[0] + lam * d[0] - s_r0[0], s_r[1] + lam * d[1] - s_r0[1], s_r[2] + lam * d[2] - s_r0[2]};
-                const double h0 = s_R0[0] * w[0] + s_R0[3] * w[1] + s_R0[6] * w[2];
-                const double h1 = s_R0[1] * w[0] + s_R0[4] * w[1] + s_R0[7] * w[2];
-                const double h2 = s_R0[2] * w[0] + s_R0[5] * w[1] + s_R0[8] * w[2];
-                bad = !(h2 > 0.0);
-                if (!bad) {
-                    double s[2];
-                    distort(c, c.cx + c.fx * h0 / h2, c.cy + c.fy * h1 / h2, s);
-                    const double sx = (s[0] + 0.5) / sc - 0.5 - (double)(to_level(s_uv0[0], l) - WARP_R);
-                    const double sy = (s[1] + 0.5) / sc - 0.5 - (double)(to_level(s_uv0[1], l) - WARP_R);
-                    bad = !(sx >= 0.0 && sx <= (double)(WARP_S - 1) && sy >= 0.0 && sy <= (double)(WARP_S - 1));
-                    if (!bad) {
-                        const int x0 = min((int)floor(sx), WARP_S - 2), y0 = min((int)floor(sy), WARP_S - 2);
-                        const double ax = sx - (double)x0, ay = sy - (double)y0;
-                        const uint8_t *p = s_src + l * WARP_SS + y0 * WARP_S + x0;
-                        const double top = (1.0 - ax) * (double)p[0] + ax * (double)p[1];
-                        const double bot = (1.0 - ax) * (double)p[WARP_S] + ax * (double)p[WARP_S + 1];
-                        const double b = (1.0 - ay) * top + ay * bot;
-                        val = min(max((int)floor(b + 0.5), 0), 255);
-                    }
-                }
-            }
-        }
-        if (bad) s_bad[l] = 1; // any lane of the level: the whole level falls back
+        double d[3], s[2], b;
+        patch_ray(c, s_v.R, tmpl_pos(cxl, t % NCC_T, sc), tmpl_pos(cyl, t / NCC_T, sc), d);
+        if (patch_to_source(c, s_v, s_pl, d, s) &&
+            patch_sample(s_src, l, src_coord(s[0], sc, s_v.uv0[l][0]), src_coord(s[1], sc, s_v.uv0[l][1]), &b))
+            val = min(max((int)floor(b + 0.5), 0), 255);
+        else
+            s_bad[l] = 1; // any lane of the level: the whole level falls back
     }
     __syncthreads();
     if (live && !s_bad[l]) out[((size_t)fi * 3 + l) * NCC_TT + t] = (uint8_t)val;
@@ -210,107 +256,48 @@ k_ncc_warp(const int *plist, const int *d_npred, const double *uv_tab, const dou
 // One estimator step per listed match: the feature's source patches are aligned to the current frame around the match's pixel
 // and the slope (p, q) of its patch plane takes one information-filter step.  tests/patch_normal_ref.py is the definition; every
 // operation below is in its order (fp64, no contraction, sums in pixel order, then levels 0, 1, 2).
-
-// steps 2-4 of k_ncc_warp for one ray d (world axes) and one plane: level-0 position in the capture frame; false: not valid
-__device__ __forceinline__ bool pn_to_source(const CamD &c, const double *d, const double *n, double nXr, const double *r, const double *r0,
-                                             const double *R0, double *s)
-{
-    const double nd = n[0] * d[0] + n[1] * d[1] + n[2] * d[2];
-    if (!(nd < 0.0)) return false;
-    const double lam = nXr / nd;
-    if (!(lam > 0.0)) return false;
-    const double w[3] = {r[0] + lam * d[0] - r0[0], r[1] + lam * d[1] - r0[1], r[2] + lam * d[2] - r0[2]};
-    const double h0 = R0[0] * w[0] + R0[3] * w[1] + R0[6] * w[2];
-    const double h1 = R0[1] * w[0] + R0[4] * w[1] + R0[7] * w[2];
-    const double h2 = R0[2] * w[0] + R0[5] * w[1] + R0[8] * w[2];
-    if (!(h2 > 0.0)) return false;
-    distort(c, c.cx + c.fx * h0 / h2, c.cy + c.fy * h1 / h2, s);
-    return true;
-}
-
-// ray of the level-0 position (px, py) in world axes (step 2 of k_ncc_warp)
-__device__ __forceinline__ void pn_ray(const CamD &c, const double *R, double px, double py, double *d)
-{
-    const double pdx = px - c.cx, pdy = py - c.cy;
-    const double mx = c.dx * pdx, my = c.dy * pdy;
-    const double rd2 = mx * mx + my * my;
-    const double f = 1.0 + c.k1 * rd2 + c.k2 * rd2 * rd2;
-    const double hc[3] = {pdx * f / c.fx, pdy * f / c.fy, 1.0};
-    mat3_vec(R, hc, d);
-}
-
 constexpr int PN_VEC = 6; // vectors per level: the prediction at the five slopes, the measurement
 
 // One workgroup per match, 128 lanes per level (121 active, lanes 121..125 of level 0 carry the anchor at the five slopes).
 // Latency-bound: five plane intersections and Newton solves per lane, six barriers-separated serial sums of 121 terms by six lanes
 // per level (the order of the restatement), 18 KB of vectors and 5 KB of source bytes in LDS.
-__global__ void __launch_bounds__(384)
+__global__ void __launch_bounds__(PATCH_BLOCK)
 k_ncc_normal(Pyr pyr, const EkfMatch *list, int M, int N, const double *st, CamD c, const double *feat_pos, const int *feat_type,
              const uint8_t *wsrc, const double *wpose, PatchNormalRec *wnorm, int *counts)
 {
     __shared__ uint8_t s_src[3 * WARP_SS + 1];
     __shared__ double s_vec[3][PN_VEC][128];
     __shared__ double s_sum[3][PN_VEC];
-    __shared__ double s_R[9], s_R0[9], s_n[5][3], s_nXr[5], s_r[3], s_r0[3], s_anc[5][2], s_pq[2];
-    __shared__ int s_bad[3], s_anchor[2], s_uv0l[3][2], s_ctr0[2];
+    __shared__ PatchView s_v;
+    __shared__ PatchPlane s_pl[5]; // the slope, p + h, p - h, q + h, q - h
+    __shared__ double s_anc[5][2], s_pq[2];
+    __shared__ int s_bad[3], s_anchor[2];
 
     const int k = blockIdx.x, tid = threadIdx.x;
     if (k >= M) return;
     const int fi = list[k].featureIndex;
     if (fi < 0 || fi >= N) return; // (the host validates the list)
-    const double *pose = wpose + 9 * (size_t)fi;
-    const bool has_src = pose[3] != 0.0 || pose[4] != 0.0 || pose[5] != 0.0 || pose[6] != 0.0; // uniform over the block
-    if (!has_src) {
+    const double *pose = wpose + WPOSE_DOUBLES * (size_t)fi;
+    if (!patch_has_source(pose)) { // uniform over the block
         if (tid == 0) atomicAdd(counts + CNT_PN_SKIP, 1);
         return;
     }
-    for (int i = tid; i < 3 * WARP_SS; i += 384) s_src[i] = wsrc[(size_t)fi * 3 * WARP_SS + i];
+    patch_stage_source(s_src, wsrc, fi);
     if (tid < 3) s_bad[tid] = 0;
     if (tid == 0) {
-        const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)fi;
-        double X[3] = {y[0], y[1], y[2]};
-        if (feat_type[fi] == EKF_FEATURE_INVERSE_DEPTH) {
-            double m[3];
-            dir_vec(y[3], y[4], m);
-            X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
-        }
-        quat_to_rot(x + 3, s_R);
-        quat_to_rot(pose + 3, s_R0);
-        double p, q;
-        if (wnorm[fi].updates > 0) {
-            p = wnorm[fi].pq[0];
-            q = wnorm[fi].pq[1];
-        } else { // first update: the rule of 4.6 as a slope
-            const double w[3] = {X[0] - pose[0], X[1] - pose[1], X[2] - pose[2]};
-            const double h0 = s_R0[0] * w[0] + s_R0[3] * w[1] + s_R0[6] * w[2];
-            const double h1 = s_R0[1] * w[0] + s_R0[4] * w[1] + s_R0[7] * w[2];
-            const double h2 = s_R0[2] * w[0] + s_R0[5] * w[1] + s_R0[8] * w[2];
-            p = -h0 / h2;
-            q = -h1 / h2;
-        }
-        s_pq[0] = p;
-        s_pq[1] = q;
-        for (int j = 0; j < 5; ++j) { // the slope, p + h, p - h, q + h, q - h
+        patch_view_fill(s_v, st, feat_pos, feat_type, fi, pose);
+        double pq[2] = {wnorm[fi].pq[0], wnorm[fi].pq[1]};
+        if (wnorm[fi].updates <= 0) pn_rule_slope(s_v.R0, s_v.X, s_v.r0, pq); // first update: the rule of 4.6 as a slope
+        s_pq[0] = pq[0];
+        s_pq[1] = pq[1];
+        for (int j = 0; j < 5; ++j) {
             const double dp = j == 1 ? PN_FD_STEP : (j == 2 ? -PN_FD_STEP : 0.0), dq = j == 3 ? PN_FD_STEP : (j == 4 ? -PN_FD_STEP : 0.0);
             double n[3];
-            pn_normal(s_R0, p + dp, q + dq, n);
-            double nXr = 0.0;
-            for (int i = 0; i < 3; ++i) {
-                s_n[j][i] = n[i];
-                nXr += n[i] * (X[i] - x[i]);
-            }
-            s_nXr[j] = nXr;
-        }
-        for (int i = 0; i < 3; ++i) {
-            s_r[i] = x[i];
-            s_r0[i] = pose[i];
+            pn_normal(s_v.R0, pq[0] + dp, pq[1] + dq, n);
+            patch_plane_set(s_pl[j], s_v, n);
         }
         s_anchor[0] = to_level(list[k].imagePos[0], 0);
         s_anchor[1] = to_level(list[k].imagePos[1], 0);
-        for (int l = 0; l < 3; ++l) {
-            s_uv0l[l][0] = to_level(pose[7], l);
-            s_uv0l[l][1] = to_level(pose[8], l);
-        }
     }
     __syncthreads();
 
@@ -323,39 +310,30 @@ k_ncc_normal(Pyr pyr, const EkfMatch *list, int M, int N, const double *st, CamD
     bool bad = false;
     if (live) {
         double d[3];
-        pn_ray(c, s_R, ((double)(cxl + t % NCC_T - NCC_R) + 0.5) * sc - 0.5, ((double)(cyl + t / NCC_T - NCC_R) + 0.5) * sc - 0.5, d);
+        patch_ray(c, s_v.R, tmpl_pos(cxl, t % NCC_T, sc), tmpl_pos(cyl, t / NCC_T, sc), d);
 #pragma unroll
         for (int j = 0; j < 5; ++j)
-            if (!pn_to_source(c, d, s_n[j], s_nXr[j], s_r, s_r0, s_R0, s5[j])) bad = true;
+            if (!patch_to_source(c, s_v, s_pl[j], d, s5[j])) bad = true;
     } else if (anchor_lane) { // where the anchor itself lands at slope j
         const int j = t - NCC_TT;
         double d[3], s[2] = {0.0, 0.0};
-        pn_ray(c, s_R, (double)s_anchor[0], (double)s_anchor[1], d);
-        if (!pn_to_source(c, d, s_n[j], s_nXr[j], s_r, s_r0, s_R0, s)) s_bad[0] = s_bad[1] = s_bad[2] = 1;
+        patch_ray(c, s_v.R, (double)s_anchor[0], (double)s_anchor[1], d);
+        if (!patch_to_source(c, s_v, s_pl[j], d, s)) s_bad[0] = s_bad[1] = s_bad[2] = 1;
         s_anc[j][0] = s[0];
         s_anc[j][1] = s[1];
     }
     __syncthreads();
     if (live) {
-        const double offx = (double)(s_uv0l[l][0] - WARP_R), offy = (double)(s_uv0l[l][1] - WARP_R);
+        const int ux = s_v.uv0[l][0], uy = s_v.uv0[l][1];
         // the source's centre pixel (level 0) in this level's source coordinates: the anchor is moved onto it
-        const double ctrx = ((double)s_uv0l[0][0] + 0.5) / sc - 0.5 - offx, ctry = ((double)s_uv0l[0][1] + 0.5) / sc - 0.5 - offy;
+        const double ctrx = src_coord((double)s_v.uv0[0][0], sc, ux), ctry = src_coord((double)s_v.uv0[0][1], sc, uy);
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
             double b = 0.0;
             if (!bad) {
-                const double sx = ((s5[j][0] + 0.5) / sc - 0.5 - offx) - (((s_anc[j][0] + 0.5) / sc - 0.5 - offx) - ctrx);
-                const double sy = ((s5[j][1] + 0.5) / sc - 0.5 - offy) - (((s_anc[j][1] + 0.5) / sc - 0.5 - offy) - ctry);
-                if (sx >= 0.0 && sx <= (double)(WARP_S - 1) && sy >= 0.0 && sy <= (double)(WARP_S - 1)) {
-                    const int x0 = min((int)floor(sx), WARP_S - 2), y0 = min((int)floor(sy), WARP_S - 2);
-                    const double ax = sx - (double)x0, ay = sy - (double)y0;
-                    const uint8_t *p = s_src + l * WARP_SS + y0 * WARP_S + x0;
-                    const double top = (1.0 - ax) * (double)p[0] + ax * (double)p[1];
-                    const double bot = (1.0 - ax) * (double)p[WARP_S] + ax * (double)p[WARP_S + 1];
-                    b = (1.0 - ay) * top + ay * bot;
-                } else {
-                    bad = true;
-                }
+                const double sx = src_coord(s5[j][0], sc, ux) - (src_coord(s_anc[j][0], sc, ux) - ctrx);
+                const double sy = src_coord(s5[j][1], sc, uy) - (src_coord(s_anc[j][1], sc, uy) - ctry);
+                if (!patch_sample(s_src, l, sx, sy, &b)) bad = true;
             }
             s_vec[l][j][t] = b;
         }
@@ -483,6 +461,20 @@ __device__ inline void block_argmax(double &key, int &idx, double *s_key, int *s
     __syncthreads();
 }
 
+// sum of v over the workgroup in two halves around a barrier the caller has anyway (block_argmax's): every wavefront posts its
+// sum to s_cnt (NCC_BLOCK / 64 ints), and after the barrier block_sum_get adds them
+__device__ __forceinline__ void block_sum_post(int v, int *s_cnt)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = v;
+}
+__device__ __forceinline__ int block_sum_get(const int *s_cnt)
+{
+    int v = 0;
+    for (int w = 0; w < NCC_BLOCK / 64; ++w) v += s_cnt[w];
+    return v;
+}
+
 // ---- sub-pixel fit --------------------------------------------------------------------------
 // Offset of the vertex of the parabola through the keys at -1, 0, +1 pixels, one axis; *fit = 0 and offset 0 where the
 // rule leaves the integer: a neighbour outside the frame (key -2, see k_ncc_match) or without a score (-1), a neighbour
@@ -502,19 +494,17 @@ __device__ inline double subpix_offset(double km, double k0, double kp, int *fit
     return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
 }
 
-// One level of the search by the whole workgroup (256 lanes): stages the (cw + 10)^2 window whose candidates start at (x0, y0) and the
-// level's template tl in LDS, evaluates the candidates inside the frame -- at the coarse level (l == 2) only the predicted pixel
-// (gcx, gcy) and those whose centre lies in the gate -- and leaves the best one in (bx, by), its key in bkey: -3 and an unchanged
-// position when the level had no candidate (position carried over, as the CPU loop does).  Shared by k_ncc_match and
-// k_ncc_wide_finish.
-__device__ __forceinline__ void ncc_search_level(const Pyr &pyr, int l, int x0, int y0, int cw, const uint8_t *tl, const Gate &g, int gcx,
-                                                 int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double *s_key, int *s_idx, int &bx,
-                                                 int &by, double &bkey)
+// The candidate scan, shared by every level of k_ncc_match / k_ncc_wide_finish (ncc_search_level) and by the tiles of
+// k_ncc_wide_coarse.  The candidate rule, written once: a candidate is a pixel of the scanned box that lies inside the frame and,
+// at the coarse level (l == 2), is the predicted pixel (gcx, gcy) or has its centre in the gate; the best one is the first
+// maximum of the key in raster order.  block_argmax orders equal keys by idx, the candidate's raster position: in the frame
+// (comparable between the tiles of the wide search) or in the box (what the levels of one slot need; undone by a division by a
+// constant at the fine levels).
+
+// the level's template tl and its sums (s_tsum = sum, sum of squares) into LDS, by the whole workgroup
+__device__ __forceinline__ void ncc_stage_template(const uint8_t *tl, uint8_t *s_t, int *s_tsum)
 {
     const int tid = threadIdx.x;
-    const int pitch = cw + 2 * NCC_R;
-    for (int i = tid; i < pitch * pitch; i += 256)
-        s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + i % pitch, y0 - NCC_R + i / pitch);
     if (tid < NCC_TT) s_t[tid] = tl[tid];
     __syncthreads();
     if (tid == 0) {
@@ -523,19 +513,51 @@ __device__ __forceinline__ void ncc_search_level(const Pyr &pyr, int l, int x0, 
         s_tsum[0] = st; s_tsum[1] = stt;
     }
     __syncthreads();
+}
+
+// Stages the (cwx + 10) x (cwy + 10) window of the box of cwx x cwy candidates that starts at (x0, y0) and the template, and scans
+// the box: the lane's best key (-3: none) and its idx (0x7fffffff: none).  The two callers differ at compile time only:
+//   TILE = false (ncc_search_level): a square box, cwx == cwy, rows of cwx candidates, idx = the position in the box;
+//   TILE = true (k_ncc_wide_coarse): a box of up to 32 x 32 in rows of NCC_WIDE_TILE (no division), idx = y * w[l] + x, and the
+//   candidates the lane evaluated are counted in ncand.
+template <bool TILE>
+__device__ __forceinline__ void ncc_scan(const Pyr &pyr, int l, int x0, int y0, int cwx, int cwy, const uint8_t *tl, const Gate &g, int gcx,
+                                         int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double &key, int &idx, int &ncand)
+{
+    const int tid = threadIdx.x, row = TILE ? NCC_WIDE_TILE : cwx, pitch = row + 2 * NCC_R;
+    for (int i = tid; i < pitch * (cwy + 2 * NCC_R); i += NCC_BLOCK) {
+        const int ix = i % pitch, iy = i / pitch;
+        if (!TILE || ix < cwx + 2 * NCC_R) s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + ix, y0 - NCC_R + iy);
+    }
+    ncc_stage_template(tl, s_t, s_tsum);
     const int st = s_tsum[0], stt = s_tsum[1];
-    double key = -3.0;
-    int idx = 0x7fffffff;
-    for (int c = tid; c < cw * cw; c += 256) {
-        const int ox = c % cw, oy = c / cw, x = x0 + ox, y = y0 + oy;
+    key = -3.0;
+    idx = 0x7fffffff;
+    ncand = 0;
+    for (int c = tid; c < row * cwy; c += NCC_BLOCK) {
+        const int ox = c % row, oy = c / row, x = x0 + ox, y = y0 + oy;
+        if (TILE && ox >= cwx) continue;
         if (x < 0 || y < 0 || x >= pyr.w[l] || y >= pyr.h[l]) continue;
         if (l == 2 && !(x == gcx && y == gcy)) {
             const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
             if (!gate_contains(g, (double)fx, (double)fy)) continue;
         }
         const double kk = ncc_key(s_win, pitch, ox, oy, s_t, st, stt);
-        if (kk > key) { key = kk; idx = c; } // c ascending per thread: first maximum kept
+        if (TILE) ++ncand;
+        if (kk > key) { key = kk; idx = TILE ? y * pyr.w[l] + x : c; } // (y, x) ascending per lane: first maximum kept
     }
+}
+
+// One level of the search by the whole workgroup (256 lanes): scans the cw x cw candidates that start at (x0, y0) and leaves the
+// best one in (bx, by), its key in bkey: -3 and an unchanged position when the level had no candidate (position carried over, as
+// the CPU loop does).  s_t and s_tsum keep the level's template and its sums.
+__device__ __forceinline__ void ncc_search_level(const Pyr &pyr, int l, int x0, int y0, int cw, const uint8_t *tl, const Gate &g, int gcx,
+                                                 int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double *s_key, int *s_idx, int &bx,
+                                                 int &by, double &bkey)
+{
+    double key;
+    int idx, ncand;
+    ncc_scan<false>(pyr, l, x0, y0, cw, cw, tl, g, gcx, gcy, s_win, s_t, s_tsum, key, idx, ncand);
     block_argmax(key, idx, s_key, s_idx);
     if (idx != 0x7fffffff) { bx = x0 + idx % cw; by = y0 + idx / cw; }
     bkey = key;
@@ -731,46 +753,20 @@ k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot
     const WideSlot &ws = list[j];
     const int ntx = ws.tx;
     if (tile >= ntx * ws.ty) return;
-    const int cx = ws.cx, cy = ws.cy;
     const int tx0 = ws.x0 + (tile % ntx) * NCC_WIDE_TILE, ty0 = ws.y0 + (tile / ntx) * NCC_WIDE_TILE;
     const int cwx = min(NCC_WIDE_TILE, ws.x1 - tx0 + 1), cwy = min(NCC_WIDE_TILE, ws.y1 - ty0 + 1); // inside the frame: the box is
     const Gate g = ws.g;
     const int fi = plist[ws.slot];
-    const int wr = cwx + 2 * NCC_R, hr = cwy + 2 * NCC_R;
-    for (int i = tid; i < WIDE_WIN * hr; i += 256) {
-        const int ix = i % WIDE_WIN, iy = i / WIDE_WIN;
-        if (ix < wr) s_win[i] = (uint8_t)pyr_at(pyr, 2, tx0 - NCC_R + ix, ty0 - NCC_R + iy);
-    }
-    if (tid < NCC_TT) s_t[tid] = tmpl[((size_t)fi * 3 + 2) * NCC_TT + tid];
-    __syncthreads();
-    if (tid == 0) {
-        int st = 0, stt = 0;
-        for (int i = 0; i < NCC_TT; ++i) { st += s_t[i]; stt += s_t[i] * s_t[i]; }
-        s_tsum[0] = st; s_tsum[1] = stt;
-    }
-    __syncthreads();
-    const int st = s_tsum[0], stt = s_tsum[1], w2 = pyr.w[2];
-    double key = -3.0;
-    int idx = 0x7fffffff, ncand = 0;
-    for (int c = tid; c < NCC_WIDE_TILE * NCC_WIDE_TILE; c += 256) {
-        const int ox = c % NCC_WIDE_TILE, oy = c / NCC_WIDE_TILE, x = tx0 + ox, y = ty0 + oy;
-        if (ox >= cwx || oy >= cwy) continue;
-        if (!(x == cx && y == cy)) {
-            const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
-            if (!gate_contains(g, (double)fx, (double)fy)) continue;
-        }
-        const double kk = ncc_key(s_win, WIDE_WIN, ox, oy, s_t, st, stt);
-        ++ncand;
-        if (kk > key) { key = kk; idx = y * w2 + x; } // (y, x) ascending per thread: first maximum kept
-    }
-    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = ncand;
+    double key;
+    int idx, ncand;
+    ncc_scan<true>(pyr, 2, tx0, ty0, cwx, cwy, tmpl + ((size_t)fi * 3 + 2) * NCC_TT, g, ws.cx, ws.cy, s_win, s_t, s_tsum, key, idx, ncand);
+    block_sum_post(ncand, s_cnt);
     block_argmax(key, idx, s_key, s_idx); // (its barriers order s_cnt too)
     if (tid == 0) {
         WidePartial p;
         p.key = key;
         p.idx = idx;
-        p.ncand = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        p.ncand = block_sum_get(s_cnt);
         part[(size_t)j * max_tiles + tile] = p;
     }
 }
@@ -802,13 +798,12 @@ k_ncc_wide_finish(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot
         ncand += p.ncand;
         if (p.key > key || (p.key == key && p.idx < idx)) { key = p.key; idx = p.idx; }
     }
-    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = ncand;
+    block_sum_post(ncand, s_cnt);
     block_argmax(key, idx, s_key, s_idx); // (its barriers order g and s_cnt too)
     if (tid == 0) {
         // the candidates are summed in 64 bits by plain atomic adds (a compare-and-swap loop on one counter by a thousand workgroups
         // took milliseconds); the slot that finishes last writes the saturated sum to the counter block
-        atomicAdd(&totals->ncand, (unsigned long long)(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]));
+        atomicAdd(&totals->ncand, (unsigned long long)block_sum_get(s_cnt));
         __threadfence();
         if (atomicAdd(&totals->done, 1u) == (unsigned)counts[CNT_WIDE_SLOTS] - 1u) {
             __threadfence();
@@ -863,7 +858,7 @@ void launch_ncc_normal(EkfEngine *e, int M)
 {
     (void)hipMemsetAsync(e->d.counts + CNT_PN_UPD, 0, 2 * sizeof(int), e->stream);
     if (M > 0)
-        k_ncc_normal<<<M, 384, 0, e->stream>>>(pyr_of(e), e->d.pn_list, M, e->N, e->d.state, e->cam, e->d.feat_pos, e->d.feat_type, e->d.wsrc,
+        k_ncc_normal<<<M, PATCH_BLOCK, 0, e->stream>>>(pyr_of(e), e->d.pn_list, M, e->N, e->d.state, e->cam, e->d.feat_pos, e->d.feat_type, e->d.wsrc,
                                                e->d.wpose, e->d.wnorm, e->d.counts);
 }
 
@@ -876,7 +871,7 @@ static const uint8_t *match_templates(EkfEngine *e, int n_pred)
     (void)hipMemsetAsync(e->d.counts + CNT_WARP_OK, 0, 2 * sizeof(int), e->stream);
     (void)hipMemcpyAsync(e->d.wtmpl, e->d.tmpl, (size_t)e->N * 3 * NCC_TT, hipMemcpyDeviceToDevice, e->stream);
     if (n_pred > 0)
-        k_ncc_warp<<<n_pred, 384, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, e->d.pred_uv, e->d.state, e->cam, e->d.feat_pos,
+        k_ncc_warp<<<n_pred, PATCH_BLOCK, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, e->d.pred_uv, e->d.state, e->cam, e->d.feat_pos,
                                                   e->d.feat_type, e->d.wsrc, e->d.wpose, e->d.wtmpl, e->d.counts,
                                                   e->pn_on ? e->d.wnorm : nullptr);
     return e->d.wtmpl;

@@ -289,6 +289,23 @@ int ekf_set_ncc_wide_search(EkfEngine *e, int on);
 /* of the last NCC match: predictions searched wide, and the coarse candidates evaluated for them (saturating at
  * INT_MAX); 0 and 0 with the mode off */
 int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candidates);
+/* Distinctiveness test (opt-in; coef = 0 is off and the default: the path above, bit for bit).  With 0 < coef <= 1 an NCC
+ * match is accepted only if no second place in its gate scores nearly as well.  The rival is the best
+ * coarse candidate of the same search (same candidates, capped or wide) outside the 5 x 5 coarse pixels around the coarse
+ * best, first in raster order among equals, refined through the same two finer levels against the same templates; it
+ * counts only if its refined key is not negative and its pixel lies in the gate.  With d1 = (float)(1 - sqrt(key)) of the
+ * best (the match's distance) and d2 that of the rival, a match with a rival is kept when (double)d1 < (double)d2 * coef,
+ * strictly: two perfect repetitions (0 against 0) are ambiguous.  A rejected match leaves the list; the matches that stay,
+ * their positions, distances and order do not change, and the sub-pixel counts cover them only.  Takes effect with the
+ * next match (ekf_step_image, ekf_step_staged_image, ekf_match_ncc); composes with the modes above.  EKF_ERR_INVALID_ARG
+ * for a coef outside [0, 1] (NaN included; nothing changes) and for a non-zero coef on a sharded engine;
+ * EKF_IMAGE_MATCHER_KEYPOINTS ignores the mode.  Allocates 20 bytes per feature of capacity on first use. */
+int ekf_set_ncc_distinct(EkfEngine *e, double coef);
+/* of the last NCC match: accepted matches that had a rival, and those of them the test rejected; 0 and 0 with the mode off */
+int ekf_get_ncc_distinct_counts(const EkfEngine *e, int *with_rival, int *rejected);
+/* one record per prediction slot of the last NCC match, in slot order (the order of its predictions); *count receives
+ * their number, 0 with the mode off or before the first such match.  EKF_ERR_INVALID_ARG if capacity is smaller */
+int ekf_get_ncc_rivals(EkfEngine *e, EkfNccRival *out, int capacity, int *count);
 /* Patch normals (opt-in; off: the path above, bit for bit; needs the template warp).  The warp's patch plane faces the
  * camera that captured the feature; with this mode on each feature's plane has a slope (p, q) in that camera's axes --
  * normal n = R(q0) (p, q, -1) / |(p, q, -1)| in world axes -- estimated on the device by aligning the stored source

@@ -82,6 +82,16 @@ typedef struct EkfKeypoint {
     float x, y;
 } EkfKeypoint;
 
+/* What the NCC matcher's distinctiveness test (ekf_set_ncc_distinct) found for one prediction.  No counterpart in the
+ * reference, whose two-best test (Matching.cpp:188-262) lives in the descriptor matcher. */
+typedef struct EkfNccRival {
+    int32_t featureIndex;
+    int32_t state;       /* 0 = no valid match, 1 = valid and no rival in the gate, 2 = rival and kept, 3 = rival and rejected */
+    float rivalPos[2];   /* level-0 pixel of the rival (states 2, 3; else 0)                                              */
+    float distance;      /* 1 - zncc of the best place (states 1, 2, 3; else 0): the match's distance                    */
+    float rivalDistance; /* ... and of the rival (states 2, 3; else 0)                                                   */
+} EkfNccRival;           /* 24 bytes, no padding                                                                         */
+
 /* One landmark of the map as a 3-D point (ekf_get_map_points).  No counterpart in the reference, whose map is only
  * ever read in the filter's own parametrisation.  r, q = camera position and orientation (state elements 0..2, 3..6),
  * R(q) = Core/EKFMath.cpp:133-155, m(theta, phi) = Core/EKFMath.cpp:159-166. */

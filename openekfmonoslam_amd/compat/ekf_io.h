@@ -679,6 +679,9 @@ public:
     // NCC gates with a major semi-axis of 64 px or more searched whole instead of within 66 px of the prediction
     // (ekf_set_ncc_wide_search); at any time, it takes effect with the next step.  A setter for the same reason.
     void setWideSearch(bool on) { chk(ekf_set_ncc_wide_search(e_, on ? 1 : 0), "ekf_set_ncc_wide_search"); }
+    // NCC matches with a second place in the gate that scores nearly as well are dropped: kept when distance < rival distance * coef,
+    // 0 < coef <= 1, 0 = off (ekf_set_ncc_distinct); at any time, it takes effect with the next step.  A setter for the same reason.
+    void setNccDistinct(double coef) { chk(ekf_set_ncc_distinct(e_, coef), "ekf_set_ncc_distinct"); }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path, patchNormals_); }

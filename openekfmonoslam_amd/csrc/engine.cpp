@@ -137,7 +137,7 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -2090,19 +2090,20 @@ int ekf_get_step_keypoints(const EkfEngine *e, int *detected, int *kept)
 
 // wide search: the list of wide slots (cap records) and their per-tile partial results (cap x tiles of the coarse level), allocated
 // by the first match that needs them and again when a larger frame brings more tiles
-static int ensure_wide_tables(EkfEngine *e)
+// (parts = 2: a second partial table behind the first, for the rival pass of the distinctiveness test)
+static int ensure_wide_tables(EkfEngine *e, int parts)
 {
     const int tiles = ncc_wide_tiles(e->img.w[2], e->img.h[2]);
-    if (e->d.wide_list && tiles <= e->wide_tiles) return EKF_OK;
+    if (e->d.wide_list && tiles <= e->wide_tiles && parts <= e->wide_parts) return EKF_OK;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (void *p : {e->d.wide_list, e->d.wide_part})
         if (p) (void)hipFree(p);
     e->d.wide_list = e->d.wide_part = nullptr;
-    e->wide_tiles = 0;
+    e->wide_tiles = e->wide_parts = 0;
     uint8_t *list = nullptr, *part = nullptr;
     hipError_t st = dalloc(&list, (size_t)e->cap * NCC_WIDE_SLOT_BYTES + NCC_WIDE_TOTALS_BYTES);
-    if (st == hipSuccess) st = dalloc(&part, (size_t)e->cap * (size_t)std::max(tiles, 1) * NCC_WIDE_PARTIAL_BYTES);
+    if (st == hipSuccess) st = dalloc(&part, (size_t)parts * e->cap * (size_t)std::max(tiles, 1) * NCC_WIDE_PARTIAL_BYTES);
     if (st != hipSuccess) {
         if (list) (void)hipFree(list);
         e->err = std::string("wide search tables: ") + hipGetErrorString(st);
@@ -2111,6 +2112,7 @@ static int ensure_wide_tables(EkfEngine *e)
     e->d.wide_list = list;
     e->d.wide_part = part;
     e->wide_tiles = tiles;
+    e->wide_parts = parts;
     return EKF_OK;
 }
 
@@ -2122,9 +2124,10 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches)
     }
     e->last_match_warped = e->warp_on;
     const bool subpix = e->subpix_on, wide = e->wide_on;
-    int rc = wide ? ensure_wide_tables(e) : EKF_OK;
+    const double coef = e->distinct_coef;
+    int rc = wide ? ensure_wide_tables(e, coef > 0.0 ? 2 : 1) : EKF_OK;
     if (rc) return rc;
-    launch_match_ncc(e, e->n_pred, subpix, wide);
+    launch_match_ncc(e, e->n_pred, subpix, wide, coef);
     rc = read_counts(e);
     if (rc) return rc;
     *n_matches = e->h_counts[CNT_NMATCH];
@@ -2134,6 +2137,9 @@ static int match_ncc_dev(EkfEngine *e, int *n_matches)
     e->subpix_counts[1] = subpix ? e->h_counts[CNT_SUBPIX_INT] : 0;
     e->wide_counts[0] = wide ? e->h_counts[CNT_WIDE_SLOTS] : 0;
     e->wide_counts[1] = wide ? e->h_counts[CNT_WIDE_CANDS] : 0;
+    e->distinct_counts[0] = coef > 0.0 ? e->h_counts[CNT_RIVAL_WITH] : 0;
+    e->distinct_counts[1] = coef > 0.0 ? e->h_counts[CNT_RIVAL_REJ] : 0;
+    e->rival_slots = coef > 0.0 ? std::max(e->n_pred, 0) : 0;
     return check_async(e);
 }
 
@@ -2327,6 +2333,68 @@ int ekf_get_ncc_wide_counts(const EkfEngine *e, int *wide_slots, int *wide_candi
     if (!e) return EKF_ERR_INVALID_ARG;
     if (wide_slots) *wide_slots = e->wide_counts[0];
     if (wide_candidates) *wide_candidates = e->wide_counts[1];
+    return EKF_OK;
+}
+
+int ekf_set_ncc_distinct(EkfEngine *e, double coef)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (!(coef >= 0.0 && coef <= 1.0)) { // (NaN fails both)
+        e->err = "NCC distinctiveness test: the coefficient lies outside [0, 1]";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (coef > 0.0 && e->shard_world > 1) {
+        e->err = "NCC distinctiveness test: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (coef > 0.0 && !e->d.mt_rival) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        const hipError_t st = dalloc(&e->d.mt_rival, (size_t)e->cap);
+        if (st != hipSuccess) {
+            e->err = std::string("NCC distinctiveness table: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    e->distinct_coef = coef;
+    if (coef == 0.0) e->rival_slots = 0; // off: ekf_get_ncc_rivals has nothing to return
+    return EKF_OK;
+}
+
+int ekf_get_ncc_distinct_counts(const EkfEngine *e, int *with_rival, int *rejected)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (with_rival) *with_rival = e->distinct_counts[0];
+    if (rejected) *rejected = e->distinct_counts[1];
+    return EKF_OK;
+}
+
+int ekf_get_ncc_rivals(EkfEngine *e, EkfNccRival *out, int capacity, int *count)
+{
+    if (!e || !count || capacity < 0 || (capacity > 0 && !out)) return EKF_ERR_INVALID_ARG;
+    const int n = e->distinct_coef > 0.0 ? e->rival_slots : 0;
+    *count = n;
+    if (n == 0) return EKF_OK;
+    if (capacity < n) {
+        e->err = "ekf_get_ncc_rivals: the buffer holds fewer records than the last match had prediction slots";
+        return EKF_ERR_INVALID_ARG;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<NccRivalRec> rec((size_t)n);
+    std::vector<int> feat((size_t)n);
+    HIPCHK(hipMemcpy(rec.data(), e->d.mt_rival, (size_t)n * sizeof(NccRivalRec), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(feat.data(), e->d.plist, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < n; ++k) {
+        EkfNccRival o;
+        o.featureIndex = feat[k];
+        o.state = rec[k].state;
+        o.rivalPos[0] = (float)rec[k].rx;
+        o.rivalPos[1] = (float)rec[k].ry;
+        o.distance = rec[k].d1;
+        o.rivalDistance = rec[k].d2;
+        out[k] = o;
+    }
     return EKF_OK;
 }
 

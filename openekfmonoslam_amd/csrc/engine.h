@@ -41,6 +41,14 @@ struct RowMap {
 __host__ __device__ inline int local_row(const RowMap &m, int i) { return i < 13 ? i : m.base + (i - m.r0); }
 __host__ __device__ inline bool owns_row(const RowMap &m, int i) { return i < 13 || (i >= m.r0 && i < m.r1); }
 
+// distinctiveness test of the NCC matcher: what it found for one prediction slot
+struct NccRivalRec {
+    int state;  // 0 = not a valid match, 1 = valid and no rival, 2 = rival and kept, 3 = rival and rejected
+    int rx, ry; // level-0 pixel of the refined rival (states 2, 3; else 0)
+    float d1;   // 1 - sqrt(key) of the best (states 1, 2, 3; else 0)
+    float d2;   // ... and of the rival (states 2, 3; else 0)
+};
+
 // integer slots of the device counter block
 enum {
     CNT_NPRED = 0,    // predictions of the last full prediction
@@ -64,6 +72,8 @@ enum {
     CNT_WIDE_CANDS,   // ... and the coarse candidates evaluated for them, saturating at INT_MAX (k_ncc_wide_finish)
     CNT_PN_UPD,       // patch normals: features whose estimate the last estimator launch updated (k_ncc_normal)
     CNT_PN_SKIP,      // ... and listed features it left alone (no source patch, no usable level, solve not finite)
+    CNT_RIVAL_WITH,   // distinctiveness test: accepted matches of the last NCC match that had a rival in the gate (k_ncc_match<.., true>)
+    CNT_RIVAL_REJ,    // ... and those of them the test rejected
     CNT_COUNT = 40    // (publish_counts_block / k_publish_counts copy with the lanes t < 64; the mirror page holds 64 ints)
 };
 constexpr int MAX_SHARD_WORLD = 16;
@@ -111,6 +121,7 @@ struct DeviceArrays {
     int *mt_kp = nullptr;
     float *mt_dist = nullptr;
     EkfKeypoint *mt_xy = nullptr; // NCC matcher: matched pixel per prediction slot
+    NccRivalRec *mt_rival = nullptr; // NCC matcher, distinctiveness test (ekf_set_ncc_distinct): per prediction slot
     uint8_t *tmpl = nullptr;      // NCC matcher: 3 levels x 121 bytes per feature
     // template warp (ekf_set_template_warp; allocated by its first call)
     uint8_t *wsrc = nullptr;      // 3 levels x 41 x 41 source bytes per feature
@@ -291,6 +302,10 @@ struct EkfEngine {
     bool pn_on = false;            // ekf_set_patch_normals: patch normals estimated per frame and used by the warp
     int pn_counts[2] = {0, 0};     // features updated / skipped by the last estimator launch
     int wide_tiles = 0;            // tiles per slot d.wide_part was allocated for (the coarse level's tile count)
+    int wide_parts = 0;            // partial tables d.wide_part holds, one behind the other: 1, or 2 for the rival pass
+    double distinct_coef = 0.0;    // ekf_set_ncc_distinct: 0 = off, else an NCC match with a rival peak is kept when d1 < d2 * coef
+    int distinct_counts[2] = {0, 0}; // accepted matches with a rival / rejected by the test in the last NCC match
+    int rival_slots = 0;           // prediction slots of the last NCC match that ran with the test on (records of d.mt_rival)
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -447,7 +462,8 @@ void launch_ncc_warp_capture(EkfEngine *e, const int *d_idx, const double *d_uv,
 void launch_ncc_normal(EkfEngine *e, int M);
 // subpix: k_ncc_match<true>, positions refined by the fit of DESIGN.md 4.7; wide: the slots whose gate exceeds the coarse window go
 // through the three kernels of DESIGN.md 4.8 instead (d.wide_list / d.wide_part sized for the current frame: engine.cpp)
-void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide);
+// coef > 0: the distinctiveness test of DESIGN.md 4.10 (d.mt_rival, CNT_RIVAL_WITH / CNT_RIVAL_REJ; with wide, d.wide_part holds two tables)
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide, double coef);
 constexpr int NCC_TT = 121;                // bytes of one 11 x 11 template; d.tmpl / d.wtmpl hold 3 levels per feature
 constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S; // template warp: side and bytes of one source patch; d.wsrc holds 3 per feature
 constexpr int WPOSE_DOUBLES = 9;           // ... and its capture pose record in d.wpose: r0 (3), q0 (4), capture pixel (2)

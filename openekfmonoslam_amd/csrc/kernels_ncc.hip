@@ -520,16 +520,23 @@ __device__ __forceinline__ void ncc_stage_template(const uint8_t *tl, uint8_t *s
 //   TILE = false (ncc_search_level): a square box, cwx == cwy, rows of cwx candidates, idx = the position in the box;
 //   TILE = true (k_ncc_wide_coarse): a box of up to 32 x 32 in rows of NCC_WIDE_TILE (no division), idx = y * w[l] + x, and the
 //   candidates the lane evaluated are counted in ncand.
-template <bool TILE>
+// EXCL (the rival pass of the distinctiveness test): the candidates within NCC_RIVAL_EXCL pixels (Chebyshev) of
+// (ex, ey) are left out; SCAN_EXCL_STAGED: and the window and the template are those an earlier scan of the same box staged.
+enum { SCAN_ALL = 0, SCAN_EXCL = 1, SCAN_EXCL_STAGED = 2 };
+constexpr int NCC_RIVAL_EXCL = 2; // the best peak's own lobe: 5 x 5 coarse pixels
+template <bool TILE, int EXCL = SCAN_ALL>
 __device__ __forceinline__ void ncc_scan(const Pyr &pyr, int l, int x0, int y0, int cwx, int cwy, const uint8_t *tl, const Gate &g, int gcx,
-                                         int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double &key, int &idx, int &ncand)
+                                         int gcy, uint8_t *s_win, uint8_t *s_t, int *s_tsum, double &key, int &idx, int &ncand, int ex = 0,
+                                         int ey = 0)
 {
     const int tid = threadIdx.x, row = TILE ? NCC_WIDE_TILE : cwx, pitch = row + 2 * NCC_R;
-    for (int i = tid; i < pitch * (cwy + 2 * NCC_R); i += NCC_BLOCK) {
-        const int ix = i % pitch, iy = i / pitch;
-        if (!TILE || ix < cwx + 2 * NCC_R) s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + ix, y0 - NCC_R + iy);
+    if constexpr (EXCL != SCAN_EXCL_STAGED) {
+        for (int i = tid; i < pitch * (cwy + 2 * NCC_R); i += NCC_BLOCK) {
+            const int ix = i % pitch, iy = i / pitch;
+            if (!TILE || ix < cwx + 2 * NCC_R) s_win[i] = (uint8_t)pyr_at(pyr, l, x0 - NCC_R + ix, y0 - NCC_R + iy);
+        }
+        ncc_stage_template(tl, s_t, s_tsum);
     }
-    ncc_stage_template(tl, s_t, s_tsum);
     const int st = s_tsum[0], stt = s_tsum[1];
     key = -3.0;
     idx = 0x7fffffff;
@@ -538,6 +545,8 @@ __device__ __forceinline__ void ncc_scan(const Pyr &pyr, int l, int x0, int y0, 
         const int ox = c % row, oy = c / row, x = x0 + ox, y = y0 + oy;
         if (TILE && ox >= cwx) continue;
         if (x < 0 || y < 0 || x >= pyr.w[l] || y >= pyr.h[l]) continue;
+        if constexpr (EXCL != SCAN_ALL)
+            if (abs(x - ex) <= NCC_RIVAL_EXCL && abs(y - ey) <= NCC_RIVAL_EXCL) continue;
         if (l == 2 && !(x == gcx && y == gcy)) {
             const float fx = (float)((x + 0.5) * 4 - 0.5), fy = (float)((y + 0.5) * 4 - 0.5);
             if (!gate_contains(g, (double)fx, (double)fy)) continue;
@@ -563,14 +572,34 @@ __device__ __forceinline__ void ncc_search_level(const Pyr &pyr, int l, int x0, 
     bkey = key;
 }
 
+// Levels 1 and 0 from the coarse pixel (bx, by): the 4 x 4 children of the best parent, twice.  t3 = the feature's three templates.
+__device__ __forceinline__ void ncc_refine(const Pyr &pyr, const uint8_t *t3, const Gate &g, uint8_t *s_win, uint8_t *s_t, int *s_tsum,
+                                           double *s_key, int *s_idx, int &bx, int &by, double &bkey)
+{
+    for (int l = 1; l >= 0; --l)
+        ncc_search_level(pyr, l, 2 * bx - 1, 2 * by - 1, 4, t3 + l * NCC_TT, g, 0, 0, s_win, s_t, s_tsum, s_key, s_idx, bx, by, bkey);
+}
+
+// Distinctiveness test (ekf_set_ncc_distinct; tests/ncc_distinct_ref.py is the definition): the slot's table and
+// the coefficient, and what the rival pass of one slot found (uniform over the workgroup)
+struct NccRivalOut {
+    NccRivalRec *tab;
+    double coef;
+};
+struct NccRival {
+    int x, y;   // coarse pixel, then the refined level-0 pixel
+    double key; // < 0: no rival
+};
+
 // What follows the level-0 search of prediction slot k, by the whole workgroup: the acceptance test and the slot's entries of the
 // match tables.  SUBPIX (ekf_set_subpixel_matches): the keys of the best pixel's four level-0 neighbours are evaluated first and
 // each axis of the reported position is moved by subpix_offset; counts then receives the fitted / integer axes of the valid
 // matches.  SUBPIX = false is the integer matcher as it was.  s_t and s_tsum still hold the level-0 template and its sums.
-template <bool SUBPIX>
+// RIVAL: an accepted match whose refined rival rv lies in the gate is kept only if d1 < d2 * coef; the slot's record goes to out.tab.
+template <bool SUBPIX, bool RIVAL>
 __device__ __forceinline__ void ncc_finish_slot(const Pyr &pyr, const Gate &g, int k, int bx, int by, double bkey, uint8_t *s_win,
                                                 const uint8_t *s_t, const int *s_tsum, double *s_key, int *mt_valid, EkfKeypoint *mt_xy,
-                                                float *mt_dist, int *counts)
+                                                float *mt_dist, int *counts, const NccRival &rv, const NccRivalOut &out)
 {
     const int tid = threadIdx.x;
     if constexpr (SUBPIX) {
@@ -589,7 +618,20 @@ __device__ __forceinline__ void ncc_finish_slot(const Pyr &pyr, const Gate &g, i
         }
     }
     if (tid == 0) {
-        const bool ok = bkey >= 0.64 && gate_contains(g, (double)(float)bx, (double)(float)by);
+        bool ok = bkey >= 0.64 && gate_contains(g, (double)(float)bx, (double)(float)by);
+        if constexpr (RIVAL) {
+            NccRivalRec rec = {ok ? 1 : 0, 0, 0, ok ? (float)(1.0 - sqrt(bkey)) : 0.f, 0.f};
+            if (ok && rv.key >= 0.0 && gate_contains(g, (double)(float)rv.x, (double)(float)rv.y)) { // a place that could have been accepted
+                rec.rx = rv.x;
+                rec.ry = rv.y;
+                rec.d2 = (float)(1.0 - sqrt(rv.key));
+                ok = (double)rec.d1 < (double)rec.d2 * out.coef; // strict: two perfect repetitions are ambiguous
+                rec.state = ok ? 2 : 3;
+                atomicAdd(counts + CNT_RIVAL_WITH, 1);
+                if (!ok) atomicAdd(counts + CNT_RIVAL_REJ, 1);
+            }
+            out.tab[k] = rec;
+        }
         mt_valid[k] = ok ? 1 : 0;
         EkfKeypoint p;
         if constexpr (SUBPIX) {
@@ -632,10 +674,12 @@ __device__ __forceinline__ void ncc_slot_geometry(double pu, double pv, const do
 // One workgroup per prediction slot.  The coarse level covers the square of radius min(rad, NCC_MAXRAD) around the prediction: a
 // gate whose major semi-axis is 64 px or more is searched within +-16 coarse pixels (about +-66 px) only.  skip_wide (wide search,
 // DESIGN.md 4.8): such a slot is left to k_ncc_wide_coarse / k_ncc_wide_finish and this workgroup returns without writing anything.
-template <bool SUBPIX>
+// RIVAL: the coarse window staged in LDS is scanned a second time without the 5 x 5 block around the coarse best,
+// and the best of that pass is refined like the best itself.
+template <bool SUBPIX, bool RIVAL>
 __global__ void __launch_bounds__(256)
 k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *tmpl,
-            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0, int *counts, int skip_wide)
+            int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int slot0, int *counts, int skip_wide, NccRivalOut rout)
 {
     __shared__ Gate g;
     __shared__ int s_geom[4]; // c2x, c2y, rad, skipped
@@ -658,15 +702,23 @@ k_ncc_match(Pyr pyr, const int *plist, const double *uv_tab, const double *S_tab
 
     int bx = s_geom[0], by = s_geom[1];
     double bkey = -3.0;
-    for (int l = 2; l >= 0; --l) {
-        // candidate window at this level: coarse = the gated square around the prediction, finer = 4x4 children
-        int x0, y0, cw;
-        if (l == 2) { x0 = s_geom[0] - s_geom[2]; y0 = s_geom[1] - s_geom[2]; cw = 2 * s_geom[2] + 1; }
-        else { x0 = 2 * bx - 1; y0 = 2 * by - 1; cw = 4; }
-        ncc_search_level(pyr, l, x0, y0, cw, tmpl + ((size_t)fi * 3 + l) * NCC_TT, g, s_geom[0], s_geom[1], s_win, s_t, s_tsum, s_key,
-                         s_idx, bx, by, bkey);
+    const uint8_t *t3 = tmpl + (size_t)fi * 3 * NCC_TT;
+    // coarse level: the gated square around the prediction; then the 4x4 children, twice
+    const int x0 = s_geom[0] - s_geom[2], y0 = s_geom[1] - s_geom[2], cw = 2 * s_geom[2] + 1;
+    ncc_search_level(pyr, 2, x0, y0, cw, t3 + 2 * NCC_TT, g, s_geom[0], s_geom[1], s_win, s_t, s_tsum, s_key, s_idx, bx, by, bkey);
+    NccRival rv = {0, 0, -3.0};
+    if constexpr (RIVAL) { // the keys outside the block are evaluated again: fewer registers than keeping them
+        int idx, ncand;
+        ncc_scan<false, SCAN_EXCL_STAGED>(pyr, 2, x0, y0, cw, cw, nullptr, g, s_geom[0], s_geom[1], s_win, s_t, s_tsum, rv.key, idx, ncand, bx, by);
+        block_argmax(rv.key, idx, s_key, s_idx);
+        if (rv.key >= 0.0) { // uniform
+            rv.x = x0 + idx % cw;
+            rv.y = y0 + idx / cw;
+            ncc_refine(pyr, t3, g, s_win, s_t, s_tsum, s_key, s_idx, rv.x, rv.y, rv.key);
+        }
     }
-    ncc_finish_slot<SUBPIX>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts);
+    ncc_refine(pyr, t3, g, s_win, s_t, s_tsum, s_key, s_idx, bx, by, bkey); // (last: s_t ends as the level-0 template either way)
+    ncc_finish_slot<SUBPIX, RIVAL>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts, rv, rout);
 }
 
 // ---- wide search ----------------------------------------------------------------------------
@@ -738,8 +790,13 @@ k_ncc_wide_classify(const int *plist, const int *d_npred, int n_pred, const doub
 
 // grid = (tiles of the coarse level, prediction slots): workgroup (t, j) searches tile t of the j-th wide slot's box and writes one
 // partial result.  The sums of ncc_key are integers, so the tile's candidates give the bits k_ncc_match would give.
+// RIVAL: a second launch behind the first.  Every workgroup reduces the slot's partials of the first launch (first)
+// to the coarse best, as k_ncc_wide_finish does -- a handful of records, and no order of the tiles can change the result --, and
+// scans its tile without the block around it.
+template <bool RIVAL>
 __global__ void __launch_bounds__(256)
-k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot *list, const int *counts, WidePartial *part, int max_tiles)
+k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot *list, const int *counts, WidePartial *part, int max_tiles,
+                  const WidePartial *first)
 {
     __shared__ uint8_t s_win[WIDE_WIN * WIDE_WIN];
     __shared__ uint8_t s_t[NCC_TT + 3];
@@ -758,8 +815,24 @@ k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot
     const Gate g = ws.g;
     const int fi = plist[ws.slot];
     double key;
-    int idx, ncand;
-    ncc_scan<true>(pyr, 2, tx0, ty0, cwx, cwy, tmpl + ((size_t)fi * 3 + 2) * NCC_TT, g, ws.cx, ws.cy, s_win, s_t, s_tsum, key, idx, ncand);
+    int idx, ncand, ex = 0, ey = 0;
+    if constexpr (RIVAL) {
+        key = -3.0;
+        idx = 0x7fffffff;
+        for (int t = tid; t < ntx * ws.ty; t += NCC_BLOCK) {
+            const WidePartial p = first[(size_t)j * max_tiles + t];
+            if (p.key > key || (p.key == key && p.idx < idx)) { key = p.key; idx = p.idx; }
+        }
+        block_argmax(key, idx, s_key, s_idx);
+        if (idx == 0x7fffffff) { // uniform: the slot has no candidate at all
+            if (tid == 0) part[(size_t)j * max_tiles + tile] = WidePartial{-3.0, 0x7fffffff, 0};
+            return;
+        }
+        ex = idx % pyr.w[2];
+        ey = idx / pyr.w[2];
+    }
+    ncc_scan<true, RIVAL ? SCAN_EXCL : SCAN_ALL>(pyr, 2, tx0, ty0, cwx, cwy, tmpl + ((size_t)fi * 3 + 2) * NCC_TT, g, ws.cx, ws.cy, s_win, s_t,
+                                                 s_tsum, key, idx, ncand, ex, ey);
     block_sum_post(ncand, s_cnt);
     block_argmax(key, idx, s_key, s_idx); // (its barriers order s_cnt too)
     if (tid == 0) {
@@ -772,11 +845,12 @@ k_ncc_wide_coarse(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot
 }
 
 // One workgroup per wide slot: the best of its tiles (larger key, then the smaller (y, x): block_argmax's rule, whatever the order
-// of the tiles), then levels 1 and 0 and the tail of k_ncc_match.
-template <bool SUBPIX>
+// of the tiles), then levels 1 and 0 and the tail of k_ncc_match.  RIVAL: the rival pass's table part2 is reduced the same way.
+template <bool SUBPIX, bool RIVAL>
 __global__ void __launch_bounds__(256)
 k_ncc_wide_finish(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot *list, const WidePartial *part, int max_tiles,
-                  WideTotals *totals, int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int *counts)
+                  WideTotals *totals, int *mt_valid, EkfKeypoint *mt_xy, float *mt_dist, int *counts, const WidePartial *part2,
+                  NccRivalOut rout)
 {
     __shared__ Gate g;
     __shared__ uint8_t s_win[14 * 14 + 4]; // 4 x 4 children and their border; the 13 x 13 window of the sub-pixel fit
@@ -814,10 +888,23 @@ k_ncc_wide_finish(Pyr pyr, const int *plist, const uint8_t *tmpl, const WideSlot
     int bx = ws.cx, by = ws.cy;
     if (idx != 0x7fffffff) { bx = idx % pyr.w[2]; by = idx / pyr.w[2]; }
     double bkey = key;
-    for (int l = 1; l >= 0; --l)
-        ncc_search_level(pyr, l, 2 * bx - 1, 2 * by - 1, 4, tmpl + ((size_t)fi * 3 + l) * NCC_TT, g, 0, 0, s_win, s_t, s_tsum, s_key, s_idx,
-                         bx, by, bkey);
-    ncc_finish_slot<SUBPIX>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts);
+    const uint8_t *t3 = tmpl + (size_t)fi * 3 * NCC_TT;
+    NccRival rv = {0, 0, -3.0};
+    if constexpr (RIVAL) {
+        int ridx = 0x7fffffff;
+        for (int t = tid; t < ntiles; t += NCC_BLOCK) {
+            const WidePartial p = part2[(size_t)j * max_tiles + t];
+            if (p.key > rv.key || (p.key == rv.key && p.idx < ridx)) { rv.key = p.key; ridx = p.idx; }
+        }
+        block_argmax(rv.key, ridx, s_key, s_idx);
+        if (rv.key >= 0.0) { // uniform
+            rv.x = ridx % pyr.w[2];
+            rv.y = ridx / pyr.w[2];
+            ncc_refine(pyr, t3, g, s_win, s_t, s_tsum, s_key, s_idx, rv.x, rv.y, rv.key);
+        }
+    }
+    ncc_refine(pyr, t3, g, s_win, s_t, s_tsum, s_key, s_idx, bx, by, bkey);
+    ncc_finish_slot<SUBPIX, RIVAL>(pyr, g, k, bx, by, bkey, s_win, s_t, s_tsum, s_key, mt_valid, mt_xy, mt_dist, counts, rv, rout);
 }
 
 static Pyr pyr_of(const EkfEngine *e)
@@ -878,27 +965,31 @@ static const uint8_t *match_templates(EkfEngine *e, int n_pred)
 }
 
 // the NCC search of the prediction slots [s_lo, s_hi); subpix: with the parabola fit, whose axis counters it zeroes first
-static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_hi, bool subpix, bool skip_wide = false)
+// coef > 0: with the distinctiveness test (its counters are zeroed by launch_match_ncc)
+static void match_ncc_slots(EkfEngine *e, const uint8_t *tmpl, int s_lo, int s_hi, bool subpix, bool skip_wide = false, double coef = 0.0)
 {
     if (subpix) {
         (void)hipMemsetAsync(e->d.counts + CNT_SUBPIX_FIT, 0, sizeof(int), e->stream);
         (void)hipMemsetAsync(e->d.counts + CNT_SUBPIX_INT, 0, sizeof(int), e->stream);
     }
     if (s_hi <= s_lo) return;
-    auto kern = subpix ? k_ncc_match<true> : k_ncc_match<false>;
+    const bool rival = coef > 0.0;
+    auto kern = rival ? (subpix ? k_ncc_match<true, true> : k_ncc_match<false, true>) : (subpix ? k_ncc_match<true, false> : k_ncc_match<false, false>);
     kern<<<s_hi - s_lo, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, e->d.pred_uv, e->d.pred_S, tmpl, e->d.mt_valid, e->d.mt_xy,
-                                             e->d.mt_dist, s_lo, e->d.counts, skip_wide ? 1 : 0);
+                                             e->d.mt_dist, s_lo, e->d.counts, skip_wide ? 1 : 0, NccRivalOut{rival ? e->d.mt_rival : nullptr, coef});
 }
 
-void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide)
+void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide, double coef)
 {
     const uint8_t *tmpl = match_templates(e, n_pred);
+    const bool rival = coef > 0.0;
+    if (rival) (void)hipMemsetAsync(e->d.counts + CNT_RIVAL_WITH, 0, 2 * sizeof(int), e->stream);
     WideSlot *list = (WideSlot *)e->d.wide_list;
     WideTotals *totals = (WideTotals *)((uint8_t *)e->d.wide_list + (size_t)e->cap * NCC_WIDE_SLOT_BYTES);
     if (wide && n_pred > 0) // before k_ncc_match: it zeroes CNT_WIDE_CANDS, and nothing of the wide path depends on the narrow one
         k_ncc_wide_classify<<<1, 1024, 0, e->stream>>>(e->d.plist, e->d.counts + CNT_NPRED, n_pred, e->d.pred_uv, e->d.pred_S, e->img.w[2],
                                                        e->img.h[2], list, totals, e->d.counts);
-    match_ncc_slots(e, tmpl, 0, n_pred, subpix, wide);
+    match_ncc_slots(e, tmpl, 0, n_pred, subpix, wide, coef);
     if (n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
         if (wide) (void)hipMemsetAsync(e->d.counts + CNT_WIDE_SLOTS, 0, 2 * sizeof(int), e->stream);
@@ -906,11 +997,16 @@ void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide)
     }
     if (wide) { // k_ncc_match has skipped the wide slots (and left their sub-pixel counts to k_ncc_wide_finish)
         const int tiles = ncc_wide_tiles(e->img.w[2], e->img.h[2]);
-        WidePartial *part = (WidePartial *)e->d.wide_part;
-        k_ncc_wide_coarse<<<dim3(tiles, n_pred), 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, e->d.counts, part, e->wide_tiles);
-        auto fin = subpix ? k_ncc_wide_finish<true> : k_ncc_wide_finish<false>;
+        WidePartial *part = (WidePartial *)e->d.wide_part, *part2 = rival ? part + (size_t)e->cap * e->wide_tiles : nullptr;
+        k_ncc_wide_coarse<false><<<dim3(tiles, n_pred), 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, e->d.counts, part, e->wide_tiles,
+                                                                             nullptr);
+        if (rival) // the rival pass: the same tiles without the block around the slot's coarse best, into the second table
+            k_ncc_wide_coarse<true><<<dim3(tiles, n_pred), 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, e->d.counts, part2,
+                                                                                e->wide_tiles, part);
+        auto fin = rival ? (subpix ? k_ncc_wide_finish<true, true> : k_ncc_wide_finish<false, true>)
+                         : (subpix ? k_ncc_wide_finish<true, false> : k_ncc_wide_finish<false, false>);
         fin<<<n_pred, 256, 0, e->stream>>>(pyr_of(e), e->d.plist, tmpl, list, part, e->wide_tiles, totals, e->d.mt_valid, e->d.mt_xy, e->d.mt_dist,
-                                            e->d.counts);
+                                            e->d.counts, part2, NccRivalOut{rival ? e->d.mt_rival : nullptr, coef});
     }
     launch_match_compact_slots(e, n_pred, e->d.mt_xy);
 }

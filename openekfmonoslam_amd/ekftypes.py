@@ -89,6 +89,12 @@ MAP_POINT_DTYPE = np.dtype(
 )
 assert MAP_POINT_DTYPE.itemsize == C.sizeof(EkfMapPoint) == 216
 assert PREDICTION_DTYPE.itemsize == 56 and MATCH_DTYPE.itemsize == 32 and KEYPOINT_DTYPE.itemsize == 8
+# EkfNccRival: what the NCC matcher's distinctiveness test found for one prediction (state 0 = no valid match, 1 = valid and no
+# rival in the gate, 2 = rival and kept, 3 = rival and rejected)
+NCC_RIVAL_DTYPE = np.dtype(
+    [("featureIndex", "<i4"), ("state", "<i4"), ("rivalPos", "<f4", (2,)), ("distance", "<f4"), ("rivalDistance", "<f4")]
+)
+assert NCC_RIVAL_DTYPE.itemsize == 24
 
 DESC_BYTES = 32
 FEATURE_DEPTH = 1

@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, PREDICTION_DTYPE, STATUS_NAMES, EkfCamera,
-                       EkfMapPoint, EkfParams, EkfStepInfo)
+from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, NCC_RIVAL_DTYPE, PREDICTION_DTYPE, STATUS_NAMES,
+                       EkfCamera, EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
@@ -115,6 +115,9 @@ ABI = {
     "ekf_get_subpixel_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_set_ncc_wide_search": (_i, [_vp, _i]),
     "ekf_get_ncc_wide_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "ekf_set_ncc_distinct": (_i, [_vp, C.c_double]),
+    "ekf_get_ncc_distinct_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "ekf_get_ncc_rivals": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ekf_set_patch_normals": (_i, [_vp, _i]),
     "ekf_refine_patch_normals": (_i, [_vp, _vp, _i]),
     "ekf_get_patch_normals": (_i, [_vp, _vp, _i, _vp]),
@@ -572,6 +575,24 @@ class EkfEngine:
         a, b = _i(0), _i(0)
         self._chk(self.L.ekf_get_ncc_wide_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_ncc_distinct(self, coef):
+        """NCC matches with a rival peak in the gate are kept only if distance < rival distance * coef, 0 < coef <= 1
+        (DESIGN.md 4.10); 0: off"""
+        self._chk(self.L.ekf_set_ncc_distinct(self.h, float(coef)))
+
+    def ncc_distinct_counts(self):
+        """(accepted matches that had a rival, those of them rejected) in the last NCC match"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_ncc_distinct_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def ncc_rivals(self):
+        """NCC_RIVAL_DTYPE [predictions of the last NCC match], in their order; empty with the mode off"""
+        out = np.zeros(max(self.cap, 1), dtype=NCC_RIVAL_DTYPE)
+        n = _i(0)
+        self._chk(self.L.ekf_get_ncc_rivals(self.h, _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
 
     def set_patch_normals(self, on=True):
         """the warp's patch planes get a normal estimated from the images, one estimator step per image step (DESIGN.md 4.9);

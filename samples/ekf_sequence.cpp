@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -9,6 +9,8 @@
 // --wide-search (likewise): gates larger than the coarse search window are searched whole (ImageEKF::setWideSearch).
 // --patch-normals (likewise; implies --warp-templates): the normals of the warp's patches are estimated from the images
 // (ImageEKF::setPatchNormals) and map.ply carries them as nx ny nz.
+// --ncc-distinct COEF (likewise): an NCC match with a second place in its gate is kept only if its distance is below COEF times
+// the rival's, 0 < COEF <= 1 (ImageEKF::setNccDistinct).
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -20,8 +22,14 @@
 int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false; // the flags are taken out of the argument list; the positional arguments keep their places
+    double distinct = 0.0;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search" ||
+        if (std::string(argv[i]) == "--ncc-distinct" && i + 1 < argc) { // the flag and its value
+            distinct = std::atof(argv[i + 1]);
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            --i;
+        } else if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search" ||
             std::string(argv[i]) == "--patch-normals") {
             if (std::string(argv[i]) == "--patch-normals") normals = true;
             (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
@@ -30,7 +38,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -45,7 +53,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -63,12 +71,13 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches or the wide search asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search or the distinctiveness test asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
         extendedKalmanFilter.setSubpixelMatches(subpix);
         extendedKalmanFilter.setWideSearch(wide);
+        extendedKalmanFilter.setNccDistinct(distinct);
         extendedKalmanFilter.init(image);
         std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
         image = generator.getNextImage();
@@ -98,6 +107,11 @@ int main(int argc, const char *argv[])
                 int slots = 0, cands = 0;
                 ekf_get_ncc_wide_counts(extendedKalmanFilter.engine(), &slots, &cands);
                 std::printf("        gates searched wide %d, coarse candidates %d\n", slots, cands);
+            }
+            if (distinct != 0.0) {
+                int with_rival = 0, rejected = 0;
+                ekf_get_ncc_distinct_counts(extendedKalmanFilter.engine(), &with_rival, &rejected);
+                std::printf("        matches with a rival in the gate %d, rejected %d\n", with_rival, rejected);
             }
             image = generator.getNextImage();
         }

@@ -162,6 +162,26 @@ int ekf_get_feature_layout(EkfEngine *e, int32_t *type, int32_t *covpos);
 int ekf_keep_step_predictions(EkfEngine *e, int on);
 int ekf_get_step_predictions(EkfEngine *e, EkfPrediction *preds, int *n_preds);
 
+/* Filter consistency (opt-in; off: no extra launch, allocation or read-back, every result bit for bit).  With the mode on
+ * every covariance update -- ekf_update, and the first and the second update inside ekf_step, ekf_step_frame, ekf_step_image
+ * and ekf_step_staged_image; not ekf_update_only_state, not RANSAC hypotheses -- is followed by one small launch that records
+ * its normalised innovation squared and, per match, the innovation, its marginal Mahalanobis distance and its conditional
+ * share of the NIS (EkfUpdateConsistency / EkfInnovation, ekf_types.h).  Records and running totals stay on
+ * the device until a getter asks; a step gains no read-back.  An update that was skipped (no matches, S not positive definite)
+ * leaves no record.  Allocates 48 bytes x 2 x max_features plus a 96-byte control block on first use.  EKF_ERR_INVALID_ARG on a
+ * sharded engine. */
+int ekf_set_consistency(EkfEngine *e, int on);
+/* the updates recorded since the last step or ekf_update began: 0 to 2 records, in the order they ran.  The getters below
+ * synchronise the stream and report a pending asynchronous error as ekf_get_state does.  out may be NULL (count only);
+ * capacity < *count -> EKF_ERR_CAPACITY with *count = number needed. */
+int ekf_get_consistency(EkfEngine *e, EkfUpdateConsistency *out, int capacity, int *count);
+/* the matches of record `which` of ekf_get_consistency, in the update's order */
+int ekf_get_innovations(EkfEngine *e, int which, EkfInnovation *out, int capacity, int *count);
+/* sums over every update recorded since the engine was created or the totals were last reset, added on the device in the
+ * order the updates ran (two runs give the same bits); any pointer may be NULL */
+int ekf_get_consistency_totals(EkfEngine *e, double *nis_sum, int64_t *rows_sum, int64_t *updates);
+int ekf_reset_consistency_totals(EkfEngine *e);
+
 /* -- stages ---------------------------------------------------------------------------------------------- */
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);

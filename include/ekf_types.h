@@ -106,6 +106,27 @@ typedef struct EkfMapPoint {
     uint32_t times_predicted, times_matched;
 } EkfMapPoint;         /* 25 doubles + 4 x 32 bit = 216 bytes, no padding                                            */
 
+/* Filter consistency (ekf_set_consistency): one record per covariance update, and one per match of such an update.  No
+ * counterpart in the reference.  With S = H P H' + pixelErrorX I of the update, L its Cholesky factor and nu the dead-banded
+ * innovation in the update's order: z = inv(L) nu, nis = sum of z_k^2 (chi-square with `rows` degrees of freedom for a
+ * consistent filter). */
+typedef struct EkfUpdateConsistency {
+    int32_t stage;   /* 0 = ekf_update, 1 = a step's first (low-innovation) update, 2 = its second (high-innovation) update */
+    int32_t matches; /* M                                                                                                   */
+    int32_t rows;    /* m = 2 M: the degrees of freedom of nis                                                              */
+    int32_t _pad;
+    double nis;
+} EkfUpdateConsistency; /* 24 bytes */
+
+typedef struct EkfInnovation {
+    int32_t featureIndex;
+    int32_t stage;
+    double nu[2];           /* innovation: imagePos - predicted distorted pixel, 0 where |.| <= EKF_DELTA                   */
+    double d2_marginal;     /* nu' inv(S_i) nu with S_i the match's own 2x2 block of S; 1e300 when det(S_i) <= 0             */
+    double nis_conditional; /* z_2i^2 + z_2i+1^2: the match's share of nis, conditional on the matches before it in the list */
+    double _reserved;
+} EkfInnovation; /* 48 bytes, no padding */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

@@ -682,6 +682,17 @@ public:
     // NCC matches with a second place in the gate that scores nearly as well are dropped: kept when distance < rival distance * coef,
     // 0 < coef <= 1, 0 = off (ekf_set_ncc_distinct); at any time, it takes effect with the next step.  A setter for the same reason.
     void setNccDistinct(double coef) { chk(ekf_set_ncc_distinct(e_, coef), "ekf_set_ncc_distinct"); }
+    // Filter consistency (ekf_set_consistency): every covariance update records its NIS and per-match innovations on the device;
+    // at any time, it takes effect with the next step.  output.yml and log.txt do not change.
+    void setConsistency(bool on) { chk(ekf_set_consistency(e_, on ? 1 : 0), "ekf_set_consistency"); }
+    // the updates of the last step (0 to 2 records: stage 1 = its low-innovation update, 2 = its high-innovation update)
+    void consistency(std::vector<EkfUpdateConsistency> &out)
+    {
+        int n = 0;
+        out.resize(2);
+        chk(ekf_get_consistency(e_, out.data(), (int)out.size(), &n), "ekf_get_consistency");
+        out.resize((size_t)n);
+    }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path, patchNormals_); }

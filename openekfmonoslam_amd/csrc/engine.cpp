@@ -4,6 +4,7 @@
 #include "../../include/ekf_test_hooks.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <algorithm>
 #include <atomic>
@@ -137,7 +138,7 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival, d.cons_ctl, d.cons_recs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -1380,6 +1381,7 @@ static int recover_failed_update(EkfEngine *e, int *status)
         e->ps_backoff = e->ps_backoff_len;
         e->ps_ok_streak = 0;
         ++e->force_launches;
+        e->cons_stage = e->last_update_stage; // (filter consistency: the retry records the stage of the update it repeats)
         int rc = update_dev(e, e->last_update_M, e->last_update_cov, false);
         --e->force_launches;
         ++e->sweep_retries;
@@ -1418,6 +1420,8 @@ int ekf_update(EkfEngine *e, const EkfMatch *matches, int M)
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     if ((rc = complete_hp_table(e))) return rc;
+    if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
+    e->cons_stage = 0;
     rc = update_dev(e, M, true);
     if (rc) return rc;
     return finish_update(e);
@@ -1564,6 +1568,7 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     }
     bool restarted = false;
 restart:
+    if (e->consistency) ++e->cons_epoch; // filter consistency: the records of this step
     StageTimer tm(e);
     tm.mark();
     // 1-2. prediction (:273-284), timesPredicted++ (EKF.cpp:572)
@@ -1629,6 +1634,7 @@ restart:
     li.n_outliers = no;
     tm.mark();
     // 7. low-innovation update (:430)
+    e->cons_stage = 1;
     if ((rc = update_dev(e, ni, true, lean))) return rc;
     tm.mark();
     // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
@@ -1667,6 +1673,7 @@ restart:
     if (normals && nr > 0)
         HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     // 10. high-innovation update (:529-532)
+    e->cons_stage = 2;
     if ((rc = update_dev(e, nr, true, lean))) return rc;
     tm.mark();
     if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
@@ -2395,6 +2402,103 @@ int ekf_get_ncc_rivals(EkfEngine *e, EkfNccRival *out, int capacity, int *count)
         o.rivalDistance = rec[k].d2;
         out[k] = o;
     }
+    return EKF_OK;
+}
+
+// ---------------------------------------------------------------------------------- filter consistency
+int ekf_set_consistency(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) {
+        e->err = "filter consistency: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (on && !e->d.cons_ctl) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        hipError_t st = dalloc(&e->d.cons_recs, (size_t)CONS_SLOTS * e->cap);
+        if (st == hipSuccess) st = dalloc(&e->d.cons_ctl, 1);
+        if (st != hipSuccess) {
+            e->err = std::string("filter consistency tables: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    if (on && !e->consistency) ++e->cons_epoch; // records of an earlier period with the mode on are not this one's
+    e->consistency = on != 0;
+    return EKF_OK;
+}
+
+// synchronises, reports a pending asynchronous error (whose retry may record) and reads the control block; *n = records of the
+// current epoch
+static int read_consistency(EkfEngine *e, ConsCtl *ctl, int *n, int *pending)
+{
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    *pending = take_pending_error(e);
+    std::memset(ctl, 0, sizeof(*ctl));
+    if (e->d.cons_ctl) HIPCHK(hipMemcpy(ctl, e->d.cons_ctl, sizeof(*ctl), hipMemcpyDeviceToHost));
+    *n = (e->consistency && ctl->epoch == e->cons_epoch) ? std::min(std::max(ctl->count, 0), CONS_SLOTS) : 0;
+    return EKF_OK;
+}
+
+int ekf_get_consistency(EkfEngine *e, EkfUpdateConsistency *out, int capacity, int *count)
+{
+    if (!e || !count || (out && capacity < 0)) return EKF_ERR_INVALID_ARG;
+    *count = 0;
+    ConsCtl ctl;
+    int n = 0, pending = EKF_OK, rc;
+    if ((rc = read_consistency(e, &ctl, &n, &pending))) return rc;
+    *count = n;
+    if (n == 0 || !out) return pending;
+    if (capacity < n) {
+        e->err = "ekf_get_consistency: capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " records";
+        return EKF_ERR_CAPACITY;
+    }
+    for (int k = 0; k < n; ++k) out[k] = ctl.rec[k];
+    return pending;
+}
+
+int ekf_get_innovations(EkfEngine *e, int which, EkfInnovation *out, int capacity, int *count)
+{
+    if (!e || !count || (out && capacity < 0)) return EKF_ERR_INVALID_ARG;
+    *count = 0;
+    ConsCtl ctl;
+    int n = 0, pending = EKF_OK, rc;
+    if ((rc = read_consistency(e, &ctl, &n, &pending))) return rc;
+    if (which < 0 || which >= n) {
+        e->err = "ekf_get_innovations: record " + std::to_string(which) + " of " + std::to_string(n);
+        return EKF_ERR_INVALID_ARG;
+    }
+    const int M = std::min(std::max(ctl.rec[which].matches, 0), e->cap);
+    *count = M;
+    if (M == 0 || !out) return pending;
+    if (capacity < M) {
+        e->err = "ekf_get_innovations: capacity " + std::to_string(capacity) + " < " + std::to_string(M) + " matches";
+        return EKF_ERR_CAPACITY;
+    }
+    HIPCHK(hipMemcpy(out, e->d.cons_recs + (size_t)which * e->cap, (size_t)M * sizeof(EkfInnovation), hipMemcpyDeviceToHost));
+    return pending;
+}
+
+int ekf_get_consistency_totals(EkfEngine *e, double *nis_sum, int64_t *rows_sum, int64_t *updates)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    ConsCtl ctl;
+    int n = 0, pending = EKF_OK, rc;
+    if ((rc = read_consistency(e, &ctl, &n, &pending))) return rc;
+    if (nis_sum) *nis_sum = ctl.nis_sum;
+    if (rows_sum) *rows_sum = ctl.rows_sum;
+    if (updates) *updates = ctl.updates;
+    return pending;
+}
+
+int ekf_reset_consistency_totals(EkfEngine *e)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (!e->d.cons_ctl) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    static_assert(offsetof(ConsCtl, nis_sum) == 8 && offsetof(ConsCtl, rec) == 32, "layout of the totals");
+    HIPCHK(hipMemsetAsync((char *)e->d.cons_ctl + offsetof(ConsCtl, nis_sum), 0, offsetof(ConsCtl, rec) - offsetof(ConsCtl, nis_sum), e->stream));
     return EKF_OK;
 }
 

@@ -78,6 +78,17 @@ enum {
 };
 constexpr int MAX_SHARD_WORLD = 16;
 
+// filter consistency (ekf_set_consistency): the device-resident control block of k_consistency.  A step or an
+// ekf_update begins a new epoch on the host; the first record written under a new epoch takes slot 0.
+constexpr int CONS_SLOTS = 2; // covered updates of one epoch: a step's first (LI) and second (HI) update
+struct ConsCtl {
+    int epoch;                          // epoch of the records below
+    int count;                          // records of that epoch, 0 .. CONS_SLOTS
+    double nis_sum;                     // running totals since the last ekf_reset_consistency_totals, added in stream order
+    long long rows_sum, updates;
+    EkfUpdateConsistency rec[CONS_SLOTS];
+};
+
 // doubles in the device state block
 enum { ST_X = 0, ST_R = 13, ST_F = 32, ST_GQG = 32 + 169, ST_JN = 32 + 338, ST_COUNT = 32 + 338 + 16 };
 
@@ -188,6 +199,8 @@ struct DeviceArrays {
     int *Grow = nullptr;        // row of the H P table behind every gathered row (k_gather without the copy)
     int8_t *Wq = nullptr, *Gq = nullptr; // digit planes of inv(L)' and of G for B = inv(L) G on the int8 MFMA (updates above B_SWEEP_MAX rows)
     int *Wexp = nullptr, *Gexp = nullptr; // their column scales
+    ConsCtl *cons_ctl = nullptr;        // filter consistency (ekf_set_consistency; allocated by its first call)
+    EkfInnovation *cons_recs = nullptr; // CONS_SLOTS x cap records: the matches of record s from s * cap on, update order
     float *Pdiag = nullptr;     // sharded exact configuration: diagonal of P, n floats, completed by an exchange
     int8_t *Bstage = nullptr;   // ... and the digit planes of B in the exchange layout [column][plane][k / 16][16]
 };
@@ -306,6 +319,10 @@ struct EkfEngine {
     double distinct_coef = 0.0;    // ekf_set_ncc_distinct: 0 = off, else an NCC match with a rival peak is kept when d1 < d2 * coef
     int distinct_counts[2] = {0, 0}; // accepted matches with a rival / rejected by the test in the last NCC match
     int rival_slots = 0;           // prediction slots of the last NCC match that ran with the test on (records of d.mt_rival)
+    bool consistency = false;      // ekf_set_consistency: every covariance update is followed by k_consistency
+    int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
+    int cons_stage = 0;            // stage the next covered update records: 0 ekf_update, 1 a step's first update, 2 its second
+    int last_update_stage = 0;     // ... and that of the last update enqueued (its retry records the same stage)
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -452,6 +469,9 @@ void launch_compact_P(EkfEngine *e, int n_new, const int *d_new2old);
 void launch_linearity(EkfEngine *e, double *d_out);
 void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3);
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
+// filter consistency (kernels_consistency.hip): NIS and the per-match innovations of the update whose sweep was just enqueued, from
+// d.zvec, the M matches in d.matches and the prediction tables -> d.cons_ctl / d.cons_recs; does nothing when the error flag is set
+void launch_consistency(EkfEngine *e, int M);
 void launch_ncc_pyramid(EkfEngine *e, const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3], const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);

@@ -1676,6 +1676,7 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
     e->last_update_cov = update_cov;
     e->last_update_sym = e->p_exact_sym;
     e->last_update_persist = persist;
+    e->last_update_stage = e->cons_stage;
     double *V = e->d.Dinv, *W = b_in_sweep ? nullptr : e->d.W; // W = inv(L)' (and L row-major in LL): the GEMM path's
     float *Wf = sizeof(TB) == 4 && !b_in_sweep ? e->d.Wf : nullptr;
     bool merged_ga = false;
@@ -1926,6 +1927,8 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
             k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
                                                            e->N, e->d.dx_part, ld, update_cov ? 1 : 0, frz);
     }
+    // filter consistency: z is final in d.zvec and the error flag tells whether this sweep failed
+    if (e->consistency && update_cov) launch_consistency(e, M);
     if (!update_cov) return;
     const bool fix_diag = sizeof(T) == 4 && !EXACT;
     if (EXACT) launch_p_update_exact(e, m, false, true, planes_b || shard_cols || gemm_planes); // (column scales: k_gather + k_dx_partial, or a-priori; planes: the sweep's / the GEMM's / the ranks')

@@ -96,6 +96,28 @@ NCC_RIVAL_DTYPE = np.dtype(
 )
 assert NCC_RIVAL_DTYPE.itemsize == 24
 
+
+
+class EkfUpdateConsistency(C.Structure):
+    """One covariance update with the consistency mode on (ekf_get_consistency); 24 bytes."""
+
+    _fields_ = [("stage", C.c_int32), ("matches", C.c_int32), ("rows", C.c_int32), ("_pad", C.c_int32), ("nis", C.c_double)]
+
+
+class EkfInnovation(C.Structure):
+    """One match of such an update (ekf_get_innovations); 48 bytes, no padding."""
+
+    _fields_ = [("featureIndex", C.c_int32), ("stage", C.c_int32), ("nu", C.c_double * 2), ("d2_marginal", C.c_double),
+                ("nis_conditional", C.c_double), ("_reserved", C.c_double)]
+
+
+# numpy views of the two: stage 0 = ekf_update, 1 = a step's first (LI) update, 2 = its second (HI) update
+CONSISTENCY_DTYPE = np.dtype([("stage", "<i4"), ("matches", "<i4"), ("rows", "<i4"), ("_pad", "<i4"), ("nis", "<f8")])
+INNOVATION_DTYPE = np.dtype([("featureIndex", "<i4"), ("stage", "<i4"), ("nu", "<f8", (2,)), ("d2_marginal", "<f8"),
+                             ("nis_conditional", "<f8"), ("_reserved", "<f8")])
+assert CONSISTENCY_DTYPE.itemsize == C.sizeof(EkfUpdateConsistency) == 24
+assert INNOVATION_DTYPE.itemsize == C.sizeof(EkfInnovation) == 48
+
 DESC_BYTES = 32
 FEATURE_DEPTH = 1
 FEATURE_INVERSE_DEPTH = 2

@@ -11,8 +11,8 @@ import os
 
 import numpy as np
 
-from .ekftypes import (DESC_BYTES, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, NCC_RIVAL_DTYPE, PREDICTION_DTYPE, STATUS_NAMES,
-                       EkfCamera, EkfMapPoint, EkfParams, EkfStepInfo)
+from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, NCC_RIVAL_DTYPE,
+                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
@@ -86,6 +86,11 @@ ABI = {
     "ekf_get_camera_covariance": (_i, [_vp, _vp]),
     "ekf_get_map_points": (_i, [_vp, C.POINTER(EkfMapPoint), _i, C.POINTER(_i)]),
     "ekf_get_unseen_features": (_i, [_vp, _vp, C.POINTER(_i)]),
+    "ekf_set_consistency": (_i, [_vp, _i]),
+    "ekf_get_consistency": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "ekf_get_innovations": (_i, [_vp, _i, _vp, _i, C.POINTER(_i)]),
+    "ekf_get_consistency_totals": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ekf_reset_consistency_totals": (_i, [_vp]),
     "ekf_state_dim": (_i, [_vp]),
     "ekf_descriptor_bytes": (_i, [_vp]),
     "ekf_num_features": (_i, [_vp]),
@@ -343,6 +348,34 @@ class EkfEngine:
         n = _i(0)
         self._chk(self.L.ekf_get_map_points(self.h, buf, len(buf), C.byref(n)))
         return np.frombuffer(buf, dtype=MAP_POINT_DTYPE)[: n.value]
+
+    # ---- filter consistency
+    def set_consistency(self, on=True):
+        """every covariance update records its NIS and per-match innovations on the device; off (the default): no extra launch"""
+        self._chk(self.L.ekf_set_consistency(self.h, 1 if on else 0))
+
+    def consistency(self):
+        """CONSISTENCY_DTYPE [0..2]: the updates recorded since the last step or update() began (stage, matches, rows, nis)"""
+        out = np.zeros(2, dtype=CONSISTENCY_DTYPE)
+        n = _i(0)
+        self._chk(self.L.ekf_get_consistency(self.h, _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def innovations(self, which):
+        """INNOVATION_DTYPE [matches of record `which`], in the update's order: nu, d2_marginal, nis_conditional"""
+        out = np.zeros(max(self.cap, 1), dtype=INNOVATION_DTYPE)
+        n = _i(0)
+        self._chk(self.L.ekf_get_innovations(self.h, int(which), _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def consistency_totals(self):
+        """(sum of nis, sum of rows, updates) over every update recorded since creation or the last reset"""
+        s, r, u = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.ekf_get_consistency_totals(self.h, C.byref(s), C.byref(r), C.byref(u)))
+        return s.value, r.value, u.value
+
+    def reset_consistency_totals(self):
+        self._chk(self.L.ekf_reset_consistency_totals(self.h))
 
     def unseen_features(self):
         idx = np.zeros(max(self.N, 1), dtype=np.int32)

@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -11,6 +11,9 @@
 // (ImageEKF::setPatchNormals) and map.ply carries them as nx ny nz.
 // --ncc-distinct COEF (likewise): an NCC match with a second place in its gate is kept only if its distance is below COEF times
 // the rival's, 0 < COEF <= 1 (ImageEKF::setNccDistinct).
+// --consistency (likewise): every covariance update records its normalised innovation squared on the device
+// (ImageEKF::setConsistency); after each frame one line frame,stage,matches,rows,nis per update is appended to
+// outdir/consistency.csv, and after the last frame total NIS / total rows is printed (1 for a consistent filter).
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -21,7 +24,7 @@
 
 int main(int argc, const char *argv[])
 {
-    bool warp = false, subpix = false, wide = false, normals = false; // the flags are taken out of the argument list; the positional arguments keep their places
+    bool warp = false, subpix = false, wide = false, normals = false, consistency = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
     for (int i = 1; i < argc; ++i)
         if (std::string(argv[i]) == "--ncc-distinct" && i + 1 < argc) { // the flag and its value
@@ -30,15 +33,16 @@ int main(int argc, const char *argv[])
             argc -= 2;
             --i;
         } else if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search" ||
-            std::string(argv[i]) == "--patch-normals") {
+            std::string(argv[i]) == "--patch-normals" || std::string(argv[i]) == "--consistency") {
             if (std::string(argv[i]) == "--patch-normals") normals = true;
-            (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
+            if (std::string(argv[i]) == "--consistency") consistency = true;
+            else (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc;
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -53,7 +57,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -71,13 +75,17 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search or the distinctiveness test asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test or the consistency records asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
         extendedKalmanFilter.setSubpixelMatches(subpix);
         extendedKalmanFilter.setWideSearch(wide);
         extendedKalmanFilter.setNccDistinct(distinct);
+        extendedKalmanFilter.setConsistency(consistency);
+        std::FILE *csv = 0;
+        if (consistency && !outputPath.empty() && !(csv = std::fopen((outputPath + "consistency.csv").c_str(), "w")))
+            throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
         extendedKalmanFilter.init(image);
         std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
         image = generator.getNextImage();
@@ -113,7 +121,23 @@ int main(int argc, const char *argv[])
                 ekf_get_ncc_distinct_counts(extendedKalmanFilter.engine(), &with_rival, &rejected);
                 std::printf("        matches with a rival in the gate %d, rejected %d\n", with_rival, rejected);
             }
+            if (consistency) {
+                std::vector<EkfUpdateConsistency> recs;
+                extendedKalmanFilter.consistency(recs);
+                for (size_t k = 0; k < recs.size(); ++k) {
+                    std::printf("        update stage %d: matches %d rows %d nis %.6f\n", recs[k].stage, recs[k].matches, recs[k].rows, recs[k].nis);
+                    if (csv) std::fprintf(csv, "%d,%d,%d,%d,%.17g\n", extendedKalmanFilter.steps(), recs[k].stage, recs[k].matches, recs[k].rows, recs[k].nis);
+                }
+            }
             image = generator.getNextImage();
+        }
+        if (consistency) {
+            double nis = 0.0;
+            int64_t rows = 0, updates = 0;
+            ekf_get_consistency_totals(extendedKalmanFilter.engine(), &nis, &rows, &updates);
+            std::printf("consistency: %lld updates, total NIS %.6f / total rows %lld = %.6f\n", (long long)updates, nis, (long long)rows,
+                        rows > 0 ? nis / (double)rows : 0.0);
+            if (csv && std::fclose(csv) != 0) throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
         }
         if (!outputPath.empty()) extendedKalmanFilter.writeMapPly(outputPath + "map.ply");
     } catch (const std::exception &ex) {

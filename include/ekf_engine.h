@@ -182,6 +182,28 @@ int ekf_get_innovations(EkfEngine *e, int which, EkfInnovation *out, int capacit
 int ekf_get_consistency_totals(EkfEngine *e, double *nis_sum, int64_t *rows_sum, int64_t *updates);
 int ekf_reset_consistency_totals(EkfEngine *e);
 
+/* Measurement budget (opt-in; K = 0, the default, is off: no extra launch, allocation or read-back, every result bit for bit).
+ * With 0 < K < number of map features, the full prediction of ekf_step, ekf_step_frame, ekf_step_image and
+ * ekf_step_staged_image (both image matchers) ranks the features it sees by the information their measurement carries,
+ * 0.5 ln(det S_i / det R) -- with R = pixelErrorX I the ranking of det S_i, formed in fp64 from 13 x 13 entries of P per
+ * feature -- and hands the K best on, in feature order: only they get H P rows, are searched for, enter RANSAC, the updates,
+ * the rescue and the consistency records, and only their timesPredicted / timesMatched move (removeBadMapFeatures' ratio is
+ * then over the frames a feature was searched in).  EkfStepInfo.n_predicted = min(predicted, K).  What describes the whole
+ * prediction is unchanged: ekf_get_unseen_features (a visible, unselected feature is not unseen), ekf_get_step_predictions
+ * and the gates behind ekf_detect_new_features and the keypoint detector cover every predicted feature.  With K >= number
+ * of map features the budget cannot bind and the step is today's.  An active budget puts ekf_step on the path that reads the
+ * counts back after each stage (as ekf_keep_step_predictions does).  ekf_predict_measurements and the other stage calls
+ * ignore the budget.  Allocates 48 bytes x max_features on the first call with K > 0.  K < 0, or K > 0 on a sharded engine:
+ * EKF_ERR_INVALID_ARG, nothing changes.  DESIGN.md 4.12. */
+int ekf_set_measurement_budget(EkfEngine *e, int K);
+/* one record per feature predicted by the last step, in feature order, if the budget was active in it; *count = 0 otherwise.
+ * The records stay on the device until asked for.  Synchronises the stream and reports a pending asynchronous error as
+ * ekf_get_state does.  out may be NULL (count only); capacity < *count -> EKF_ERR_CAPACITY with *count = number needed. */
+int ekf_get_measurement_ranks(EkfEngine *e, EkfMeasurementRank *out, int capacity, int *count);
+/* the last step's full prediction: features predicted and features handed on (equal when the budget did not bind); either
+ * pointer may be NULL */
+int ekf_get_measurement_budget_counts(const EkfEngine *e, int *predicted, int *selected);
+
 /* -- stages ---------------------------------------------------------------------------------------------- */
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);

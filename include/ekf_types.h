@@ -127,6 +127,17 @@ typedef struct EkfInnovation {
     double _reserved;
 } EkfInnovation; /* 48 bytes, no padding */
 
+/* Measurement budget (ekf_set_measurement_budget): one record per feature the step's full prediction saw.  No counterpart in
+ * the reference.  S_i = H_i P H_i' + pixelErrorX I is the feature's 2x2 innovation covariance, r = pixelErrorX. */
+typedef struct EkfMeasurementRank {
+    int32_t featureIndex;
+    int32_t rank;     /* 0 = most informative; ties go to the lower feature index                                      */
+    int32_t selected; /* 1: handed on to the H P pass, the matcher and the updates; 0: left for a later frame            */
+    int32_t _pad;
+    double key;       /* det(S_i); -1 when it is NaN or not positive (such a feature ranks last)                        */
+    double gain;      /* 0.5 * log(key / (r * r)): the information the measurement carries, in nats; 0 when key = -1    */
+} EkfMeasurementRank; /* 32 bytes, no padding */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

@@ -560,7 +560,7 @@ public:
     ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
-          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false)
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -608,6 +608,11 @@ public:
         if (out_.isOpened()) ekf_timing_reset(e_);
         chk(ekf_step_image(e_, image.data.data(), image.width, image.height, image.width * image.channels, image.channels, &info), "ekf_step_image");
         if (!outputPath_.empty()) writePredictionImage(image); // EKF.cpp:294-305
+        if (budget_ > 0 && log_.is_open()) { // measurement budget: what the step's full prediction saw and what it handed on
+            int predicted = 0, selected = 0;
+            chk(ekf_get_measurement_budget_counts(e_, &predicted, &selected), "ekf_get_measurement_budget_counts");
+            log_ << "Measurement budget: predicted " << predicted << " selected " << selected << std::endl;
+        }
         const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         const int inliers = info.n_inliers + info.n_rescued;
         // EKF.cpp:574-612 (updateMapFeatures already ran inside the step)
@@ -692,6 +697,22 @@ public:
         out.resize(2);
         chk(ekf_get_consistency(e_, out.data(), (int)out.size(), &n), "ekf_get_consistency");
         out.resize((size_t)n);
+    }
+    // Measurement budget (ekf_set_measurement_budget): a step measures at most the K most informative of the features it predicts,
+    // 0 = off; at any time, it takes effect with the next step.  With K > 0 log.txt gains one line per step, "Measurement budget:
+    // predicted P selected S"; output.yml does not change.
+    void setMeasurementBudget(int K)
+    {
+        chk(ekf_set_measurement_budget(e_, K), "ekf_set_measurement_budget");
+        budget_ = K;
+    }
+    // one record per feature the last step predicted, in feature order, if the budget was active in it (else empty)
+    void measurementRanks(std::vector<EkfMeasurementRank> &out)
+    {
+        int n = 0;
+        chk(ekf_get_measurement_ranks(e_, 0, 0, &n), "ekf_get_measurement_ranks");
+        out.resize((size_t)n);
+        if (n > 0) chk(ekf_get_measurement_ranks(e_, out.data(), n, &n), "ekf_get_measurement_ranks");
     }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
@@ -797,6 +818,7 @@ private:
     double detectorThreshold_;
     bool keypoints_; // EKF_IMAGE_MATCHER_KEYPOINTS: new features keep a BRIEF-32 descriptor, no templates
     bool patchNormals_; // setPatchNormals(true): writeMapPly adds the normals
+    int budget_;        // setMeasurementBudget(K)
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

@@ -138,7 +138,8 @@ void ekf_engine_destroy(EkfEngine *e)
                     d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
                     d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
                     e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival, d.cons_ctl, d.cons_recs};
+                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival, d.cons_ctl, d.cons_recs,
+                    d.bud_key, d.bud_all, d.bud_flag, d.bud_recs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &kv : e->pu_tables)
@@ -652,6 +653,7 @@ int ekf_set_state(EkfEngine *e, const double x13[13], int n_features, const doub
     HIPCHK(hipMemset(e->d.pred_vis, 0, (size_t)e->cap * sizeof(int)));
     HIPCHK(hipMemset(e->d.pred_vis_full, 0, (size_t)e->cap * sizeof(int)));
     e->n_step_preds = 0;
+    e->bud_recs_n = e->bud_predicted = e->bud_selected = 0; // measurement budget: the records belong to the map they were made on
     HIPCHK(hipMemset(e->d.feat_times_predicted, 0, (size_t)e->cap * sizeof(unsigned)));
     HIPCHK(hipMemset(e->d.feat_times_matched, 0, (size_t)e->cap * sizeof(unsigned)));
     if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * WPOSE_DOUBLES * sizeof(double))); // template warp: no feature has a source patch
@@ -1072,15 +1074,35 @@ static int complete_hp_table(EkfEngine *e)
 // gates and matches all predictions).  The H.P rows stay with their owners until somebody consumes them: the rows of a
 // RANSAC batch's hypotheses (ransac_dev) and the rows of the matches an update selects (lean_gather_exchange) -- 2M of
 // the 2N rows, and for the outlier re-prediction nothing but the S_i (missing 2a / EKF.cpp:473).
+// budget > 0 (a step's full prediction with the measurement budget active): the predicted features are scored and
+// ranked before the H P pass and the `budget` most informative go on; what describes the whole prediction -- the kept step
+// predictions and the gate snapshot -- is taken from all of them first, with the S_i the selector formed.
 static int predict_measurements_dev(EkfEngine *e, const int *d_idx, int count, int *n_out, bool count_predicted = false,
-                                    bool lean = false)
+                                    bool lean = false, int budget = 0)
 {
     launch_predict_features(e, d_idx, d_idx ? count : e->N, false);
     const bool slots = lean && !d_idx && e->shard_world > 1; // sharded step: where each rank's run of the predicted list starts (matching by owner)
     if (slots) launch_shard_bounds_idx(e, e->d.plist, e->d.counts + CNT_NPRED);
     int rc = read_counts(e);
     if (rc) return rc;
-    const int np = e->h_counts[d_idx ? CNT_NPRED_SUB : CNT_NPRED];
+    int np = e->h_counts[d_idx ? CNT_NPRED_SUB : CNT_NPRED];
+    const bool budgeted = budget > 0 && !d_idx;
+    if (budgeted) {
+        const int np_all = np;
+        launch_budget_select(e, np_all, budget);
+        if (e->keep_step_preds) {
+            launch_pack_predictions(e, e->d.plist, np_all, e->d.step_preds);
+            e->n_step_preds = np_all;
+        }
+        if (e->img.valid) {
+            launch_gate_snapshot(e, np_all);
+            e->n_gates = np_all;
+        }
+        if (np_all > 0) launch_compact(e, e->d.bud_flag, e->d.bud_all, np_all, e->d.plist, e->d.counts + CNT_NPRED);
+        np = std::min(np_all, budget);
+        e->bud_recs_n = e->bud_predicted = np_all;
+        e->bud_selected = np;
+    }
     if (slots) {
         e->slot_rb.assign(e->shard_world + 1, 0);
         for (int r = 0; r <= e->shard_world; ++r) e->slot_rb[r] = e->h_counts[CNT_SHARD0 + r];
@@ -1096,11 +1118,11 @@ static int predict_measurements_dev(EkfEngine *e, const int *d_idx, int count, i
         for (int r = 0; r <= e->shard_world; ++r) rb[r] = e->shard_feat_begin[r];
         if ((rc = exchange_rows(e, EKF_XCHG_PRED_S, e->d.pred_S, 4 * sizeof(double), rb, "the innovation covariance blocks"))) return rc;
     }
-    if (!d_idx && e->keep_step_preds) { // EKF.cpp:294-305 draws the step's predictions as they were BEFORE the updates
+    if (!d_idx && !budgeted && e->keep_step_preds) { // EKF.cpp:294-305 draws the step's predictions as they were BEFORE the updates
         launch_pack_predictions(e, e->d.plist, np, e->d.step_preds);
         e->n_step_preds = np;
     }
-    if (!d_idx && e->img.valid) { // image mode: keep the gates of this prediction for detectNewImageFeatures' mask
+    if (!d_idx && !budgeted && e->img.valid) { // image mode: keep the gates of this prediction for detectNewImageFeatures' mask
         launch_gate_snapshot(e, np);
         e->n_gates = np;
     }
@@ -1551,7 +1573,8 @@ static int detect_step_keypoints(EkfEngine *e);
 static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info,
                     bool use_ncc = false, bool detect = false)
 {
-    const bool dev_counts = !use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1;
+    const bool budget_active = e->budget_K > 0 && e->budget_K < e->N; // measurement budget: with K >= N it cannot bind
+    const bool dev_counts = !use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1 && !budget_active;
     const bool lean = e->shard_world > 1; // sharded: rows of H.P travel when consumed, not after every prediction
     int *cnt = e->d.counts;
     EkfStepInfo li;
@@ -1579,7 +1602,7 @@ restart:
         launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred);
     } else {
         launch_predict(e);
-        if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean))) return rc;
+        if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean, budget_active ? e->budget_K : 0))) return rc;
     }
     tm.mark();
     // 4. matching (:337); keypoints from images: detector + descriptor inside the gates of this prediction (Matching.cpp:188-210)
@@ -1617,6 +1640,10 @@ restart:
     }
     li.n_predicted = np;
     li.n_matches = M;
+    if (!budget_active) { // measurement budget counts of a step it did not bind in
+        e->bud_recs_n = 0;
+        e->bud_predicted = e->bud_selected = np;
+    }
     int ni = 0, no = 0;
     if (M > 0) {
         li.n_hypotheses = e->h_counts[CNT_RS_NEXT];
@@ -2499,6 +2526,61 @@ int ekf_reset_consistency_totals(EkfEngine *e)
     HIPCHK(hipSetDevice(e->device));
     static_assert(offsetof(ConsCtl, nis_sum) == 8 && offsetof(ConsCtl, rec) == 32, "layout of the totals");
     HIPCHK(hipMemsetAsync((char *)e->d.cons_ctl + offsetof(ConsCtl, nis_sum), 0, offsetof(ConsCtl, rec) - offsetof(ConsCtl, nis_sum), e->stream));
+    return EKF_OK;
+}
+
+// ---------------------------------------------------------------------------------- measurement budget
+int ekf_set_measurement_budget(EkfEngine *e, int K)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (K < 0) {
+        e->err = "measurement budget: K < 0";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (K > 0 && e->shard_world > 1) {
+        e->err = "measurement budget: not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (K > 0 && !e->d.bud_recs) {
+        HIPCHK(hipSetDevice(e->device));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        hipError_t st = dalloc(&e->d.bud_key, e->cap);
+        if (st == hipSuccess) st = dalloc(&e->d.bud_all, e->cap);
+        if (st == hipSuccess) st = dalloc(&e->d.bud_flag, e->cap);
+        if (st == hipSuccess) st = dalloc(&e->d.bud_recs, e->cap);
+        if (st != hipSuccess) {
+            e->err = std::string("measurement budget tables: ") + hipGetErrorString(st);
+            return EKF_ERR_HIP;
+        }
+    }
+    if (K == 0) e->bud_recs_n = 0;
+    e->budget_K = K;
+    return EKF_OK;
+}
+
+int ekf_get_measurement_ranks(EkfEngine *e, EkfMeasurementRank *out, int capacity, int *count)
+{
+    if (!e || !count || (out && capacity < 0)) return EKF_ERR_INVALID_ARG;
+    *count = 0;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int pending = take_pending_error(e);
+    const int n = e->d.bud_recs ? std::min(std::max(e->bud_recs_n, 0), e->cap) : 0;
+    *count = n;
+    if (n == 0 || !out) return pending;
+    if (capacity < n) {
+        e->err = "ekf_get_measurement_ranks: capacity " + std::to_string(capacity) + " < " + std::to_string(n) + " records";
+        return EKF_ERR_CAPACITY;
+    }
+    HIPCHK(hipMemcpy(out, e->d.bud_recs, (size_t)n * sizeof(EkfMeasurementRank), hipMemcpyDeviceToHost));
+    return pending;
+}
+
+int ekf_get_measurement_budget_counts(const EkfEngine *e, int *predicted, int *selected)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (predicted) *predicted = e->bud_predicted;
+    if (selected) *selected = e->bud_selected;
     return EKF_OK;
 }
 

@@ -201,6 +201,12 @@ struct DeviceArrays {
     int *Wexp = nullptr, *Gexp = nullptr; // their column scales
     ConsCtl *cons_ctl = nullptr;        // filter consistency (ekf_set_consistency; allocated by its first call)
     EkfInnovation *cons_recs = nullptr; // CONS_SLOTS x cap records: the matches of record s from s * cap on, update order
+    // measurement budget (ekf_set_measurement_budget; allocated by its first call with K > 0): per slot of the full
+    // predicted list
+    double *bud_key = nullptr;             // det(S_i - I + pixelErrorX I), -1 when not positive
+    int *bud_all = nullptr;                // the list before the selection (the compaction writes d.plist from it)
+    int *bud_flag = nullptr;               // selected?
+    EkfMeasurementRank *bud_recs = nullptr; // ekf_get_measurement_ranks
     float *Pdiag = nullptr;     // sharded exact configuration: diagonal of P, n floats, completed by an exchange
     int8_t *Bstage = nullptr;   // ... and the digit planes of B in the exchange layout [column][plane][k / 16][16]
 };
@@ -323,6 +329,9 @@ struct EkfEngine {
     int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
     int cons_stage = 0;            // stage the next covered update records: 0 ekf_update, 1 a step's first update, 2 its second
     int last_update_stage = 0;     // ... and that of the last update enqueued (its retry records the same stage)
+    int budget_K = 0;              // ekf_set_measurement_budget: 0 = off, else a step measures at most this many features
+    int bud_recs_n = 0;            // records in d.bud_recs: predicted features of the last step if the budget was active in it, else 0
+    int bud_predicted = 0, bud_selected = 0; // the last step's full prediction: features predicted / handed on (equal when the budget did not bind)
     double kp_min_response = 0.0;              // ... and the keypoint detector's threshold there
     int step_kp_detected = 0, step_kp_kept = 0; // keypoints of the last KEYPOINTS-mode image step
     size_t rowmask_cap = 0;   // words of d.kp_rowmask
@@ -472,6 +481,10 @@ void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, m
 // filter consistency (kernels_consistency.hip): NIS and the per-match innovations of the update whose sweep was just enqueued, from
 // d.zvec, the M matches in d.matches and the prediction tables -> d.cons_ctl / d.cons_recs; does nothing when the error flag is set
 void launch_consistency(EkfEngine *e, int M);
+// measurement budget (kernels_budget.hip): S_i of the np features in d.plist -> d.pred_S, their keys, ranks, records and selected flags
+// (rank < K, or all when np <= K) -> d.bud_*; launch_compact (k_compact) then turns flags into a list
+void launch_budget_select(EkfEngine *e, int np, int K);
+void launch_compact(EkfEngine *e, const int *flag, const int *idx, int count, int *list, int *out_count);
 void launch_ncc_pyramid(EkfEngine *e, const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_pyramid_on(EkfEngine *e, hipStream_t stream, uint8_t *const px[3], const uint8_t *d_raw, int stride, int channels);
 void launch_ncc_capture(EkfEngine *e, const int *d_idx, const double *d_uv, int count);

@@ -299,6 +299,11 @@ __global__ void __launch_bounds__(1024) k_compact(const int *flag, const int *id
     if (tid == 1023) *out_count = total;
 }
 
+void launch_compact(EkfEngine *e, const int *flag, const int *idx, int count, int *list, int *out_count)
+{
+    k_compact<<<1, 1024, 0, e->stream>>>(flag, idx, count, list, out_count);
+}
+
 // state_only: pixel predictions into the scratch tables (vis2/uv2, list plist_sub, counter CNT_NPRED_SUB) so the
 // tables the following stages consume stay untouched.
 // defer_compact (the step's full prediction, more than 256 features): the compaction is left to the launch of k_hp_rows that follows

@@ -118,6 +118,19 @@ INNOVATION_DTYPE = np.dtype([("featureIndex", "<i4"), ("stage", "<i4"), ("nu", "
 assert CONSISTENCY_DTYPE.itemsize == C.sizeof(EkfUpdateConsistency) == 24
 assert INNOVATION_DTYPE.itemsize == C.sizeof(EkfInnovation) == 48
 
+
+class EkfMeasurementRank(C.Structure):
+    """One predicted feature of a step with the measurement budget active (ekf_get_measurement_ranks); 32 bytes, no padding."""
+
+    _fields_ = [("featureIndex", C.c_int32), ("rank", C.c_int32), ("selected", C.c_int32), ("_pad", C.c_int32), ("key", C.c_double),
+                ("gain", C.c_double)]
+
+
+# rank 0 = most informative; key = det(S_i), -1 when not positive; gain = 0.5 log(key / pixelErrorX^2), 0 when key = -1
+MEASUREMENT_RANK_DTYPE = np.dtype([("featureIndex", "<i4"), ("rank", "<i4"), ("selected", "<i4"), ("_pad", "<i4"), ("key", "<f8"),
+                                   ("gain", "<f8")])
+assert MEASUREMENT_RANK_DTYPE.itemsize == C.sizeof(EkfMeasurementRank) == 32
+
 DESC_BYTES = 32
 FEATURE_DEPTH = 1
 FEATURE_INVERSE_DEPTH = 2

@@ -11,7 +11,8 @@ import os
 
 import numpy as np
 
-from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE, NCC_RIVAL_DTYPE,
+from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
+                       MEASUREMENT_RANK_DTYPE, NCC_RIVAL_DTYPE,
                        PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +92,9 @@ ABI = {
     "ekf_get_innovations": (_i, [_vp, _i, _vp, _i, C.POINTER(_i)]),
     "ekf_get_consistency_totals": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "ekf_reset_consistency_totals": (_i, [_vp]),
+    "ekf_set_measurement_budget": (_i, [_vp, _i]),
+    "ekf_get_measurement_ranks": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "ekf_get_measurement_budget_counts": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_state_dim": (_i, [_vp]),
     "ekf_descriptor_bytes": (_i, [_vp]),
     "ekf_num_features": (_i, [_vp]),
@@ -376,6 +380,25 @@ class EkfEngine:
 
     def reset_consistency_totals(self):
         self._chk(self.L.ekf_reset_consistency_totals(self.h))
+
+    # ---- measurement budget
+    def set_measurement_budget(self, K):
+        """a step measures at most the K most informative of the features it predicts (largest det S_i); 0 (the default): off"""
+        self._chk(self.L.ekf_set_measurement_budget(self.h, int(K)))
+
+    def measurement_ranks(self):
+        """MEASUREMENT_RANK_DTYPE [features the last step predicted], in feature order, if the budget was active in it; else empty"""
+        n = _i(0)
+        self._chk(self.L.ekf_get_measurement_ranks(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=MEASUREMENT_RANK_DTYPE)
+        self._chk(self.L.ekf_get_measurement_ranks(self.h, _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def measurement_budget_counts(self):
+        """(predicted, selected) of the last step's full prediction; equal when the budget did not bind"""
+        a, b = _i(0), _i(0)
+        self._chk(self.L.ekf_get_measurement_budget_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def unseen_features(self):
         idx = np.zeros(max(self.N, 1), dtype=np.int32)

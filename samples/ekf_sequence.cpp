@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -14,6 +14,8 @@
 // --consistency (likewise): every covariance update records its normalised innovation squared on the device
 // (ImageEKF::setConsistency); after each frame one line frame,stage,matches,rows,nis per update is appended to
 // outdir/consistency.csv, and after the last frame total NIS / total rows is printed (1 for a consistent filter).
+// --budget K (likewise): a step measures at most the K most informative of the features it predicts (ImageEKF::setMeasurementBudget);
+// after each frame the predicted and the selected count are printed and appended to outdir/log.txt.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -26,9 +28,11 @@ int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
+    int budget = 0;
     for (int i = 1; i < argc; ++i)
-        if (std::string(argv[i]) == "--ncc-distinct" && i + 1 < argc) { // the flag and its value
-            distinct = std::atof(argv[i + 1]);
+        if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget") && i + 1 < argc) { // the flag and its value
+            if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
+            else distinct = std::atof(argv[i + 1]);
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
             argc -= 2;
             --i;
@@ -42,7 +46,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -57,7 +61,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -75,7 +79,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test or the consistency records asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records or a measurement budget asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -83,6 +87,7 @@ int main(int argc, const char *argv[])
         extendedKalmanFilter.setWideSearch(wide);
         extendedKalmanFilter.setNccDistinct(distinct);
         extendedKalmanFilter.setConsistency(consistency);
+        extendedKalmanFilter.setMeasurementBudget(budget);
         std::FILE *csv = 0;
         if (consistency && !outputPath.empty() && !(csv = std::fopen((outputPath + "consistency.csv").c_str(), "w")))
             throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
@@ -120,6 +125,11 @@ int main(int argc, const char *argv[])
                 int with_rival = 0, rejected = 0;
                 ekf_get_ncc_distinct_counts(extendedKalmanFilter.engine(), &with_rival, &rejected);
                 std::printf("        matches with a rival in the gate %d, rejected %d\n", with_rival, rejected);
+            }
+            if (budget > 0) {
+                int predicted = 0, selected = 0;
+                ekf_get_measurement_budget_counts(extendedKalmanFilter.engine(), &predicted, &selected);
+                std::printf("        measurement budget: predicted %d selected %d\n", predicted, selected);
             }
             if (consistency) {
                 std::vector<EkfUpdateConsistency> recs;

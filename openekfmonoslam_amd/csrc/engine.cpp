@@ -85,13 +85,11 @@ static RcclApi &rccl_api()
     return api;
 }
 
-template <typename T>
-static hipError_t dalloc(T **p, size_t count, bool zero = true)
+// a failed allocation (DeviceBuffers, or a Group's status): the error text and the code of the call
+static int alloc_failed(EkfEngine *e, hipError_t st, const char *what)
 {
-    if (count == 0) count = 1;
-    hipError_t st = hipMalloc((void **)p, count * sizeof(T));
-    if (st == hipSuccess && zero) st = hipMemset(*p, 0, count * sizeof(T));
-    return st;
+    e->err = std::string(what) + ": " + hipGetErrorString(st);
+    return EKF_ERR_HIP;
 }
 
 static int exchange_rows(EkfEngine *e, int what, void *base, size_t row_bytes, const std::vector<int32_t> &rb, const char *name);
@@ -130,20 +128,7 @@ void ekf_engine_destroy(EkfEngine *e)
     e->ps_reg.reset();
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    DeviceArrays &d = e->d;
-    void *ptrs[] = {d.state,     d.feat_pos,  d.feat_type, d.feat_covpos, d.feat_desc, d.feat_times_predicted, d.feat_times_matched, d.P, d.P2, d.mm_scratch, d.mm_index, d.map_points, d.pred_vis, d.pred_vis_full, d.step_preds,
-                    d.pred_uv,   d.pred_vis2, d.pred_uv2,  d.pred_S,      d.Hs,        d.Hf,       d.HP,
-                    d.work_idx,  d.work_flag, d.plist,     d.plist_sub,   d.counts, d.shard_feat,    d.kps,      d.kdesc,
-                    d.mt_valid,  d.mt_kp,     d.mt_dist,   d.matches,     d.msel,      d.mout,     d.match_of_feat,
-                    d.hyp_count, d.hyp_flags, d.best_flags, d.A,          d.S,         d.nu,       d.Dinv,     d.W, d.Wf, d.G, d.LL, d.LLf, d.Tbuf, d.gates, d.cell_resp, d.cell_xy,
-                    d.mHs,       d.mHf,       d.mpos,      d.mdim,        d.dx_part,   d.mask,     d.preds_out, d.sq_part, d.diag_save, d.cam_part, d.cam_save, d.HPc, d.Gc, d.Bc, d.zvec, d.yvec,
-                    e->frames.kps, e->frames.desc, d.mt_xy, d.tmpl, e->img.px[0], e->img.px[1], e->img.px[2], e->img.px2[0], e->img.px2[1], e->img.px2[2], e->img.raw, e->img.seq, d.sweep_ctl, d.pu_ctr, d.Bq, d.Bexp, d.Bz, d.Lq, d.Lexp, d.Grow, d.Pdiag, d.Bstage, d.Wq, d.Gq, d.Wexp, d.Gexp, d.Wz, d.Gz,
-                    d.kp_rowmask, d.det_kps, d.det_desc, d.det_centres, d.wsrc, d.wpose, d.wtmpl, d.wide_list, d.wide_part, d.wnorm, d.pn_list, d.mt_rival, d.cons_ctl, d.cons_recs,
-                    d.bud_key, d.bud_all, d.bud_flag, d.bud_recs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto &kv : e->pu_tables)
-        if (kv.second.first) (void)hipFree(kv.second.first);
+    e->bufs.release_all();
     for (auto &ev : e->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto &pr : e->px_events) (void)hipEventDestroy(pr.first);
@@ -244,8 +229,9 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     DeviceArrays &d = e->d;
     const size_t w = e->f32 ? 4 : 8;
     const size_t cap = e->cap, mcap = e->mcap;
-#define ALLOC(ptr, count)                                                        \
-    if ((st = dalloc(&(ptr), (count))) != hipSuccess) return fail(st, "hipMalloc " #ptr)
+#define ALLOC_AS(name, call) \
+    if ((st = e->bufs.call) != hipSuccess) return fail(st, "hipMalloc " name)
+#define ALLOC(ptr, count) ALLOC_AS(#ptr, alloc(&(ptr), (count)))
     ALLOC(d.state, ST_COUNT);
     ALLOC(d.feat_pos, 6 * cap);
     ALLOC(d.feat_type, cap);
@@ -254,49 +240,44 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     ALLOC(d.feat_times_predicted, cap);
     ALLOC(d.feat_times_matched, cap);
     {
-        uint8_t *raw = nullptr;
         // rows of P kept here: all of them, or (sharded) camera block + the largest share of the features
         e->p_rows_cap = world == 1 ? round_up(e->ncap, LD_ALIGN)
                                    : SHARD_BASE + round_up(6 * ((e->cap + world - 1) / world), LD_ALIGN) + LD_ALIGN;
-        if ((st = dalloc(&raw, (size_t)e->p_rows_cap * e->ldP * w)) != hipSuccess) return fail(st, "hipMalloc P");
-        d.P = raw;
+        ALLOC_AS("P", alloc_bytes(&d.P, (size_t)e->p_rows_cap * e->ldP * w));
         const size_t wb = e->exact ? 8 : w; // element size of H P, its gathered rows and B = inv(L) G
-        if ((st = dalloc(&raw, (size_t)mcap * e->ldP * wb)) != hipSuccess) return fail(st, "hipMalloc HP");
-        d.HP = raw;
+        ALLOC_AS("HP", alloc_bytes(&d.HP, (size_t)mcap * e->ldP * wb));
         // + one row: the row operand of a sharded downdate tile may read up to 127 columns past n
-        if ((st = dalloc(&raw, (size_t)(mcap + 1) * e->ldP * wb)) != hipSuccess) return fail(st, "hipMalloc A");
-        d.A = raw;
+        ALLOC_AS("A", alloc_bytes(&d.A, (size_t)(mcap + 1) * e->ldP * wb));
         if (e->exact) { // digit planes of B and their column scales (kernels_pexact.hip)
             e->bq_rows = round_up((int)mcap, 64) + 64;
-            if ((st = dalloc(&d.Bq, (size_t)PX_S * e->bq_rows * e->ldP)) != hipSuccess) return fail(st, "hipMalloc Bq");
-            if ((st = dalloc(&d.Bexp, (size_t)e->ldP)) != hipSuccess) return fail(st, "hipMalloc Bexp");
+            ALLOC_AS("Bq", alloc(&d.Bq, (size_t)PX_S * e->bq_rows * e->ldP));
+            ALLOC_AS("Bexp", alloc(&d.Bexp, (size_t)e->ldP));
             e->px_scale_shift = 0; // engine.h: measured, and left at 0 -- one bit already costs the 1e-5 component-wise gate in one of five N = 1000 scenes
             if (const char *ev = std::getenv("EKF_PX_SCALE_SHIFT")) e->px_scale_shift = std::max(0, std::min(6, std::atoi(ev)));
             e->bz_stride = e->bq_rows / 16;
-            if ((st = dalloc(&d.Bz, (size_t)(e->ldP / 32 + 8) * e->bz_stride)) != hipSuccess) return fail(st, "hipMalloc Bz");
+            ALLOC_AS("Bz", alloc(&d.Bz, (size_t)(e->ldP / 32 + 8) * e->bz_stride));
             {   // rows of B from digit planes (chol_bplanes.h): planes of L for the sweeps that form B
                 e->lq_nbk = (std::min((int)mcap, B_SWEEP_MAX) + NB - 1) / NB + 2;
-                if ((st = dalloc(&d.Lq, (size_t)PX_S * e->lq_nbk * e->lq_nbk * 1024)) != hipSuccess) return fail(st, "hipMalloc Lq");
-                if ((st = dalloc(&d.Lexp, (size_t)mcap + 256)) != hipSuccess) return fail(st, "hipMalloc Lexp");
-                if ((st = dalloc(&d.Grow, (size_t)mcap + 256)) != hipSuccess) return fail(st, "hipMalloc Grow");
+                ALLOC_AS("Lq", alloc(&d.Lq, (size_t)PX_S * e->lq_nbk * e->lq_nbk * 1024));
+                ALLOC_AS("Lexp", alloc(&d.Lexp, (size_t)mcap + 256));
+                ALLOC_AS("Grow", alloc(&d.Grow, (size_t)mcap + 256));
             }
             if ((int)mcap > B_SWEEP_MAX) { // B = inv(L) G on the int8 MFMA for updates above B_SWEEP_MAX rows: planes of inv(L)' and of G
-                if ((st = dalloc(&d.Wq, (size_t)PX_S * e->bq_rows * (round_up((int)mcap, 128) + 128))) != hipSuccess) return fail(st, "hipMalloc Wq");
-                if ((st = dalloc(&d.Gq, (size_t)PX_S * e->bq_rows * e->ldP)) != hipSuccess) return fail(st, "hipMalloc Gq");
-                if ((st = dalloc(&d.Wexp, (size_t)round_up((int)mcap, 128) + 128)) != hipSuccess) return fail(st, "hipMalloc Wexp");
-                if ((st = dalloc(&d.Gexp, (size_t)e->ldP)) != hipSuccess) return fail(st, "hipMalloc Gexp");
+                ALLOC_AS("Wq", alloc(&d.Wq, (size_t)PX_S * e->bq_rows * (round_up((int)mcap, 128) + 128)));
+                ALLOC_AS("Gq", alloc(&d.Gq, (size_t)PX_S * e->bq_rows * e->ldP));
+                ALLOC_AS("Wexp", alloc(&d.Wexp, (size_t)round_up((int)mcap, 128) + 128));
+                ALLOC_AS("Gexp", alloc(&d.Gexp, (size_t)e->ldP));
                 // their tables of non-zero pieces of plane 0 (k_slice_B writes them, k_b_gemm_i8p reads them)
-                if ((st = dalloc(&d.Wz, (size_t)((round_up((int)mcap, 128) + 128) / 32 + 8) * e->bz_stride)) != hipSuccess) return fail(st, "hipMalloc Wz");
-                if ((st = dalloc(&d.Gz, (size_t)(e->ldP / 32 + 8) * e->bz_stride)) != hipSuccess) return fail(st, "hipMalloc Gz");
+                ALLOC_AS("Wz", alloc(&d.Wz, (size_t)((round_up((int)mcap, 128) + 128) / 32 + 8) * e->bz_stride));
+                ALLOC_AS("Gz", alloc(&d.Gz, (size_t)(e->ldP / 32 + 8) * e->bz_stride));
             }
             if (world > 1) { // sharded: the diagonal table and the exchange image of the planes (rows of B up to B_SWEEP_MAX)
-                if ((st = dalloc(&d.Pdiag, (size_t)e->ldP)) != hipSuccess) return fail(st, "hipMalloc Pdiag");
+                ALLOC_AS("Pdiag", alloc(&d.Pdiag, (size_t)e->ldP));
                 e->bstage_rows = e->bq_rows; // any update's rows of B
-                if ((st = dalloc(&d.Bstage, (size_t)PX_S * e->bstage_rows * e->ldP)) != hipSuccess) return fail(st, "hipMalloc Bstage");
+                ALLOC_AS("Bstage", alloc(&d.Bstage, (size_t)PX_S * e->bstage_rows * e->ldP));
             }
         }
-        if ((st = dalloc(&raw, (size_t)(mcap + 1) * e->ldP * wb)) != hipSuccess) return fail(st, "hipMalloc G");
-        d.G = raw;
+        ALLOC_AS("G", alloc_bytes(&d.G, (size_t)(mcap + 1) * e->ldP * wb));
     }
     ALLOC(d.mm_scratch, (size_t)60 * cap + 4 * (size_t)e->ldP + 64);
     ALLOC(d.mm_index, (size_t)e->ncap + 8);
@@ -343,9 +324,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     ALLOC(d.W, mw * e->ldW);
     ALLOC(d.Tbuf, mw * e->ldW);
     {   // flags of the persistent sweep (chol_persist.h): done / lrdy tables of (B_SWEEP_MAX / 32 + 2)^2 words each, zeroed here once
-        uint8_t *raw = nullptr;
-        if ((st = dalloc(&raw, (size_t)256 + sizeof(unsigned) * 2 * (B_SWEEP_MAX / NB + 2) * (B_SWEEP_MAX / NB + 2))) != hipSuccess) return fail(st, "hipMalloc sweep_ctl");
-        d.sweep_ctl = raw;
+        ALLOC_AS("sweep_ctl", alloc_bytes(&d.sweep_ctl, (size_t)256 + sizeof(unsigned) * 2 * (B_SWEEP_MAX / NB + 2) * (B_SWEEP_MAX / NB + 2)));
     }
     if (e->f32 && !e->exact) ALLOC(d.Wf, mw * e->ldW);
     ALLOC(d.mHs, 14 * cap);
@@ -365,6 +344,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     ALLOC(d.mask, mcap);
     ALLOC(d.preds_out, cap);
 #undef ALLOC
+#undef ALLOC_AS
     for (auto &ev : e->ev)
         if ((st = hipEventCreate(&ev)) != hipSuccess) return fail(st, "hipEventCreate");
     e->h_counts.assign(CNT_COUNT, 0);
@@ -745,11 +725,8 @@ int ekf_get_map_points(EkfEngine *e, EkfMapPoint *points, int capacity, int *cou
         return EKF_ERR_CAPACITY;
     }
     if (!e->d.map_points) {
-        const hipError_t st = dalloc(&e->d.map_points, (size_t)e->cap);
-        if (st != hipSuccess) {
-            e->err = std::string("hipMalloc map_points: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        const hipError_t st = e->bufs.alloc(&e->d.map_points, (size_t)e->cap);
+        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc map_points");
     }
     launch_map_points(e, e->d.map_points);
     HIPCHK(hipGetLastError());
@@ -847,8 +824,8 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     const int n_new = (int)new2old.size();
     if (!e->d.P2) {
         const size_t bytes = (size_t)round_up(e->ncap, LD_ALIGN) * e->ldP * (e->f32 ? 4 : 8);
-        HIPCHK(hipMalloc(&e->d.P2, bytes));
-        HIPCHK(hipMemset(e->d.P2, 0, bytes));
+        const hipError_t st = e->bufs.alloc_bytes(&e->d.P2, bytes); // zeroed, or not kept
+        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc P2");
     }
     HIPCHK(hipMemcpyAsync(e->d.mm_index, new2old.data(), (size_t)n_new * sizeof(int), hipMemcpyHostToDevice, e->stream));
     launch_compact_P(e, n_new, e->d.mm_index);
@@ -1761,22 +1738,28 @@ int ekf_frames_upload(EkfEngine *e, int n_frames, const int32_t *kp_counts, cons
     if (!e || n_frames < 0 || (n_frames > 0 && (!kp_counts || !kps_concat || !desc_concat))) return EKF_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->frames.kps) (void)hipFree(e->frames.kps);
-    if (e->frames.desc) (void)hipFree(e->frames.desc);
-    e->frames = Frames();
+    e->bufs.release(&e->frames.kps);
+    e->bufs.release(&e->frames.desc);
+    e->frames = Frames(); // what every failure below leaves: no frames
+    Frames f;
     size_t total = 0;
     for (int i = 0; i < n_frames; ++i) {
         if (kp_counts[i] < 0) return EKF_ERR_INVALID_ARG;
-        e->frames.offset.push_back((int)total);
-        e->frames.count.push_back(kp_counts[i]);
+        f.offset.push_back((int)total);
+        f.count.push_back(kp_counts[i]);
         total += (size_t)kp_counts[i];
     }
-    e->frames.n = n_frames;
-    if (total == 0) return EKF_OK;
-    HIPCHK(hipMalloc((void **)&e->frames.kps, total * sizeof(EkfKeypoint)));
-    HIPCHK(hipMalloc((void **)&e->frames.desc, total * e->desc_bytes));
-    HIPCHK(hipMemcpy(e->frames.kps, kps_concat, total * sizeof(EkfKeypoint), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->frames.desc, desc_concat, total * e->desc_bytes, hipMemcpyHostToDevice));
+    f.n = n_frames;
+    if (total > 0) {
+        auto g = e->bufs.group();
+        g.alloc(&f.kps, total, false);
+        g.alloc(&f.desc, total * e->desc_bytes, false);
+        if (g.status() != hipSuccess) return alloc_failed(e, g.status(), "hipMalloc frames");
+        HIPCHK(hipMemcpy(f.kps, kps_concat, total * sizeof(EkfKeypoint), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(f.desc, desc_concat, total * e->desc_bytes, hipMemcpyHostToDevice));
+        (void)g.commit();
+    }
+    e->frames = f;
     return EKF_OK;
 }
 
@@ -1795,17 +1778,22 @@ static int ensure_pyramid(EkfEngine *e, int w, int h)
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->stream2) HIPCHK(hipStreamSynchronize(e->stream2));
     e->img.prefetched = -1;
-    int lw = w, lh = h;
+    e->img.valid = false; // until all six levels exist there is no pyramid: no size, no image
     for (int l = 0; l < 3; ++l) {
-        if (e->img.px[l]) (void)hipFree(e->img.px[l]);
-        if (e->img.px2[l]) (void)hipFree(e->img.px2[l]);
-        e->img.px[l] = e->img.px2[l] = nullptr;
-        e->img.w[l] = lw;
-        e->img.h[l] = lh;
-        HIPCHK(hipMalloc((void **)&e->img.px[l], (size_t)std::max(lw, 1) * std::max(lh, 1)));
-        HIPCHK(hipMalloc((void **)&e->img.px2[l], (size_t)std::max(lw, 1) * std::max(lh, 1)));
-        lw /= 2;
-        lh /= 2;
+        e->bufs.release(&e->img.px[l]);
+        e->bufs.release(&e->img.px2[l]);
+        e->img.w[l] = e->img.h[l] = 0;
+    }
+    auto g = e->bufs.group();
+    for (int l = 0; l < 3; ++l) {
+        const size_t bytes = (size_t)std::max(w >> l, 1) * std::max(h >> l, 1);
+        g.alloc(&e->img.px[l], bytes, false);
+        g.alloc(&e->img.px2[l], bytes, false);
+    }
+    if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "hipMalloc image pyramid");
+    for (int l = 0; l < 3; ++l) {
+        e->img.w[l] = w >> l;
+        e->img.h[l] = h >> l;
     }
     return EKF_OK;
 }
@@ -1824,9 +1812,10 @@ int ekf_image_upload(EkfEngine *e, const uint8_t *image, int width, int height, 
     const size_t bytes = (size_t)stride * height;
     if (e->img.raw_cap < bytes) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->img.raw) (void)hipFree(e->img.raw);
-        e->img.raw = nullptr;
-        HIPCHK(hipMalloc((void **)&e->img.raw, bytes));
+        e->bufs.release(&e->img.raw);
+        e->img.raw_cap = 0;
+        const hipError_t st = e->bufs.alloc(&e->img.raw, bytes, false);
+        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc image staging");
         e->img.raw_cap = bytes;
     }
     HIPCHK(hipMemcpyAsync(e->img.raw, image, bytes, hipMemcpyHostToDevice, e->stream));
@@ -1891,12 +1880,13 @@ int ekf_detect_new_features(EkfEngine *e, int max_new, int divide_times, double 
     if (ncell <= 0) return EKF_OK;
     if (e->cells_cap < ncell) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d.cell_resp) (void)hipFree(e->d.cell_resp);
-        if (e->d.cell_xy) (void)hipFree(e->d.cell_xy);
-        e->d.cell_resp = nullptr;
-        e->d.cell_xy = nullptr;
-        HIPCHK(hipMalloc((void **)&e->d.cell_resp, (size_t)ncell * sizeof(long long)));
-        HIPCHK(hipMalloc((void **)&e->d.cell_xy, (size_t)ncell * 2 * sizeof(int)));
+        e->bufs.release(&e->d.cell_resp);
+        e->bufs.release(&e->d.cell_xy);
+        e->cells_cap = 0;
+        auto g = e->bufs.group();
+        g.alloc(&e->d.cell_resp, (size_t)ncell, false);
+        g.alloc(&e->d.cell_xy, (size_t)ncell * 2, false);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "hipMalloc detector cells");
         e->cells_cap = ncell;
     }
     launch_detect_cells(e, e->n_gates, cells_x, cells_y, e->d.cell_resp, e->d.cell_xy);
@@ -1993,23 +1983,23 @@ static int ensure_kp_scratch(EkfEngine *e, int det_cap)
     const size_t words = kp_rowmask_words(e->img.w[0], e->img.h[0]);
     if (e->rowmask_cap < words) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d.kp_rowmask) (void)hipFree(e->d.kp_rowmask);
-        e->d.kp_rowmask = nullptr;
+        e->bufs.release(&e->d.kp_rowmask);
         e->rowmask_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->d.kp_rowmask, words * sizeof(unsigned long long)));
+        const hipError_t st = e->bufs.alloc(&e->d.kp_rowmask, words, false);
+        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc keypoint row mask");
         e->rowmask_cap = words;
     }
     if (e->det_cap < det_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
-        for (void *p : {(void *)e->d.det_kps, (void *)e->d.det_desc, (void *)e->d.det_centres})
-            if (p) (void)hipFree(p);
-        e->d.det_kps = nullptr;
-        e->d.det_desc = nullptr;
-        e->d.det_centres = nullptr;
+        e->bufs.release(&e->d.det_kps);
+        e->bufs.release(&e->d.det_desc);
+        e->bufs.release(&e->d.det_centres);
         e->det_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->d.det_kps, (size_t)det_cap * sizeof(EkfKeypoint)));
-        HIPCHK(hipMalloc((void **)&e->d.det_desc, (size_t)det_cap * EKF_DESC_BYTES));
-        HIPCHK(hipMalloc((void **)&e->d.det_centres, (size_t)det_cap * 2 * sizeof(int)));
+        auto g = e->bufs.group();
+        g.alloc(&e->d.det_kps, (size_t)det_cap, false);
+        g.alloc(&e->d.det_desc, (size_t)det_cap * EKF_DESC_BYTES, false);
+        g.alloc(&e->d.det_centres, (size_t)det_cap * 2, false);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "hipMalloc keypoint staging");
         e->det_cap = det_cap;
     }
     return EKF_OK;
@@ -2131,20 +2121,13 @@ static int ensure_wide_tables(EkfEngine *e, int parts)
     if (e->d.wide_list && tiles <= e->wide_tiles && parts <= e->wide_parts) return EKF_OK;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (void *p : {e->d.wide_list, e->d.wide_part})
-        if (p) (void)hipFree(p);
-    e->d.wide_list = e->d.wide_part = nullptr;
+    e->bufs.release(&e->d.wide_list);
+    e->bufs.release(&e->d.wide_part);
     e->wide_tiles = e->wide_parts = 0;
-    uint8_t *list = nullptr, *part = nullptr;
-    hipError_t st = dalloc(&list, (size_t)e->cap * NCC_WIDE_SLOT_BYTES + NCC_WIDE_TOTALS_BYTES);
-    if (st == hipSuccess) st = dalloc(&part, (size_t)parts * e->cap * (size_t)std::max(tiles, 1) * NCC_WIDE_PARTIAL_BYTES);
-    if (st != hipSuccess) {
-        if (list) (void)hipFree(list);
-        e->err = std::string("wide search tables: ") + hipGetErrorString(st);
-        return EKF_ERR_HIP;
-    }
-    e->d.wide_list = list;
-    e->d.wide_part = part;
+    auto g = e->bufs.group();
+    g.alloc_bytes(&e->d.wide_list, (size_t)e->cap * NCC_WIDE_SLOT_BYTES + NCC_WIDE_TOTALS_BYTES);
+    g.alloc_bytes(&e->d.wide_part, (size_t)parts * e->cap * (size_t)std::max(tiles, 1) * NCC_WIDE_PARTIAL_BYTES);
+    if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "wide search tables");
     e->wide_tiles = tiles;
     e->wide_parts = parts;
     return EKF_OK;
@@ -2188,17 +2171,11 @@ int ekf_set_template_warp(EkfEngine *e, int on)
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
         const size_t cap = (size_t)e->cap;
-        hipError_t st = dalloc(&e->d.wsrc, cap * 3 * WARP_SS);
-        if (st == hipSuccess) st = dalloc(&e->d.wtmpl, cap * 3 * NCC_TT);
-        if (st == hipSuccess) st = dalloc(&e->d.wpose, cap * WPOSE_DOUBLES); // zeroed: no feature has a source patch yet
-        if (st != hipSuccess) {
-            for (void *p : {(void *)e->d.wsrc, (void *)e->d.wtmpl, (void *)e->d.wpose})
-                if (p) (void)hipFree(p);
-            e->d.wsrc = e->d.wtmpl = nullptr;
-            e->d.wpose = nullptr;
-            e->err = std::string("template warp tables: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        auto g = e->bufs.group();
+        g.alloc(&e->d.wsrc, cap * 3 * WARP_SS);
+        g.alloc(&e->d.wtmpl, cap * 3 * NCC_TT);
+        g.alloc(&e->d.wpose, cap * WPOSE_DOUBLES); // zeroed: no feature has a source patch yet
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "template warp tables");
     }
     e->warp_on = on != 0;
     if (!e->warp_on) e->pn_on = false; // the patch normals live in the warp
@@ -2219,14 +2196,10 @@ int ekf_set_patch_normals(EkfEngine *e, int on)
     if (on && !e->d.wnorm) {
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
-        hipError_t st = dalloc(&e->d.wnorm, (size_t)e->cap); // zeroed: no feature has an estimate yet
-        if (st == hipSuccess) st = dalloc(&e->d.pn_list, (size_t)e->cap);
-        if (st != hipSuccess) {
-            if (e->d.wnorm) (void)hipFree(e->d.wnorm);
-            e->d.wnorm = nullptr;
-            e->err = std::string("patch normal tables: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        auto g = e->bufs.group();
+        g.alloc(&e->d.wnorm, (size_t)e->cap); // zeroed: no feature has an estimate yet
+        g.alloc(&e->d.pn_list, (size_t)e->cap);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "patch normal tables");
     }
     e->pn_on = on != 0;
     return EKF_OK;
@@ -2384,11 +2357,8 @@ int ekf_set_ncc_distinct(EkfEngine *e, double coef)
     if (coef > 0.0 && !e->d.mt_rival) {
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
-        const hipError_t st = dalloc(&e->d.mt_rival, (size_t)e->cap);
-        if (st != hipSuccess) {
-            e->err = std::string("NCC distinctiveness table: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        const hipError_t st = e->bufs.alloc(&e->d.mt_rival, (size_t)e->cap);
+        if (st != hipSuccess) return alloc_failed(e, st, "NCC distinctiveness table");
     }
     e->distinct_coef = coef;
     if (coef == 0.0) e->rival_slots = 0; // off: ekf_get_ncc_rivals has nothing to return
@@ -2443,12 +2413,10 @@ int ekf_set_consistency(EkfEngine *e, int on)
     if (on && !e->d.cons_ctl) {
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
-        hipError_t st = dalloc(&e->d.cons_recs, (size_t)CONS_SLOTS * e->cap);
-        if (st == hipSuccess) st = dalloc(&e->d.cons_ctl, 1);
-        if (st != hipSuccess) {
-            e->err = std::string("filter consistency tables: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        auto g = e->bufs.group();
+        g.alloc(&e->d.cons_recs, (size_t)CONS_SLOTS * e->cap);
+        g.alloc(&e->d.cons_ctl, 1);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "filter consistency tables");
     }
     if (on && !e->consistency) ++e->cons_epoch; // records of an earlier period with the mode on are not this one's
     e->consistency = on != 0;
@@ -2544,14 +2512,12 @@ int ekf_set_measurement_budget(EkfEngine *e, int K)
     if (K > 0 && !e->d.bud_recs) {
         HIPCHK(hipSetDevice(e->device));
         HIPCHK(hipStreamSynchronize(e->stream));
-        hipError_t st = dalloc(&e->d.bud_key, e->cap);
-        if (st == hipSuccess) st = dalloc(&e->d.bud_all, e->cap);
-        if (st == hipSuccess) st = dalloc(&e->d.bud_flag, e->cap);
-        if (st == hipSuccess) st = dalloc(&e->d.bud_recs, e->cap);
-        if (st != hipSuccess) {
-            e->err = std::string("measurement budget tables: ") + hipGetErrorString(st);
-            return EKF_ERR_HIP;
-        }
+        auto g = e->bufs.group();
+        g.alloc(&e->d.bud_key, e->cap);
+        g.alloc(&e->d.bud_all, e->cap);
+        g.alloc(&e->d.bud_flag, e->cap);
+        g.alloc(&e->d.bud_recs, e->cap);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "measurement budget tables");
     }
     if (K == 0) e->bud_recs_n = 0;
     e->budget_K = K;
@@ -2626,12 +2592,12 @@ int ekf_images_upload(EkfEngine *e, int n_frames, const uint8_t *images, int wid
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->stream2) HIPCHK(hipStreamSynchronize(e->stream2));
     e->img.prefetched = -1;
-    if (e->img.seq) (void)hipFree(e->img.seq);
-    e->img.seq = nullptr;
+    e->bufs.release(&e->img.seq);
     e->img.seq_n = 0;
     if (n_frames == 0) return EKF_OK;
     const size_t bytes = (size_t)stride * height * n_frames;
-    HIPCHK(hipMalloc((void **)&e->img.seq, bytes));
+    const hipError_t st = e->bufs.alloc(&e->img.seq, bytes, false);
+    if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc image sequence");
     HIPCHK(hipMemcpy(e->img.seq, images, bytes, hipMemcpyHostToDevice));
     e->img.seq_n = n_frames;
     e->img.seq_w = width;

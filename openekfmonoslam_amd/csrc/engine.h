@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ekf_engine.h"
+#include "device_buffers.h"
 #include "device_math.h"
 #include "patch_normal.h"
 
@@ -357,6 +358,8 @@ struct EkfEngine {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;             // image-only work of the next frame, overlapped with the update
     hipEvent_t ev_main = nullptr, ev_prefetch = nullptr;
+    // owner of every device allocation below (d, frames, img, pu_tables): allocate and free through it alone (device_buffers.h)
+    ekf::DeviceBuffers bufs{ekf::DeviceAllocApi{hipMalloc, hipMemset, hipFree}};
     ekf::DeviceArrays d;
     ekf::Frames frames;
     ekf::Image img;

@@ -1728,8 +1728,7 @@ void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bo
     const int4 *tm_d = nullptr;
     if (dual) {
         if (!e->d.pu_ctr) {
-            if (hipMalloc((void **)&e->d.pu_ctr, 16 * sizeof(unsigned)) != hipSuccess || hipMemset(e->d.pu_ctr, 0, 16 * sizeof(unsigned)) != hipSuccess) {
-                e->d.pu_ctr = nullptr;
+            if (e->bufs.alloc(&e->d.pu_ctr, 16) != hipSuccess) {
                 e->err = "exact downdate: unit counters";
                 e->hook_rc = EKF_ERR_HIP;
             }

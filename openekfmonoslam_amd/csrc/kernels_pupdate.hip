@@ -589,13 +589,12 @@ void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order)
         }
         for (size_t k = 0; k < out.size(); ++k) table[(size_t)x * per + k] = out[k];
     }
-    e->d.pu_tilemap = nullptr;
-    if (hipMalloc((void **)&e->d.pu_tilemap, table.size() * sizeof(int4)) != hipSuccess ||
+    e->d.pu_tilemap = nullptr; // (an alias of an entry of pu_tables, which stays the engine's)
+    if (e->bufs.alloc_bytes(&e->d.pu_tilemap, table.size() * sizeof(int4), false) != hipSuccess ||
         hipMemcpyAsync(e->d.pu_tilemap, table.data(), table.size() * sizeof(int4), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
         hipStreamSynchronize(e->stream) != hipSuccess) {
         // no work list: the caller's launch is skipped (grid 0) and the update reports the failure instead of downdating garbage
-        if (e->d.pu_tilemap) (void)hipFree(e->d.pu_tilemap);
-        e->d.pu_tilemap = nullptr;
+        e->bufs.release(&e->d.pu_tilemap);
         e->pu_per_xcd = 0;
         e->pu_tilemap_nt = -1;
         e->err = "work list of the covariance downdate: allocation or upload failed";

@@ -549,6 +549,9 @@ class EkfEngine:
 
     # ---- staged sequences
     def upload_frames(self, frames):
+        if len(frames) == 0:  # drops the staged frames
+            self._chk(self.L.ekf_frames_upload(self.h, 0, None, None, None))
+            return
         counts = np.array([len(k) for k, _ in frames], dtype=np.int32)
         kps = np.ascontiguousarray(np.concatenate([k for k, _ in frames]), dtype=KEYPOINT_DTYPE)
         desc = self._desc(np.concatenate([d for _, d in frames]))

@@ -1,7 +1,7 @@
 /*
- * ekf_test_hooks.h -- fault injection for the test suite.  NOT part of the drop-in boundary (include/ekf_engine.h): nothing a host
- * of the reference would call.  The symbols are exported by libekf_engine.so so that the tests can reach them through the same
- * C ABI as everything else.
+ * ekf_test_hooks.h -- fault injection and read-back of intermediate tables for the test suite.  NOT part of the drop-in boundary
+ * (include/ekf_engine.h): nothing a host of the reference would call.  The symbols are exported by libekf_engine.so so that the
+ * tests can reach them through the same C ABI as everything else.
  */
 #ifndef EKF_TEST_HOOKS_H
 #define EKF_TEST_HOOKS_H
@@ -27,6 +27,14 @@ int ekf_debug_plane0_pieces(EkfEngine *e, int *nonzero, int *total);
  * consulted (they are still written).  The results must be the same bit for bit either way -- which is what the suite checks with
  * two engines on the same frames (tests/test_gpu_exact_edge_cases.py). */
 int ekf_debug_dense_products(EkfEngine *e, int on);
+/* Read-back of the H P row pairs the last measurement prediction left on the device (csrc/kernels_predict.hip, k_hp_rows), for the
+ * stage tests of the prediction (tests/test_gpu_prediction_stages.py).  For each of the `count` listed features: rows 2 fi and
+ * 2 fi + 1 of the table, columns 0 .. n-1, into HP [count x 2 x n], converted to double from the type the table is stored in (fp32
+ * in EKF_PRECISION_F32, fp64 in every other configuration).  HPc (may be null) [count x 2 x 13]: the fp64 copy of the 13 camera
+ * columns that the same kernel writes beside the rows, in every configuration.  Rows of features the prediction did not reach hold
+ * whatever an earlier prediction left there.  Waits for the engine's stream; launches nothing and changes nothing.  Not available
+ * on a sharded engine (EKF_ERR_INVALID_ARG): a rank holds only the rows of the features it owns. */
+int ekf_debug_get_hp_rows(EkfEngine *e, const int32_t *feat_idx, int count, double *HP, double *HPc);
 
 #ifdef __cplusplus
 }

@@ -2727,6 +2727,36 @@ int ekf_debug_plane0_pieces(EkfEngine *e, int *nonzero, int *total)
     return EKF_OK;
 }
 
+int ekf_debug_get_hp_rows(EkfEngine *e, const int32_t *feat_idx, int count, double *HP, double *HPc)
+{
+    if (!e || count < 0 || (count > 0 && (!feat_idx || !HP))) return EKF_ERR_INVALID_ARG;
+    if (e->shard_world > 1) { // a rank holds only the rows of the features it owns
+        e->err = "ekf_debug_get_hp_rows is not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < count; ++k)
+        if (feat_idx[k] < 0 || feat_idx[k] >= e->N) return EKF_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int n = e->n;
+    const size_t w = hp_elem_bytes(e);
+    std::vector<float> tmp(w == 4 ? (size_t)2 * n : 0);
+    for (int k = 0; k < count; ++k) {
+        // rows 2 fi and 2 fi + 1 are adjacent: one strided copy of 2 x n elements
+        const uint8_t *src = (const uint8_t *)e->d.HP + (size_t)2 * feat_idx[k] * e->ldP * w;
+        double *dst = HP + (size_t)2 * n * k;
+        if (w == 4) {
+            HIPCHK(hipMemcpy2D(tmp.data(), (size_t)n * 4, src, (size_t)e->ldP * 4, (size_t)n * 4, 2, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < (size_t)2 * n; ++i) dst[i] = (double)tmp[i];
+        } else {
+            HIPCHK(hipMemcpy2D(dst, (size_t)n * 8, src, (size_t)e->ldP * 8, (size_t)n * 8, 2, hipMemcpyDeviceToHost));
+        }
+        if (HPc && e->d.HPc)
+            HIPCHK(hipMemcpy2D(HPc + (size_t)26 * k, 13 * 8, e->d.HPc + (size_t)2 * feat_idx[k] * 16, 16 * 8, 13 * 8, 2, hipMemcpyDeviceToHost));
+    }
+    return EKF_OK;
+}
+
 int ekf_debug_stall_sweep_after(EkfEngine *e, int skip)
 {
     if (!e || skip < 0) return EKF_ERR_INVALID_ARG;

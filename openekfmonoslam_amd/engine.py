@@ -167,6 +167,7 @@ TEST_HOOKS = {
     "ekf_debug_stall_sweep_after": (_i, [_vp, _i]),
     "ekf_debug_plane0_pieces": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "ekf_debug_dense_products": (_i, [_vp, _i]),
+    "ekf_debug_get_hp_rows": (_i, [_vp, _vp, _i, _vp, _vp]),
 }
 
 # int fn(void *user, int what, void *device_base, size_t row_bytes, const int32_t *row_begin, int world, int rank)
@@ -429,6 +430,15 @@ class EkfEngine:
     def dense_products(self, on=True):
         """test hook: the exact downdate / int8 GEMM multiply every digit product (the zero-piece tables are not consulted)"""
         self._chk(self.L.ekf_debug_dense_products(self.h, 1 if on else 0))
+
+    def hp_rows(self, feat_idx):
+        """test hook: (HP [k, 2, n], HPc [k, 2, 13]) -- the H P row pairs of the listed features as the last measurement prediction
+        left them on the device, and the fp64 copy of their 13 camera columns"""
+        idx = np.ascontiguousarray(feat_idx, dtype=np.int32)
+        HP = np.zeros((max(len(idx), 1), 2, self.n))
+        HPc = np.zeros((max(len(idx), 1), 2, 13))
+        self._chk(self.L.ekf_debug_get_hp_rows(self.h, _p(idx), len(idx), _p(HP), _p(HPc)))
+        return HP[: len(idx)], HPc[: len(idx)]
 
     def set_update_path(self, path):
         """0: by size, 1: B = inv(L) H P inside the Cholesky sweep, 2: explicit inverse + GEMM (ekf_engine.h)"""

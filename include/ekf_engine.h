@@ -204,6 +204,33 @@ int ekf_get_measurement_ranks(EkfEngine *e, EkfMeasurementRank *out, int capacit
  * pointer may be NULL */
 int ekf_get_measurement_budget_counts(const EkfEngine *e, int *predicted, int *selected);
 
+/* External measurements: an EKF update with any linearised measurement, between steps.  H is given by rows in
+ * CSR form over STATE indices -- the indices of P: 0..12 the camera (r, q, v, w), covpos + k parameter k of a feature
+ * (ekf_get_feature_layout) -- with row i holding the entries row_start[i] .. row_start[i + 1] - 1 of col / val, 1 to
+ * EKF_EXT_MAX_NNZ of them, columns strictly ascending; m = 1 .. EKF_EXT_MAX_ROWS rows.  residual = z - h(x) as the caller
+ * linearised it; R is m x m row-major and only its upper triangle is read.  With S = H P H' + R = L L':
+ *     z = inv(L) residual,  nis = z'z,  B = inv(L) H P,  x += B'z (dead-band EKF_DELTA per component, then the quaternion is
+ *     normalised),  P <- 0.5 (P + P') - B'B, then normalizeCovariance as after every update (EKF/Update.cpp:64-85, 303-312)
+ * in fp64 whatever the precision configuration; P is rounded to its storage type once per step and is bitwise symmetric
+ * afterwards.  gate_nis > 0: the update is applied only if nis <= gate_nis (else EKF_OK with out->applied = 0 and nothing
+ * changed); 0: no gate.  S not positive definite: EKF_ERR_NOT_POSITIVE_DEFINITE, nothing changed.  The tables of the last
+ * prediction are left as they are (as after ekf_update: a caller of the stage functions predicts again); no consistency
+ * record is written (the NIS comes back in out, which may be NULL).  Reports a pending asynchronous error first, as
+ * ekf_get_state does, and then does nothing else.  Synchronises the stream.  EKF_ERR_INVALID_ARG, with nothing enqueued: m or
+ * a row's length out of range, columns not strictly ascending or outside the state, a non-finite value, gate_nis < 0 or NaN,
+ * a sharded engine. */
+int ekf_update_external(EkfEngine *e, int m, const int32_t *row_start /* m + 1 */, const int32_t *col, const double *val,
+                        const double *residual /* m */, const double *R /* m x m */, double gate_nis,
+                        EkfExternalUpdate *out /* may be NULL */);
+/* a fix r of the camera position with covariance R (3 x 3 row-major, upper triangle read): H = [I3 0 ...], residual = r - x[0:3] */
+int ekf_fuse_camera_position(EkfEngine *e, const double r[3], const double R[9], double gate_nis, EkfExternalUpdate *out);
+/* a measured distance between two map features (what fixes the monocular scale): h = |X_i - X_j| with X the world point of
+ * ekf_get_map_points, one row u' Jw_i on feature i's columns and -u' Jw_j on feature j's (u = (X_i - X_j) / h, Jw = dX/dy),
+ * residual = distance - h, R = sigma^2.  EKF_ERR_INVALID_ARG: feat_i == feat_j, an index out of range, h = 0, sigma <= 0,
+ * distance <= 0. */
+int ekf_fuse_feature_distance(EkfEngine *e, int feat_i, int feat_j, double distance, double sigma, double gate_nis,
+                              EkfExternalUpdate *out);
+
 /* -- stages ---------------------------------------------------------------------------------------------- */
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);

@@ -138,6 +138,18 @@ typedef struct EkfMeasurementRank {
     double gain;      /* 0.5 * log(key / (r * r)): the information the measurement carries, in nats; 0 when key = -1    */
 } EkfMeasurementRank; /* 32 bytes, no padding */
 
+/* External measurement update (ekf_update_external): any linearised measurement z = h(x) + noise(R), handed in as sparse rows of
+ * its Jacobian H.  No counterpart in the reference, whose only measurement is the camera's. */
+#define EKF_EXT_MAX_ROWS 16 /* measurement rows per call */
+#define EKF_EXT_MAX_NNZ 32  /* non-zero entries per row of H */
+
+typedef struct EkfExternalUpdate {
+    double nis;                 /* z'z, z = inv(L) residual, S = H P H' + R = L L': chi-square with `rows` degrees of freedom */
+    double z[EKF_EXT_MAX_ROWS]; /* the whitened residual; entries >= rows are 0 */
+    int32_t rows;
+    int32_t applied;            /* 1: x and P were updated; 0: the gate rejected it, nothing changed */
+} EkfExternalUpdate;            /* 144 bytes, no padding */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

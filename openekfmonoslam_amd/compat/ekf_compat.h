@@ -843,6 +843,32 @@ public:
         stateCovarianceMatrix.markStale(e_, ekf_state_dim(e_));
         return k;
     }
+    // ---- external measurements between steps (ekf_update_external and its helpers): H by rows in CSR form over
+    // state indices, m <= EKF_EXT_MAX_ROWS rows of <= EKF_EXT_MAX_NNZ entries.  Returns the record (NIS, whitened residual,
+    // applied); throws on an error code, EKF_ERR_NOT_POSITIVE_DEFINITE included.  Resident mode: `state` is current after the
+    // call and `stateCovarianceMatrix` is marked stale exactly as a step marks it (pulled on first access).
+    EkfExternalUpdate updateExternal(int m, const int32_t *rowStart, const int32_t *col, const double *val, const double *residual,
+                                     const double *R, double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        ekf_compat::chk(e_, ekf_update_external(e_, m, rowStart, col, val, residual, R, gateNis, &out), "ekf_update_external");
+        afterExternalUpdate();
+        return out;
+    }
+    EkfExternalUpdate fuseCameraPosition(const double r[3], const double R[9], double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        ekf_compat::chk(e_, ekf_fuse_camera_position(e_, r, R, gateNis, &out), "ekf_fuse_camera_position");
+        afterExternalUpdate();
+        return out;
+    }
+    EkfExternalUpdate fuseFeatureDistance(int featureI, int featureJ, double distance, double sigma, double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        ekf_compat::chk(e_, ekf_fuse_feature_distance(e_, featureI, featureJ, distance, sigma, gateNis, &out), "ekf_fuse_feature_distance");
+        afterExternalUpdate();
+        return out;
+    }
     EkfEngine *engine() { return e_; }
     Matd stateCovarianceMatrix;
     State state;
@@ -850,6 +876,12 @@ public:
 private:
     EKF(const EKF &);
     EKF &operator=(const EKF &);
+    void afterExternalUpdate()
+    {
+        refreshLayout();
+        ekf_compat::download(e_, state, 0);
+        stateCovarianceMatrix.markStale(e_, ekf_state_dim(e_));
+    }
     // rebuild the host-side MapFeature list when the device map changed size or parametrisation
     void refreshLayout()
     {

@@ -714,6 +714,28 @@ public:
         out.resize((size_t)n);
         if (n > 0) chk(ekf_get_measurement_ranks(e_, out.data(), n, &n), "ekf_get_measurement_ranks");
     }
+    // External measurements between steps (ekf_update_external and its helpers): H by rows in CSR form over state
+    // indices; a fix of the camera position; a measured distance between two map features.  They return the record (NIS, whitened
+    // residual, applied) and throw on an error code.  output.yml and log.txt do not change.
+    EkfExternalUpdate updateExternal(int m, const int32_t *rowStart, const int32_t *col, const double *val, const double *residual,
+                                     const double *R, double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        chk(ekf_update_external(e_, m, rowStart, col, val, residual, R, gateNis, &out), "ekf_update_external");
+        return out;
+    }
+    EkfExternalUpdate fuseCameraPosition(const double r[3], const double R[9], double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        chk(ekf_fuse_camera_position(e_, r, R, gateNis, &out), "ekf_fuse_camera_position");
+        return out;
+    }
+    EkfExternalUpdate fuseFeatureDistance(int featureI, int featureJ, double distance, double sigma, double gateNis = 0.0)
+    {
+        EkfExternalUpdate out;
+        chk(ekf_fuse_feature_distance(e_, featureI, featureJ, distance, sigma, gateNis, &out), "ekf_fuse_feature_distance");
+        return out;
+    }
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path, patchNormals_); }

@@ -1440,6 +1440,145 @@ int ekf_update_only_state(EkfEngine *e, const EkfMatch *matches, int M)
     return finish_update(e);
 }
 
+// ------------------------------------------------------------------------- external measurements
+int ekf_update_external(EkfEngine *e, int m, const int32_t *row_start, const int32_t *col, const double *val, const double *residual,
+                        const double *R, double gate_nis, EkfExternalUpdate *out)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    auto invalid = [&](const std::string &why) {
+        e->err = "ekf_update_external: " + why;
+        return EKF_ERR_INVALID_ARG;
+    };
+    if (e->shard_world > 1) return invalid("not available on a sharded engine");
+    if (m < 1 || m > EXT_ROWS) return invalid("m = " + std::to_string(m) + " is outside 1.." + std::to_string(EXT_ROWS));
+    if (!row_start || !col || !val || !residual || !R) return invalid("a null argument");
+    if (!(gate_nis >= 0.0)) return invalid("gate_nis is negative or not a number");
+    ExtCtl ctl;
+    std::memset(&ctl, 0, sizeof(ctl));
+    ctl.m = m;
+    ctl.gate_nis = gate_nis;
+    const int base = row_start[0];
+    if (base < 0) return invalid("row_start[0] < 0");
+    for (int i = 0; i < m; ++i) {
+        const int k0 = row_start[i], k1 = row_start[i + 1];
+        if (k1 <= k0 || k1 - k0 > EXT_NNZ)
+            return invalid("row " + std::to_string(i) + " has " + std::to_string((long long)k1 - k0) + " entries (1.." + std::to_string(EXT_NNZ) + ")");
+        for (int k = k0; k < k1; ++k) {
+            if (col[k] < 0 || col[k] >= e->n || (k > k0 && col[k] <= col[k - 1]))
+                return invalid("row " + std::to_string(i) + ": columns must ascend strictly inside [0, " + std::to_string(e->n) + ")");
+            if (!std::isfinite(val[k])) return invalid("a value of H is not finite");
+            ctl.col[k - base] = col[k];
+            ctl.val[k - base] = val[k];
+        }
+        ctl.row_start[i] = k0 - base;
+        ctl.row_start[i + 1] = k1 - base;
+        if (!std::isfinite(residual[i])) return invalid("a residual is not finite");
+        ctl.residual[i] = residual[i];
+        for (int j = i; j < m; ++j) {
+            if (!std::isfinite(R[(size_t)i * m + j])) return invalid("an entry of R is not finite");
+            ctl.R[i * EXT_ROWS + j] = R[(size_t)i * m + j];
+        }
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc = take_pending_error(e); // as ekf_get_state; the failed update it reports is not this call's
+    if (rc) return rc;
+    if (!e->d.ext_A) {
+        auto g = e->bufs.group();
+        g.alloc(&e->d.ext_A, (size_t)(EXT_ROWS + 1) * e->ldP);
+        g.alloc(&e->d.ext_sel, (size_t)EXT_ROWS * EXT_ENTRIES);
+        g.alloc(&e->d.ext_ctl, 1);
+        g.alloc(&e->d.ext_res, 1);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "external update scratch");
+    }
+    HIPCHK(hipMemcpyAsync(e->d.ext_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, e->stream));
+    launch_external_update(e, m);
+    HIPCHK(hipGetLastError());
+    ExtResult res;
+    HIPCHK(hipMemcpyAsync(&res, e->d.ext_res, sizeof(res), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (out) *out = res.out;
+    if (res.verdict == EXT_NOT_PD) {
+        e->err = "ekf_update_external: S = H P H' + R is not positive definite";
+        return EKF_ERR_NOT_POSITIVE_DEFINITE;
+    }
+    if (res.verdict == EXT_APPLIED) e->p_exact_sym = true; // every pair was averaged and written to both places
+    return EKF_OK;
+}
+
+int ekf_fuse_camera_position(EkfEngine *e, const double r[3], const double R[9], double gate_nis, EkfExternalUpdate *out)
+{
+    if (!e || !r || !R) return EKF_ERR_INVALID_ARG;
+    NOT_WHEN_SHARDED(e)
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    double x[3];
+    HIPCHK(hipMemcpy(x, e->d.state + ST_X, sizeof(x), hipMemcpyDeviceToHost));
+    const int32_t row_start[4] = {0, 1, 2, 3}, col[3] = {0, 1, 2};
+    const double val[3] = {1.0, 1.0, 1.0}, residual[3] = {r[0] - x[0], r[1] - x[1], r[2] - x[2]};
+    return ekf_update_external(e, 3, row_start, col, val, residual, R, gate_nis, out);
+}
+
+// world point X of a feature and Jw = dX/dy (3 x 6 row-major, the identity block for a depth feature), as k_map_points forms them
+static void feature_world_point(const double *y, int type, double *X, double *Jw)
+{
+    for (int i = 0; i < 18; ++i) Jw[i] = 0.0;
+    Jw[0] = Jw[7] = Jw[14] = 1.0;
+    for (int i = 0; i < 3; ++i) X[i] = y[i];
+    if (type != EKF_FEATURE_INVERSE_DEPTH) return;
+    const double theta = y[3], phi = y[4], rho = y[5];
+    double mi[3];
+    dir_vec(theta, phi, mi);
+    Jw[0 * 6 + 3] = std::cos(phi) * std::cos(theta) / rho;  Jw[2 * 6 + 3] = -std::cos(phi) * std::sin(theta) / rho;
+    Jw[0 * 6 + 4] = -std::sin(phi) * std::sin(theta) / rho; Jw[1 * 6 + 4] = -std::cos(phi) / rho;
+    Jw[2 * 6 + 4] = -std::sin(phi) * std::cos(theta) / rho;
+    for (int i = 0; i < 3; ++i) {
+        Jw[i * 6 + 5] = -mi[i] / (rho * rho);
+        X[i] += mi[i] / rho;
+    }
+}
+
+int ekf_fuse_feature_distance(EkfEngine *e, int feat_i, int feat_j, double distance, double sigma, double gate_nis,
+                              EkfExternalUpdate *out)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    NOT_WHEN_SHARDED(e)
+    auto invalid = [&](const char *why) {
+        e->err = std::string("ekf_fuse_feature_distance: ") + why;
+        return EKF_ERR_INVALID_ARG;
+    };
+    if (feat_i < 0 || feat_i >= e->N || feat_j < 0 || feat_j >= e->N || feat_i == feat_j) return invalid("two different map features are needed");
+    if (!(sigma > 0.0) || !(distance > 0.0) || !std::isfinite(sigma) || !std::isfinite(distance)) return invalid("distance and sigma must be positive");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int f[2] = {feat_i, feat_j};
+    double y[2][6], X[2][3], Jw[2][18];
+    for (int s = 0; s < 2; ++s) {
+        HIPCHK(hipMemcpy(y[s], e->d.feat_pos + 6 * (size_t)f[s], sizeof(y[s]), hipMemcpyDeviceToHost));
+        feature_world_point(y[s], e->h_type[f[s]], X[s], Jw[s]);
+    }
+    const double dX[3] = {X[0][0] - X[1][0], X[0][1] - X[1][1], X[0][2] - X[1][2]};
+    const double h = std::sqrt(dX[0] * dX[0] + dX[1] * dX[1] + dX[2] * dX[2]);
+    if (!(h > 0.0) || !std::isfinite(h)) return invalid("the two features coincide");
+    const double u[3] = {dX[0] / h, dX[1] / h, dX[2] / h};
+    int32_t col[12];
+    double val[12];
+    int nnz = 0;
+    const int first = e->h_covpos[feat_i] < e->h_covpos[feat_j] ? 0 : 1; // columns ascend: the feature stored first comes first
+    for (int t = 0; t < 2; ++t) {
+        const int s = t == 0 ? first : 1 - first;
+        const int d = dims_of(e->h_type[f[s]]), pos = e->h_covpos[f[s]];
+        const double sign = s == 0 ? 1.0 : -1.0;
+        for (int k = 0; k < d; ++k) {
+            col[nnz] = pos + k;
+            val[nnz++] = sign * (u[0] * Jw[s][k] + u[1] * Jw[s][6 + k] + u[2] * Jw[s][12 + k]);
+        }
+    }
+    const int32_t row_start[2] = {0, nnz};
+    const double residual = distance - h, R = sigma * sigma;
+    return ekf_update_external(e, 1, row_start, col, val, &residual, &R, gate_nis, out);
+}
+
 int ekf_rescue(EkfEngine *e, const EkfMatch *outliers, int M, uint8_t *rescued_mask)
 {
     if (!e || !rescued_mask) return EKF_ERR_INVALID_ARG;

@@ -93,6 +93,23 @@ struct ConsCtl {
 // doubles in the device state block
 enum { ST_X = 0, ST_R = 13, ST_F = 32, ST_GQG = 32 + 169, ST_JN = 32 + 338, ST_COUNT = 32 + 338 + 16 };
 
+// external measurement update (ekf_update_external): what a call uploads, and the record its solve kernel leaves
+constexpr int EXT_ROWS = EKF_EXT_MAX_ROWS, EXT_NNZ = EKF_EXT_MAX_NNZ, EXT_ENTRIES = EXT_ROWS * EXT_NNZ;
+enum { EXT_APPLIED = 0, EXT_GATED = 1, EXT_NOT_PD = 2 }; // ExtResult::verdict; the kernels behind the solve return unless APPLIED
+struct ExtCtl {
+    double val[EXT_ENTRIES];      // H in CSR form over state indices, rows one behind the other
+    double R[EXT_ROWS * EXT_ROWS]; // leading dimension EXT_ROWS; the upper triangle is read
+    double residual[EXT_ROWS];
+    double gate_nis;              // 0: no gate
+    int col[EXT_ENTRIES];
+    int row_start[EXT_ROWS + 1];
+    int m;
+};
+struct ExtResult {
+    EkfExternalUpdate out;
+    int verdict, pad;
+};
+
 struct DeviceArrays {
     // map + state
     double *state = nullptr;    // ST_COUNT doubles: x13, R, F, GQG, Jnorm
@@ -200,6 +217,11 @@ struct DeviceArrays {
     int *Grow = nullptr;        // row of the H P table behind every gathered row (k_gather without the copy)
     int8_t *Wq = nullptr, *Gq = nullptr; // digit planes of inv(L)' and of G for B = inv(L) G on the int8 MFMA (updates above B_SWEEP_MAX rows)
     int *Wexp = nullptr, *Gexp = nullptr; // their column scales
+    // external measurement update (ekf_update_external; one group, allocated by its first call)
+    double *ext_A = nullptr;      // (EXT_ROWS + 1) x ldP: A = H P, overwritten by B = inv(L) A; the row behind them is dx = B' z
+    double *ext_sel = nullptr;    // EXT_ROWS x EXT_ENTRIES: A[i, col_e] for every entry e of H, what S = A H' + R reads
+    ExtCtl *ext_ctl = nullptr;
+    ExtResult *ext_res = nullptr;
     ConsCtl *cons_ctl = nullptr;        // filter consistency (ekf_set_consistency; allocated by its first call)
     EkfInnovation *cons_recs = nullptr; // CONS_SLOTS x cap records: the matches of record s from s * cap on, update order
     // measurement budget (ekf_set_measurement_budget; allocated by its first call with K > 0): per slot of the full
@@ -412,6 +434,24 @@ void launch_xty(EkfEngine *e, const XtyArgs &a, int batch, bool f32, hipStream_t
 // there, i.e. K = 0 and an unchanged filter, EKF/Update.cpp:101-108).  counts == nullptr: no guard (stage calls that synchronise).
 #ifdef __HIPCC__
 __device__ __forceinline__ bool filter_frozen(const int *counts) { return counts != nullptr && counts[CNT_ERR] != 0; }
+
+// quaternion normalisation and its Jacobian (Update.cpp:45-62, 303-312), one thread: J from the un-normalised q, then q /= |q|
+// and R(q)
+__device__ inline void quat_norm_dev(double *st)
+{
+    double *q = st + ST_X + 3;
+    const double r = q[0], x = q[1], y = q[2], z = q[3];
+    const double nrm = sqrt(r * r + x * x + y * y + z * z);
+    const double a = 1.0 / (nrm * nrm * nrm);
+    double *J = st + ST_JN;
+    const double M[16] = {x * x + y * y + z * z, -r * x, -r * y, -r * z,
+                          -x * r, r * r + y * y + z * z, -x * y, -x * z,
+                          -y * r, -y * x, r * r + x * x + z * z, -y * z,
+                          -z * r, -z * x, -z * y, r * r + x * x + y * y};
+    for (int i = 0; i < 16; ++i) J[i] = M[i] * a;
+    q[0] = r / nrm; q[1] = x / nrm; q[2] = y / nrm; q[3] = z / nrm;
+    quat_to_rot(q, st + ST_R);
+}
 #endif
 
 // Exclusive prefix sum of one int per thread over a 1024-thread workgroup (and the total): inside a wavefront by shuffles,
@@ -481,6 +521,9 @@ void launch_compact_P(EkfEngine *e, int n_new, const int *d_new2old);
 void launch_linearity(EkfEngine *e, double *d_out);
 void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3);
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
+// external measurement update (kernels_external.hip): the call's ExtCtl is in d.ext_ctl; enqueues A = H P, the solve, the state
+// update, the downdate and the normalisation of the covariance, and leaves the record in d.ext_res
+void launch_external_update(EkfEngine *e, int m);
 // filter consistency (kernels_consistency.hip): NIS and the per-match innovations of the update whose sweep was just enqueued, from
 // d.zvec, the M matches in d.matches and the prediction tables -> d.cons_ctl / d.cons_recs; does nothing when the error flag is set
 void launch_consistency(EkfEngine *e, int M);

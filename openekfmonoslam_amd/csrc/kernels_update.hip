@@ -1108,22 +1108,7 @@ k_dx_partial(const T *B, int ld, int m, int n, const double *z, double *part, in
 // and columns get the same treatment: the camera state -- above all the angular velocity, which is observed only
 // through these cross-covariances -- inherits their error (measured: w block 2e-4 -> see DESIGN.md section 6).
 // The old values are saved by k_dx_partial (its k-split 0) before the downdate; k_fix_normalize writes the new ones after it.
-// quaternion normalisation and its Jacobian (Update.cpp:45-62, 303-312), one thread
-__device__ inline void quat_norm_dev(double *st)
-{
-    double *q = st + ST_X + 3;
-    const double r = q[0], x = q[1], y = q[2], z = q[3];
-    const double nrm = sqrt(r * r + x * x + y * y + z * z);
-    const double a = 1.0 / (nrm * nrm * nrm);
-    double *J = st + ST_JN;
-    const double M[16] = {x * x + y * y + z * z, -r * x, -r * y, -r * z,
-                          -x * r, r * r + y * y + z * z, -x * y, -x * z,
-                          -y * r, -y * x, r * r + x * x + z * z, -y * z,
-                          -z * r, -z * x, -z * y, r * r + x * x + y * y};
-    for (int i = 0; i < 16; ++i) J[i] = M[i] * a;
-    q[0] = r / nrm; q[1] = x / nrm; q[2] = y / nrm; q[3] = z / nrm;
-    quat_to_rot(q, st + ST_R);
-}
+// (quat_norm_dev, the quaternion normalisation and its Jacobian: engine.h)
 
 // stateUpdate (Update.cpp:147-204): x += dx with the DELTA dead-band on every component; R(q) recomputed from
 // the un-normalised q (:168).

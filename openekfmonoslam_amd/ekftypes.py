@@ -131,6 +131,17 @@ MEASUREMENT_RANK_DTYPE = np.dtype([("featureIndex", "<i4"), ("rank", "<i4"), ("s
                                    ("gain", "<f8")])
 assert MEASUREMENT_RANK_DTYPE.itemsize == C.sizeof(EkfMeasurementRank) == 32
 
+EXT_MAX_ROWS, EXT_MAX_NNZ = 16, 32  # EKF_EXT_MAX_ROWS / EKF_EXT_MAX_NNZ: rows per external update, entries per row of H
+
+
+class EkfExternalUpdate(C.Structure):
+    """What ekf_update_external reports: the NIS, the whitened residual, its rows and whether the gate let it through; 144 bytes."""
+
+    _fields_ = [("nis", C.c_double), ("z", C.c_double * EXT_MAX_ROWS), ("rows", C.c_int32), ("applied", C.c_int32)]
+
+
+assert C.sizeof(EkfExternalUpdate) == 144
+
 DESC_BYTES = 32
 FEATURE_DEPTH = 1
 FEATURE_INVERSE_DEPTH = 2

@@ -13,7 +13,7 @@ import numpy as np
 
 from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
                        MEASUREMENT_RANK_DTYPE, NCC_RIVAL_DTYPE,
-                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfMapPoint, EkfParams, EkfStepInfo)
+                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
@@ -105,6 +105,9 @@ ABI = {
     "ekf_ransac": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i)]),
     "ekf_update": (_i, [_vp, _vp, _i]),
     "ekf_update_only_state": (_i, [_vp, _vp, _i]),
+    "ekf_update_external": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(EkfExternalUpdate)]),
+    "ekf_fuse_camera_position": (_i, [_vp, _vp, _vp, C.c_double, C.POINTER(EkfExternalUpdate)]),
+    "ekf_fuse_feature_distance": (_i, [_vp, _i, _i, C.c_double, C.c_double, C.c_double, C.POINTER(EkfExternalUpdate)]),
     "ekf_rescue": (_i, [_vp, _vp, _i, _vp]),
     "ekf_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(EkfStepInfo)]),
     "ekf_frames_upload": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -353,6 +356,51 @@ class EkfEngine:
         n = _i(0)
         self._chk(self.L.ekf_get_map_points(self.h, buf, len(buf), C.byref(n)))
         return np.frombuffer(buf, dtype=MAP_POINT_DTYPE)[: n.value]
+
+    # ---- external measurements
+    @staticmethod
+    def _external_result(out):
+        return {"nis": out.nis, "z": np.array(out.z[: out.rows]), "rows": out.rows, "applied": bool(out.applied)}
+
+    def update_external(self, H_rows, residual, R, gate_nis=0.0, allow_errors=()):
+        """An EKF update with any linearised measurement, between steps: H_rows is a dense [m, n] array over the state indices
+        (its non-zeros become the rows) or (row_start, col, val) in CSR form, residual = z - h(x), R the m x m measurement
+        covariance (upper triangle read); m <= 16 rows of <= 32 entries.  gate_nis > 0: applied only if nis <= gate_nis.
+        Returns {"nis", "z", "rows", "applied"}; with allow_errors, {"code": rc} for an allowed error code."""
+        if isinstance(H_rows, tuple):
+            row_start, col, val = H_rows
+        else:
+            H = np.atleast_2d(np.asarray(H_rows, dtype=np.float64))
+            nz = [np.flatnonzero(r) for r in H]
+            row_start = np.cumsum([0] + [len(k) for k in nz])
+            col = np.concatenate(nz) if nz else np.zeros(0)
+            val = np.concatenate([r[k] for r, k in zip(H, nz)]) if nz else np.zeros(0)
+        row_start = np.ascontiguousarray(row_start, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        residual = np.ascontiguousarray(np.atleast_1d(residual), dtype=np.float64)
+        m = len(row_start) - 1
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(-1)
+        if m < 0 or len(residual) != m or R.size != m * m or len(col) != len(val) or len(col) < int(row_start[-1]):
+            raise ValueError("update_external: row_start, col / val, residual and R do not describe the same m rows")
+        out = EkfExternalUpdate()
+        rc = self._chk(self.L.ekf_update_external(self.h, m, _p(row_start), _p(col), _p(val), _p(residual), _p(R), float(gate_nis),
+                                                  C.byref(out)), allow_errors)
+        return {"code": rc} if rc else self._external_result(out)
+
+    def fuse_camera_position(self, r, R, gate_nis=0.0):
+        """a fix r of the camera position with 3 x 3 covariance R"""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(3)
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+        out = EkfExternalUpdate()
+        self._chk(self.L.ekf_fuse_camera_position(self.h, _p(r), _p(R), float(gate_nis), C.byref(out)))
+        return self._external_result(out)
+
+    def fuse_feature_distance(self, i, j, d, sigma, gate_nis=0.0):
+        """a measured distance d (standard deviation sigma) between the world points of map features i and j"""
+        out = EkfExternalUpdate()
+        self._chk(self.L.ekf_fuse_feature_distance(self.h, int(i), int(j), float(d), float(sigma), float(gate_nis), C.byref(out)))
+        return self._external_result(out)
 
     # ---- filter consistency (DESIGN.md 4.11)
     def set_consistency(self, on=True):

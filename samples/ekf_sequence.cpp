@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -16,6 +16,9 @@
 // outdir/consistency.csv, and after the last frame total NIS / total rows is printed (1 for a consistent filter).
 // --budget K (likewise): a step measures at most the K most informative of the features it predicts (ImageEKF::setMeasurementBudget);
 // after each frame the predicted and the selected count are printed and appended to outdir/log.txt.
+// --position-fixes FILE (likewise): fixes of the camera position from outside the filter (mocap, GPS, odometry), one per line as
+// "frame x y z sigma" (# starts a comment; frame = the number in the step line); after that frame's step the fix is fused with
+// R = sigma^2 I and no gate (ImageEKF::fuseCameraPosition) and its NIS is printed under the step line.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -24,14 +27,44 @@
 
 #include "../openekfmonoslam_amd/compat/ekf_io.h"
 
+struct PositionFix {
+    int frame;
+    double r[3], sigma;
+};
+
+// "frame x y z sigma" per line; # starts a comment, empty lines are skipped
+static void readPositionFixes(const std::string &path, std::vector<PositionFix> &fixes)
+{
+    std::FILE *f = std::fopen(path.c_str(), "r");
+    if (!f) throw std::runtime_error("cannot read " + path);
+    char line[512];
+    for (int no = 1; std::fgets(line, sizeof(line), f); ++no) {
+        std::string text(line);
+        text = text.substr(0, text.find('#'));
+        if (text.find_first_not_of(" \t\r\n") == std::string::npos) continue;
+        PositionFix p;
+        if (std::sscanf(text.c_str(), "%d %lf %lf %lf %lf", &p.frame, &p.r[0], &p.r[1], &p.r[2], &p.sigma) != 5 || !(p.sigma > 0.0)) {
+            std::fclose(f);
+            char where[32];
+            std::snprintf(where, sizeof(where), ":%d", no);
+            throw std::runtime_error(path + where + ": expected \"frame x y z sigma\" with sigma > 0");
+        }
+        fixes.push_back(p);
+    }
+    std::fclose(f);
+}
+
 int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
     int budget = 0;
+    std::string fixesFile;
     for (int i = 1; i < argc; ++i)
-        if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget") && i + 1 < argc) { // the flag and its value
+        if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes") &&
+            i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
+            else if (std::string(argv[i]) == "--position-fixes") fixesFile = argv[i + 1];
             else distinct = std::atof(argv[i + 1]);
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
             argc -= 2;
@@ -46,7 +79,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -61,7 +94,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty()) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -79,7 +112,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records or a measurement budget asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget or position fixes asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -88,6 +121,8 @@ int main(int argc, const char *argv[])
         extendedKalmanFilter.setNccDistinct(distinct);
         extendedKalmanFilter.setConsistency(consistency);
         extendedKalmanFilter.setMeasurementBudget(budget);
+        std::vector<PositionFix> fixes;
+        if (!fixesFile.empty()) readPositionFixes(fixesFile, fixes);
         std::FILE *csv = 0;
         if (consistency && !outputPath.empty() && !(csv = std::fopen((outputPath + "consistency.csv").c_str(), "w")))
             throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
@@ -101,6 +136,12 @@ int main(int argc, const char *argv[])
             std::printf("step %d: predicted %d matches %d li %d hi %d features %d  r = %.6f %.6f %.6f\n", extendedKalmanFilter.steps(),
                         info.n_predicted, info.n_matches, info.n_inliers, info.n_rescued, ekf_num_features(extendedKalmanFilter.engine()),
                         x[0], x[1], x[2]);
+            for (size_t k = 0; k < fixes.size(); ++k)
+                if (fixes[k].frame == extendedKalmanFilter.steps()) {
+                    const double s2 = fixes[k].sigma * fixes[k].sigma, R[9] = {s2, 0, 0, 0, s2, 0, 0, 0, s2};
+                    const EkfExternalUpdate fix = extendedKalmanFilter.fuseCameraPosition(fixes[k].r, R);
+                    std::printf("        position fix: nis %.6f\n", fix.nis);
+                }
             if (warp) {
                 int warped = 0, fallback = 0;
                 ekf_get_template_warp_counts(extendedKalmanFilter.engine(), &warped, &fallback);

@@ -14,12 +14,10 @@
 #include "device_buffers.h"
 #include "device_math.h"
 #include "patch_normal.h"
+#include "update_route.h" // NB, LD_ALIGN, B_SWEEP_MAX, round_up and the route of an update
 
 namespace ekf {
 
-constexpr int NB = 32;          // Cholesky panel width
-constexpr int LD_ALIGN = 128;   // leading dimensions are multiples of this many elements
-constexpr int B_SWEEP_MAX = 2048; // rows of S up to which B = inv(L) G is formed inside the sweep's launches
 constexpr int DX_SPLIT = 16;    // k-splits of the dx = B' z reduction
 constexpr int RANSAC_WIDE_FACTOR = 8; // hypotheses per launch behind a frame's first batch, in units of cfg.ransac_batch (engine.cpp)
 #ifndef PX_S_VALUE
@@ -28,8 +26,6 @@ constexpr int RANSAC_WIDE_FACTOR = 8; // hypotheses per launch behind a frame's 
 constexpr int PX_S = PX_S_VALUE; // EKF_PRECISION_F32_EXACT: balanced base-256 digits per element of B (kernels_pexact.hip)
 // rows of B up to which the int32 level sums of the exact downdate cannot wrap: PX_S products of |d d'| <= 2^14 per level and row
 constexpr int PX_MAX_ROWS = ((1 << 17) / PX_S) / 32 * 32; // 26208 at PX_S = 5
-
-inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // Row storage of P.  A rank keeps the 13 camera rows (replicated on every rank) at local rows 0..12 and the
 // global rows [r0, r1) it owns from local row `base` on; every row holds ALL n columns.  Unsharded engine:
@@ -206,7 +202,6 @@ struct DeviceArrays {
     uint8_t *mask = nullptr;   // generic byte mask output (rescue)
     void *pu_tilemap = nullptr; // int2 (ti, tj) per upper-triangle tile, XCD-friendly order
     void *sweep_ctl = nullptr;  // flags of the persistent Cholesky sweep (chol_persist.h), zeroed once
-    unsigned *pu_ctr = nullptr; // exact downdate, two workgroups per CU (k_p_update_i8d): unit counters, two sets of eight (one per XCD list)
     int8_t *Bq = nullptr;       // EKF_PRECISION_F32_EXACT: PX_S digit planes of B, each [bq_rows / 16][ldP][16] bytes (kernels_pexact.hip)
     int *Bexp = nullptr;        // its column scales (biased exponents), ldP ints
     uint8_t *Bz = nullptr;      // ... and which 16-row x 32-column pieces of digit plane 0 hold anything but zeros: [column / 32][bz_stride] bytes
@@ -376,7 +371,6 @@ struct EkfEngine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> px_events; // exact configuration: end of the sweep -> start of the downdate (inverse, GEMM, digit planes, dx, state)
     hipEvent_t px_mid = nullptr;                               // recorded after the sweep's last launch (timing only)
     int pu_slots = 0;         // resident workgroups of the downdate kernel on this device (0: not asked yet, -1: unknown)
-    int pu_parity = 0;        // k_p_update_i8d: the counter set the next launch uses (it zeroes the other one)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;             // image-only work of the next frame, overlapped with the update
     hipEvent_t ev_main = nullptr, ev_prefetch = nullptr;

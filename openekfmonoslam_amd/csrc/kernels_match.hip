@@ -226,12 +226,6 @@ __global__ void __launch_bounds__(256) k_match_index(const EkfMatch *m, int M, i
     if (f >= 0 && f < N) atomicMin(&match_of_feat[f], i);
 }
 
-__global__ void __launch_bounds__(256) k_fill_int(int *p, int n, int v)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 void launch_match_index(EkfEngine *e, int M, const int *d_M)
 {
     if (e->N <= 0) return;

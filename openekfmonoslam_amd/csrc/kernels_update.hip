@@ -1480,40 +1480,6 @@ static int persist_capacity(EkfEngine *e)
     return cap;
 }
 
-// grid layout of the persistent sweep of an update of m rows with n_bcols 32-column blocks of B; false: it does not fit the device
-// (decided BEFORE the gather / assembly launch, which skips the first block's factorisation for a persistent sweep)
-struct PsLayout {
-    int nbk, n_b, n_t, grid, layout_cus;
-};
-template <bool PL>
-static bool persist_layout(EkfEngine *e, int m, int n_bcols, PsLayout &L)
-{
-    const int cap = persist_capacity<PL>(e);
-    const int nbk = (m + NB - 1) / NB;
-    if (cap < 64 || nbk > B_SWEEP_MAX / NB || !e->d.sweep_ctl) return false;
-    const int ntiles = (nbk + 1) * (nbk + 2) / 2 - 1;
-    // Block order: [chain][B workers][tile workers]; block n_cus -- which in-order dispatch would put on the chain workgroup's CU --
-    // is an empty spacer.  One B worker per 32-column block (at most 3/5 of the slots), the rest tile workers: with one or two
-    // tiles each they react to a published inverse within ~3 us, which the chain needs in its first panels (the band of two tiles
-    // it applies itself covers the rest).  Measured at N = 1000 (profiles/r05_persist_layout.txt): 134 tile workers beside B workers
-    // with CUs of their own 10.4 us per panel, 200 / 322 tile workers sharing the B workers' CUs 9.4 / 9.0.
-    const int C = e->n_cus;
-    const int n_b = std::max(1, std::min(n_bcols, (cap - 2) * 3 / 5));
-    int n_t = std::min(ntiles, cap - 2 - n_b);
-#ifdef EKF_SWEEP_TRACE // tuning runs of the debug build only
-    if (const char *ev = std::getenv("EKF_PS_NT")) n_t = std::max(1, std::min(n_t, atoi(ev)));
-#endif
-    n_t = std::max(n_t, (ntiles + 63) / 64);
-    if (1 + n_b + n_t + 1 > cap) return false;
-    const bool spacer = 1 + n_b + n_t > C;
-    L.nbk = nbk;
-    L.n_b = n_b;
-    L.n_t = n_t;
-    L.grid = 1 + n_b + n_t + (spacer ? 1 : 0);
-    L.layout_cus = spacer ? C : 0;
-    return true;
-}
-
 // one launch for the whole sweep of an update of m rows (layout from persist_layout); false: not launched
 template <bool PL>
 static bool launch_persistent_sweep(EkfEngine *e, int m, const double *G, double *Bout, int n_bcols, const BPlanes &bp, const PsLayout &L)
@@ -1560,223 +1526,148 @@ static bool launch_persistent_sweep(EkfEngine *e, int m, const double *G, double
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------- the update, stage by stage
+// update_impl (below) chooses the route of the update (update_route.h) and issues its launches in these stages, in this order; a
+// stage that returns false has set e->hook_rc and ends the update.
 // T: storage type of P; TB: type of H P, of its gathered rows G, of B = inv(L) G and of the arithmetic that forms it
 // (EXACT: EKF_PRECISION_F32_EXACT, T = float, and EKF_PRECISION_F64_EXACT, T = double -- TB = double, the downdate by kernels_pexact.hip)
-template <typename T, typename TB, bool EXACT = false>
-static void update_impl(EkfEngine *e, int M, bool update_cov)
+
+// what the stages read besides the route: the gathered rows of H P (or the H P table itself through the row map: planes_b on one
+// GPU), W = inv(L)' (and L row-major in LL) of the inverse + GEMM path, and the digit planes of the rows of B
+template <typename TB>
+static TB *rows_of_G(EkfEngine *e, const UpdateRoute &r) { return (TB *)(r.planes_b && !r.sharded ? e->d.HP : e->d.G); }
+static double *inv_W(EkfEngine *e, const UpdateRoute &r) { return r.b_in_sweep ? nullptr : e->d.W; }
+template <typename TB>
+static float *inv_Wf(EkfEngine *e, const UpdateRoute &r) { return sizeof(TB) == 4 && !r.b_in_sweep ? e->d.Wf : nullptr; }
+
+static BPlanes planes_of_B(EkfEngine *e, const UpdateRoute &r)
+{
+    BPlanes bp{};
+    if (!r.planes_b) return bp;
+    bp.Bq = e->d.Bq; bp.b_stride = (size_t)e->bq_rows * e->ldP; bp.ldq = e->ldP; bp.bexp = e->d.Bexp;
+    bp.Lq = e->d.Lq; bp.nbk = e->lq_nbk; bp.l_stride = (size_t)e->lq_nbk * e->lq_nbk * 1024; bp.lexp = e->d.Lexp;
+    bp.grow = r.sharded ? nullptr : e->d.Grow;
+    bp.counts = e->d.counts;
+    bp.bcol0 = r.cb0;
+    bp.c_live0 = r.c_live0; // (the saturation check of the cut: this rank's own columns)
+    bp.n_live = r.n_live;
+    bp.no_fp64 = 1; // dx = B'z from the planes: the fp64 rows of B (8 bytes per element written, then read by k_dx_partial) never exist
+    return bp;
+}
+
+// 1. sharded exact: the diagonal of P behind the a-priori column scales -- every rank's own entries, then all of them
+static bool exchange_p_diag(EkfEngine *e, const UpdateRoute &r)
+{
+    if (!(r.sharded && (r.planes_b || r.shard_cols))) return true;
+    launch_diag_extract(e, e->d.Pdiag);
+    std::vector<int32_t> drb(e->shard_row_begin.begin(), e->shard_row_begin.end());
+    e->hook_rc = e->exchange_hook(e, EKF_XCHG_PDIAG, e->d.Pdiag, sizeof(float), drb, "the diagonal of P");
+    return e->hook_rc == 0;
+}
+
+// 2. the gathered rows G of H P and S = H P H' + R
+template <typename T, typename TB, bool EXACT>
+static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r)
 {
     hipStream_t s = e->stream;
-    const int m = 2 * M, n = e->n, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
-    const int m_pad = round_up(m, NB);
-    const int n_pad = round_up(n, LD_ALIGN);
-    // the kernels behind the sweep that write x or P leave them alone when the sweep failed (filter_frozen, engine.h); the fast fp32
-    // configuration keeps its round-3 tail (its sweep is never the persistent launch: nothing to retry)
-    const int *frz = (sizeof(T) == 4 && !EXACT) ? nullptr : e->d.counts;
-    TB *G = (TB *)e->d.G; // gathered rows of H P (or the H P table itself, see planes_b)
-    TB *A = (TB *)e->d.A; // B = inv(L) G
-    // B = inv(L) G: up to B_SWEEP_MAX rows, row block k is formed inside the launch of panel k (forward substitution
-    // beside the look-ahead factorisation: no explicit inverse, no GEMM launch); above it the per-launch row block becomes
-    // longer than the factorisation it hides behind, and the explicit inverse + one big-tile GEMM is the better use of
-    // the MFMA pipe.  e->b_path (ekf_set_update_path): 0 by size, 1 always in the sweep, 2 always by GEMM.
-    const bool b_in_sweep = e->b_path == 1 || (e->b_path == 0 && m_pad <= B_SWEEP_MAX);
-    if (sizeof(TB) == 4 && b_in_sweep && m_pad > B_SWEEP_MAX) {
-        // fp32 forward substitution over more than 64 panels changes the filter's decisions (measured at N = 5000, DESIGN.md
-        // section 6): the size switch to inverse + GEMM is an accuracy boundary -- EKF_UPDATE_PATH_SWEEP is refused there
-        e->err = "EKF_UPDATE_PATH_SWEEP with more than 2048 measurement rows in the fp32 configuration";
-        e->hook_rc = EKF_ERR_INVALID_ARG;
-        return;
-    }
-    // exact configuration on one GPU, B in the sweep: its rows are formed from int8 digit planes (chol_bplanes.h), in single-panel
-    // launches (the planes of L cover B_SWEEP_MAX rows; a sharded rank does not know the diagonal of the rows it does not own)
-    const bool sharded = e->shard_world > 1;
-    const bool shard_cols = EXACT && sharded && update_cov && e->exchange_hook && e->d.Bstage && m_pad + NB <= e->bstage_rows &&
-                            (int)e->shard_row_begin.size() == e->shard_world + 1; // every rank forms its own columns of B
-    const bool planes_b = EXACT && b_in_sweep && m_pad <= B_SWEEP_MAX && e->d.Lq != nullptr && update_cov && (!sharded || shard_cols);
-    const bool apriori = planes_b || shard_cols || (EXACT && !b_in_sweep && update_cov && e->d.Wq != nullptr); // column scales of B from diag(P)
-    // sharded step with the rows of B from digit planes: G by symmetry and S by columns (k_g_cols) instead of the exchange of the rows of G
-    // (round 5: also above 2048 rows, where B = inv(L) G is the int8 GEMM over the rank's own column tiles: no rows of G travel at any size)
-    bool sym_g = false;
-    const bool gemm_own = EXACT && !b_in_sweep && update_cov && e->d.Wq != nullptr && shard_cols;
-    if constexpr (EXACT)
-        sym_g = shard_cols && (planes_b || gemm_own) && e->after_gather != nullptr && (int)e->shard_rb.size() == e->shard_world + 1 &&
-                e->d.W != nullptr && e->d.Tbuf != nullptr;
-    BPlanes bp{};
-    // sharded: this rank forms the column blocks [cb0, cb1) of B -- the blocks whose first column lies in its share of the state
-    // rows (rank 0: from column 0) -- and receives the others' digit planes afterwards (the B role divided by the ranks)
-    int cb0 = 0, cb1 = n_pad / NB;
-    std::vector<int32_t> col_rb; // column boundaries of the ranks' shares of the planes
-    if (planes_b) {
-        bp.Bq = e->d.Bq; bp.b_stride = (size_t)e->bq_rows * ld; bp.ldq = ld; bp.bexp = e->d.Bexp;
-        bp.Lq = e->d.Lq; bp.nbk = e->lq_nbk; bp.l_stride = (size_t)e->lq_nbk * e->lq_nbk * 1024; bp.lexp = e->d.Lexp;
-        bp.grow = sharded ? nullptr : e->d.Grow;
-        bp.counts = e->d.counts;
-        bp.n_live = n;
-        bp.no_fp64 = 1; // dx = B'z from the planes: the fp64 rows of B (8 bytes per element written, then read by k_dx_partial) never exist
-    }
-    if (planes_b || shard_cols) {
-        if (sharded) {
-            const int W = e->shard_world;
-            col_rb.assign(W + 1, 0);
-            // (G by symmetry: a rank can only form the columns of the rows it holds, so the shares end exactly at the ownership
-            // boundaries and the 32-column block that straddles one is formed by both neighbours, each valid in its own columns)
-            for (int r = 1; r < W; ++r) col_rb[r] = std::min(n_pad, sym_g ? e->shard_row_begin[r] : round_up(e->shard_row_begin[r], NB));
-            col_rb[W] = n_pad;
-            e->last_col_rb = col_rb;
-            if (planes_b) {
-                cb0 = col_rb[e->shard_rank] / NB;
-                cb1 = (col_rb[e->shard_rank + 1] + NB - 1) / NB;
-                bp.bcol0 = cb0;
-                bp.c_live0 = col_rb[e->shard_rank]; // (the saturation check of the cut: this rank's own columns)
-                bp.n_live = std::min(n, (int)col_rb[e->shard_rank + 1]);
-            }
-            // the diagonal of P behind the a-priori column scales: every rank's own entries, then all of them
-            launch_diag_extract(e, e->d.Pdiag);
-            std::vector<int32_t> drb(e->shard_row_begin.begin(), e->shard_row_begin.end());
-            e->hook_rc = e->exchange_hook(e, EKF_XCHG_PDIAG, e->d.Pdiag, sizeof(float), drb, "the diagonal of P");
-            if (e->hook_rc) return;
-        }
-    }
-    // ONE persistent launch for the whole sweep (chol_persist.h) where it applies: B inside the sweep, at most B_SWEEP_MAX rows, one
-    // GPU, fp64 arithmetic of B (the fp64 and the exact configuration); otherwise the launch-per-panel sweep below
-    const int sweep_mode = e->force_launches > 0 ? EKF_SWEEP_LAUNCHES : e->sweep_mode; // (the retry of a timed-out persistent sweep)
-    const int lmode = (sweep_mode == EKF_SWEEP_PERSISTENT || sweep_mode == EKF_SWEEP_LAUNCHES) ? EKF_SWEEP_AUTO : sweep_mode;
-    bool persist = (sweep_mode == EKF_SWEEP_AUTO || sweep_mode == EKF_SWEEP_PERSISTENT) && b_in_sweep && m_pad <= B_SWEEP_MAX &&
-                   !sharded && sizeof(TB) == 8 && e->d.sweep_ctl != nullptr;
-    // by size: one B worker per block of 32 columns is what the persistent sweep is laid out for; on wider maps (from 8192 state columns
-    // on, where the launch-per-panel sweep switches to two panels per launch) its B workers take several blocks each and it loses:
-    // N = 2000, 20.4 against 14.0 us per panel (profiles/r05_bench_n2000_f32x_persistent.json)
-    if (persist && sweep_mode == EKF_SWEEP_AUTO && n_pad >= 8192) persist = false;
-    if (persist && sweep_mode == EKF_SWEEP_AUTO && e->ps_backoff > 0) { // recent time-outs (a shared device): engine.h
-        --e->ps_backoff;
-        persist = false;
-    }
-    // its grid must fit the device's resident workgroups -- decided HERE, before the gather / assembly launch leaves the first
-    // block's factorisation to the chain workgroup (a device partition with few CUs: the launch-per-panel sweep instead)
-    PsLayout ps_layout{};
-    if constexpr (sizeof(TB) == 8) {
-        if (persist) persist = planes_b ? persist_layout<true>(e, m, cb1 - cb0, ps_layout) : persist_layout<false>(e, m, n_pad / NB, ps_layout);
-    } else persist = false;
-    if (persist && ++e->ps_ok_streak >= 256) e->ps_backoff_len = 0;
-    e->last_update_M = M; // what a retry needs (engine.cpp: recover_failed_update)
-    e->last_update_cov = update_cov;
-    e->last_update_sym = e->p_exact_sym;
-    e->last_update_persist = persist;
-    e->last_update_stage = e->cons_stage;
-    double *V = e->d.Dinv, *W = b_in_sweep ? nullptr : e->d.W; // W = inv(L)' (and L row-major in LL): the GEMM path's
-    float *Wf = sizeof(TB) == 4 && !b_in_sweep ? e->d.Wf : nullptr;
-    bool merged_ga = false;
-    {
-        dim3 grid((n_pad / (int)(16 / sizeof(TB)) + 255) / 256, m_pad);
-        if ((planes_b && !sharded) || sym_g) grid.x = 1; // no copy: one workgroup per row (bookkeeping, row map, its share of the column scales)
-#define GATHER_ARGS e->d.matches, M, m_pad, (const TB *)e->d.HP, G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
+    const int M = r.M, m = r.m, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
+    const bool planes_b = r.planes_b, sharded = r.sharded, sym_g = r.sym_g, apriori = r.apriori;
+    double *V = e->d.Dinv, *W = inv_W(e, r);
+    float *Wf = inv_Wf<TB>(e, r);
+    dim3 grid((n_pad / (int)(16 / sizeof(TB)) + 255) / 256, m_pad);
+    if ((planes_b && !sharded) || sym_g) grid.x = 1; // no copy: one workgroup per row (bookkeeping, row map, its share of the column scales)
+#define GATHER_ARGS e->d.matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
                     e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->d.HPc, e->d.Gc, EXACT ? e->d.Bexp : nullptr
-        merged_ga = !sharded && !sym_g && !e->after_gather;
-        if (merged_ga) {
-            // gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output)
-            const int mb = (M + 15) / 16;
-            int *gr = planes_b ? e->d.Grow : nullptr;
-#define GA_TAIL n, gr, e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts, planes_b ? e->d.Lexp : nullptr, persist ? 0 : 1, e->px_scale_shift
-            if (apriori) k_gather_assemble<TB, T><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const T *)e->d.P, ld, GA_TAIL);
-            else k_gather_assemble<TB, float><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const float *)nullptr, 0, GA_TAIL);
+    if (r.merged_ga) {
+        // gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output)
+        const int mb = (M + 15) / 16;
+        int *gr = planes_b ? e->d.Grow : nullptr;
+#define GA_TAIL n, gr, e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts, planes_b ? e->d.Lexp : nullptr, r.persist ? 0 : 1, e->px_scale_shift
+        if (apriori) k_gather_assemble<TB, T><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const T *)e->d.P, ld, GA_TAIL);
+        else k_gather_assemble<TB, float><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const float *)nullptr, 0, GA_TAIL);
 #undef GA_TAIL
-        } else if (apriori && !sharded) // a-priori column scales from the diagonal of the covariance itself
-            k_gather<TB, T><<<grid, 256, 0, s>>>(GATHER_ARGS, (const T *)e->d.P, ld, n, planes_b || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
-        else
-            k_gather<TB, float><<<grid, 256, 0, s>>>(GATHER_ARGS, apriori ? e->d.Pdiag : nullptr, 0, n,
-                                                    (planes_b && !sharded) || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
+    } else if (apriori && !sharded) // a-priori column scales from the diagonal of the covariance itself
+        k_gather<TB, T><<<grid, 256, 0, s>>>(GATHER_ARGS, (const T *)e->d.P, ld, n, planes_b || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
+    else
+        k_gather<TB, float><<<grid, 256, 0, s>>>(GATHER_ARGS, apriori ? e->d.Pdiag : nullptr, 0, n,
+                                                (planes_b && !sharded) || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
 #undef GATHER_ARGS
-        if (planes_b && !sharded) G = (TB *)e->d.HP; // the consumers read H P through the row map (sym_g: G is formed by k_g_cols below)
-    }
     // sharded step: every rank gathered the rows of the matches it owns; the others arrive here (engine.cpp)
     e->hook_rc = (e->after_gather && !sym_g) ? e->after_gather(e, M) : 0;
-    if (e->hook_rc) return;
-    {
-        dim3 grid((M + 15) / 16, (M + 15) / 16);
-        if (sym_g) {
-            // G[:, own columns] (and the camera block) from the own rows of P; S by the block columns of the own matches, one
-            // all-gather of those columns (transposed image in W, which the sweep path does not use), the rest of S's duties after it
-            // (rows of B in the sweep: the rank's 32-column blocks; inverse + GEMM: its 128-column tiles, rounded outwards like the GEMM's)
-            const int c_lo = planes_b ? cb0 * NB : col_rb[e->shard_rank] / 128 * 128;
-            const int c_hi = planes_b ? cb1 * NB : std::min(n_pad, round_up(col_rb[e->shard_rank + 1], 128));
-            // the transposed image of the own block columns of S for the exchange: the scratch of the triangular inverse
-            // (always the inverse's scratch: round 5 used W below 2048 rows, which left W's other triangle dirty for a LATER update that
-            // takes the inverse + GEMM route -- W = inv(L)' must be zero there; found by the saturation check of the cut, round 6)
-            double *St = e->d.Tbuf;
-            const int b_lo = e->shard_rb[e->shard_rank] / 2, b_hi = e->shard_rb[e->shard_rank + 1] / 2;
-            if (c_lo > 0) k_g_cols<T><<<dim3(1, (m_pad + 63) / 64), 256, 0, s>>>((const T *)e->d.P, ld, e->rm, n, M, e->d.mHs, e->d.mHf, e->d.mpos,
-                                                                          e->d.mdim, (double *)G, ld, 0, NB, m_pad);
-            k_g_cols<T><<<dim3((c_hi - c_lo + 63) / 64, (m_pad + 63) / 64), 256, 0, s>>>((const T *)e->d.P, ld, e->rm, n, M, e->d.mHs, e->d.mHf,
-                                                                                  e->d.mpos, e->d.mdim, (double *)G, ld, c_lo, c_hi, m_pad);
-            k_assemble_S<TB><<<grid, 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
-                                                 nullptr, nullptr, ldw, e->d.counts, e->d.Lexp, nullptr, b_lo, b_hi, St, m_pad, 0);
-            // (rows of the image are m_pad doubles: only the live columns of S travel, not the capacity-strided ldW)
-            e->hook_rc = e->exchange_hook(e, EKF_XCHG_SCOLS, St, (size_t)m_pad * sizeof(double), e->shard_rb, "the columns of S");
-            if (e->hook_rc) return;
-            k_s_unpack<<<dim3((m + 255) / 256, m), 256, 0, s>>>(St, m_pad, e->d.S, ldS, m, 2 * b_lo, 2 * b_hi, e->d.Lexp);
-            k_assemble_S<TB><<<dim3(1, 1), 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
-                                                       W, nullptr, ldw, e->d.counts, nullptr, nullptr, 0, 0, nullptr, 0, 1);
-        } else if (!merged_ga)
+    if (e->hook_rc) return false;
+    TB *G = rows_of_G<TB>(e, r); // (sym_g: G is formed by k_g_cols below)
+    grid = dim3((M + 15) / 16, (M + 15) / 16);
+    if (sym_g) {
+        // G[:, own columns] (and the camera block) from the own rows of P; S by the block columns of the own matches, one
+        // all-gather of those columns, the rest of S's duties after it
+        // (rows of B in the sweep: the rank's 32-column blocks; inverse + GEMM: its 128-column tiles, rounded outwards like the GEMM's)
+        const int c_lo = planes_b ? r.cb0 * NB : r.col_rb[e->shard_rank] / 128 * 128;
+        const int c_hi = planes_b ? r.cb1 * NB : std::min(n_pad, round_up(r.col_rb[e->shard_rank + 1], 128));
+        // the transposed image of the own block columns of S for the exchange: always the scratch of the triangular inverse (W would
+        // be left with a dirty other triangle for a LATER update that takes the inverse + GEMM route -- W = inv(L)' must be zero there)
+        double *St = e->d.Tbuf;
+        const int b_lo = e->shard_rb[e->shard_rank] / 2, b_hi = e->shard_rb[e->shard_rank + 1] / 2;
+        if (c_lo > 0) k_g_cols<T><<<dim3(1, (m_pad + 63) / 64), 256, 0, s>>>((const T *)e->d.P, ld, e->rm, n, M, e->d.mHs, e->d.mHf, e->d.mpos,
+                                                                      e->d.mdim, (double *)G, ld, 0, NB, m_pad);
+        k_g_cols<T><<<dim3((c_hi - c_lo + 63) / 64, (m_pad + 63) / 64), 256, 0, s>>>((const T *)e->d.P, ld, e->rm, n, M, e->d.mHs, e->d.mHf,
+                                                                              e->d.mpos, e->d.mdim, (double *)G, ld, c_lo, c_hi, m_pad);
+        k_assemble_S<TB><<<grid, 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
+                                             nullptr, nullptr, ldw, e->d.counts, e->d.Lexp, nullptr, b_lo, b_hi, St, m_pad, 0);
+        // (rows of the image are m_pad doubles: only the live columns of S travel, not the capacity-strided ldW)
+        e->hook_rc = e->exchange_hook(e, EKF_XCHG_SCOLS, St, (size_t)m_pad * sizeof(double), e->shard_rb, "the columns of S");
+        if (e->hook_rc) return false;
+        k_s_unpack<<<dim3((m + 255) / 256, m), 256, 0, s>>>(St, m_pad, e->d.S, ldS, m, 2 * b_lo, 2 * b_hi, e->d.Lexp);
+        k_assemble_S<TB><<<dim3(1, 1), 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
+                                                   W, nullptr, ldw, e->d.counts, nullptr, nullptr, 0, 0, nullptr, 0, 1);
+    } else if (!r.merged_ga)
         k_assemble_S<TB><<<grid, 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim,
                                              e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts,
                                              planes_b ? e->d.Lexp : nullptr, planes_b && !sharded ? e->d.Grow : nullptr, 0, M, nullptr, 0,
-                                             persist ? 0 : 1); // (the persistent sweep's chain workgroup factorises the first block itself)
-    }
-    const int n_bblocks = b_in_sweep ? cb1 - cb0 : 0; // row block k of B = inv(L) G rides in the launch of panel k (sharded planes: own column blocks)
+                                             r.persist ? 0 : 1); // (the persistent sweep's chain workgroup factorises the first block itself)
+    return true;
+}
+
+// 3. the Cholesky sweep of S (with the rows of B where the route forms them in it): one persistent launch, or a launch per panel / pair
+template <typename TB, bool EXACT>
+static bool cholesky_sweep(EkfEngine *e, const UpdateRoute &r)
+{
+    hipStream_t s = e->stream;
+    const int m = r.m, m_pad = r.m_pad, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
+    TB *G = rows_of_G<TB>(e, r), *A = (TB *)e->d.A; // A: B = inv(L) G
+    double *V = e->d.Dinv, *W = inv_W(e, r);
+    float *Wf = inv_Wf<TB>(e, r);
+    const BPlanes bp = planes_of_B(e, r);
     hipEvent_t sw0 = nullptr, sw1 = nullptr;
     if (e->timing) { // the sweep's launches of this update, bracketed on the engine's stream (ekf_timing_sweep)
         (void)hipEventCreate(&sw0);
         (void)hipEventCreate(&sw1);
         (void)hipEventRecord(sw0, s);
     }
-    // One panel per launch (k_chol_step) while the launch is as long as its look-ahead workgroup; two panels per launch
-    // (chol_pair.h) once the rows of B are the longest role -- a pair launch reads the finished rows of B once for both panels
-    // (the left-looking sum re-reads ALL of them every launch: at n = 12013 that traffic, not the factorisation, sets the pace).
-    // Measured: N = 1000 9.1 us per panel in single launches against 9.55 in pairs; N = 2000 19.2 against 16.7.
-    // A launch of the pair kernel with kbB = 0 eliminates one panel and prepares the first pair (it is also how a sweep in
-    // EKF_SWEEP_PAIRS mode starts); once the 64 x 64 inverse exists the sweep stays in pairs.
-    // (panels before this one) x n_pad from which a launch is in pairs.  Maps whose rows of B are more 32-column blocks than
-    // the chip has CUs (n_pad > 8192; they get the 64-column B role of chol_pair.h) run in pairs from the first launch --
-    // N = 2000: 14.0 us per panel from the start, 14.2 from 120 k, 14.5 from 195 k (single launches: 19.2); smaller maps
-    // stay in single launches up to 195 k, i.e. N = 1000 (<= 190 k) always: 9.1 against 9.55 us per panel in pairs.
-    const long long PAIR_FROM = n_bblocks > e->n_cus ? 0 : 195000;
-    constexpr int PAIR_ROWS = 3072; // rows of the trailing matrix from which a sweep without the B role starts in pairs
     bool have_pair = false;
     int n_sweep_launches = 0;
-    if (persist) {
+    if (r.persist) {
         bool launched = false;
         if constexpr (sizeof(TB) == 8) {
-            if (planes_b) launched = launch_persistent_sweep<true>(e, m, (const double *)G, nullptr, cb1 - cb0, bp, ps_layout);
-            else launched = launch_persistent_sweep<false>(e, m, (const double *)G, (double *)A, n_pad / NB, BPlanes{}, ps_layout);
+            if (r.planes_b) launched = launch_persistent_sweep<true>(e, m, (const double *)G, nullptr, r.cb1 - r.cb0, bp, r.ps);
+            else launched = launch_persistent_sweep<false>(e, m, (const double *)G, (double *)A, n_pad / NB, BPlanes{}, r.ps);
         }
         if (!launched) { // (only a failed memset of the flag block is left: the layout was checked before the gather)
             e->err = "persistent sweep could not be launched";
             e->hook_rc = EKF_ERR_HIP;
-            return;
+            return false;
         }
         n_sweep_launches = 1;
     }
-    for (int k0 = 0; k0 < m && !persist;) {
+    for (int k0 = 0; k0 < m && !r.persist;) {
         ++n_sweep_launches;
-        // (without the rows of B -- inverse + GEMM path -- a big sweep is bound by streaming the fp64 trailing matrix once per
-        // launch: 2 x 8 m^2 bytes; pairs stream it once per two panels: N = 5000, m = 3000-4500: 16.6 -> 15.4 us per panel)
-        const bool want_pairs = lmode == EKF_SWEEP_PAIRS ||
-                                (lmode == EKF_SWEEP_AUTO &&
-                                 (b_in_sweep ? (long long)(k0 / NB) * n_pad >= PAIR_FROM : m - k0 >= PAIR_ROWS));
-        // rows of B from digit planes (chol_bplanes.h b_pair_rows_planes): two panels per launch halve the re-reads of the finished
-        // planes and the rounds of workgroups of a wide map -- N = 2000: 15.4 -> 13.3 us per panel; N = 1000: 9.9 either way, so
-        // AUTO takes pairs from 8192 state columns on (profiles/r04_sweep_pairs_planes.txt)
-        const bool want_pairs_pl = lmode == EKF_SWEEP_PAIRS || (lmode == EKF_SWEEP_AUTO && n_pad >= 8192);
-        const bool pair_launch = planes_b ? (have_pair || want_pairs_pl) : (have_pair || want_pairs);
-        const int kbA = min(NB, m - k0);
-        const int kbB = have_pair ? max(0, min(NB, m - k0 - NB)) : 0;
-        const int k2 = k0 + kbA + (pair_launch ? kbB : 0); // first row of the trailing matrix (= m: nothing below)
+        const PairStep ps = choose_pair_step(r, k0, have_pair);
+        const int kbA = min(NB, m - k0), kbB = ps.kbB;
+        const int k2 = k0 + kbA + (ps.pair_launch ? kbB : 0); // first row of the trailing matrix (= m: nothing below)
         const int nrb = (m - k2 + NB - 1) / NB; // row blocks below
         const int nsr = (nrb + 1) / 2;          // 2 x 2 groups of tiles per side
         const int n_stiles = nrb == 0 ? 0 : 1 + (nrb >= 2 ? nsr * (nsr + 1) / 2 : 0); // look-ahead tile + groups
         const int n_rhs_blocks = max(1, (m - k2 + 63) / 64); // right-hand-side blocks, 64 rows each
-        // pair launches of a large fp32 map: 64 columns of B per workgroup (chol_pair.h, b_pair_rows_wide)
-        const bool b_wide = pair_launch && kbB > 0 && sizeof(TB) == 4 && n_bblocks > e->n_cus;
-        const int n_bw = b_wide ? n_pad / (2 * NB) : n_bblocks;
+        const int n_bw = ps.b_wide ? n_pad / (2 * NB) : r.n_bblocks;
         const int n_wgs = n_stiles + n_rhs_blocks + n_bw;
         const int spacer = n_wgs > e->n_cus ? e->n_cus : 0; // see k_chol_step: empty blocks where the look-ahead workgroup's CU comes round again
         const int n_spacers = spacer ? (n_wgs - 1) / (spacer - 1) : 0; // blocks spacer, 2 spacer, ... among n_wgs + n_spacers
@@ -1786,18 +1677,18 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
         if (g_trace && g_trace_n < TRACE_MAX) {
             tr = g_trace + (size_t)TRACE_SLOTS * g_trace_n++;
             static unsigned long long tags[TRACE_MAX];
-            tags[g_trace_n - 1] = ((unsigned long long)k0 << 32) | (unsigned long long)m | (pair_launch ? 1ull << 31 : 0ull);
+            tags[g_trace_n - 1] = ((unsigned long long)k0 << 32) | (unsigned long long)m | (ps.pair_launch ? 1ull << 31 : 0ull);
             (void)hipMemcpyAsync(tr + 5, &tags[g_trace_n - 1], sizeof(unsigned long long), hipMemcpyHostToDevice, s);
             tr_abl = g_trace_abl;
         }
 #endif
-        if (pair_launch) {
+        if (ps.pair_launch) {
 #define PAIR_ARGS e->d.S, e->d.LL, sizeof(TB) == 4 ? e->d.LLf : nullptr, ldS, m, m_pad, k0, kbA, kbB, k2, e->d.nu, n_stiles, V, W, Wf, ldw,      \
                   e->d.counts, sizeof(TB) == 4 ? e->d.Gc : nullptr, e->d.zvec, e->d.Bc, G, A, ld, n_bw, n_rhs_blocks,                          \
-                  n_wgs > e->n_cus ? 1 : 0, spacer, tr, b_wide ? 1 : 0
+                  n_wgs > e->n_cus ? 1 : 0, spacer, tr, ps.b_wide ? 1 : 0
             bool launched = false;
             if constexpr (EXACT) {
-                if (planes_b) {
+                if (r.planes_b) {
                     k_chol_pair<TB, TB, true><<<n_wgs + n_spacers, 256, 0, s>>>(PAIR_ARGS, bp);
                     launched = true;
                 }
@@ -1809,7 +1700,7 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
         } else {
             k_chol_step<TB, TB><<<n_wgs + n_spacers, 256, 0, s>>>(e->d.S, e->d.LL, sizeof(TB) == 4 ? e->d.LLf : nullptr, ldS, m, m_pad, k0, kbA, e->d.nu, n_stiles,
                                                              V, W, Wf, ldw, e->d.counts, sizeof(TB) == 4 ? e->d.Gc : nullptr,
-                                                             e->d.zvec, e->d.Bc, G, A, ld, n_bblocks, n_rhs_blocks,
+                                                             e->d.zvec, e->d.Bc, G, A, ld, r.n_bblocks, n_rhs_blocks,
                                                              n_wgs > e->n_cus ? 1 : 0, spacer, tr, tr_abl, bp);
             k0 += NB;
         }
@@ -1817,120 +1708,181 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
     if (e->timing) {
         (void)hipEventRecord(sw1, s);
         e->sw_events.emplace_back(sw0, sw1);
-        if (EXACT && update_cov) { // -> launch_p_update_exact: the bracket "sweep end .. downdate start"
+        if (EXACT && r.update_cov) { // -> launch_p_update_exact: the bracket "sweep end .. downdate start"
             if (e->px_mid) (void)hipEventDestroy(e->px_mid); // (an update that failed between the two left it behind)
             e->px_mid = nullptr;
             if (hipEventCreate(&e->px_mid) == hipSuccess) (void)hipEventRecord(e->px_mid, s);
         }
-        e->sw_m.push_back(b_in_sweep ? m : -m); // negative: the rows of B were not formed in these launches
+        e->sw_m.push_back(r.b_in_sweep ? m : -m); // negative: the rows of B were not formed in these launches
         e->sw_launch.push_back(n_sweep_launches);
     }
+    return true;
+}
+
+// 4. B not formed in the sweep: inv(L), then B = inv(L) G by one GEMM
+template <typename TB>
+static void inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
+{
+    if (!r.need_inverse) return;
+    hipStream_t s = e->stream;
+    const int m = r.m, m_pad = r.m_pad, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
+    double *V = e->d.Dinv, *W = inv_W(e, r);
+    float *Wf = inv_Wf<TB>(e, r);
     // inv(L): the 128 x 128 diagonal chunks in one launch, then by doubling 128 -> 256 -> ... until one block covers all rows
-    const bool need_inverse = !b_in_sweep;
-    if (need_inverse) {
-        const int nbk = m_pad / NB, n_chunks = (nbk + INV_CH - 1) / INV_CH;
-        if (nbk > 1) k_inv_diag<<<dim3(INV_CH - 1, n_chunks), 256, 0, s>>>(e->d.LL, ldS, V, W, Wf, ldw, nbk);
-    }
-    for (int sz = INV_CH * NB; need_inverse && sz < m_pad; sz *= 2) {
+    const int nbk = m_pad / NB, n_chunks = (nbk + INV_CH - 1) / INV_CH;
+    if (nbk > 1) k_inv_diag<<<dim3(INV_CH - 1, n_chunks), 256, 0, s>>>(e->d.LL, ldS, V, W, Wf, ldw, nbk);
+    for (int sz = INV_CH * NB; sz < m_pad; sz *= 2) {
         const int npairs = (m_pad - sz + 2 * sz - 1) / (2 * sz); // pairs whose second half has rows
-        {   // 32x32 output tiles on the fp64 MFMA at every level: these products are small (m^3/3 flop in total) and
-            // need many workgroups with short k-loops rather than big tiles (64x64 tiles left 3/4 of the CUs idle)
-            const int tiles = (sz / NB) * (sz / NB);
-            k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 0);
-            k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 1);
-        }
+        // 32x32 output tiles on the fp64 MFMA at every level: these products are small (m^3/3 flop in total) and
+        // need many workgroups with short k-loops rather than big tiles (64x64 tiles left 3/4 of the CUs idle)
+        const int tiles = (sz / NB) * (sz / NB);
+        k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 0);
+        k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 1);
     }
-    // exact configuration above B_SWEEP_MAX rows: the GEMM on the int8 MFMA, straight into the digit planes of B (kernels_pexact.hip)
-    bool gemm_planes = EXACT && !b_in_sweep && update_cov && e->d.Wq != nullptr && (!sharded || shard_cols);
-#ifdef EKF_SWEEP_TRACE // accuracy experiments of the debug build: B = inv(L) G above 2048 rows by the fp64 GEMM, cut into planes afterwards
-    if (std::getenv("EKF_DBG_FP64_GEMM") && !sharded) gemm_planes = false;
-#endif
-    // covariance updates of the exact and the fp64 configuration: the state update waits behind the downdate and shares a launch
-    // with the normalisation of the covariance (k_apply_normalize); the fast fp32 configuration keeps its own tail (k_fix_normalize)
-    const bool merged_tail = update_cov && !(sizeof(T) == 4 && !EXACT);
-    if (gemm_planes) {
-        const int c_lo = shard_cols ? col_rb[e->shard_rank] : 0, c_hi = shard_cols ? col_rb[e->shard_rank + 1] : n_pad;
+    if (r.gemm_planes) {
+        const int c_lo = r.shard_cols ? r.col_rb[e->shard_rank] : 0, c_hi = r.shard_cols ? r.col_rb[e->shard_rank + 1] : n_pad;
         launch_b_gemm_planes(e, m, c_lo, c_hi);
-    } else if (!b_in_sweep) {   // B = inv(L) G = W' G : one GEMM, k <= row (W upper triangular)
-        const int TM = sizeof(TB) == 4 ? 128 : 64;
-        XtyArgs g{};
-        g.X = sizeof(TB) == 4 ? (const void *)Wf : (const void *)W; g.ldx = ldw;
-        g.Y = G; g.ldy = ld;
-        g.C = A; g.ldc = ld;
-        g.M = m_pad; g.N = n_pad; g.K = m_pad;
-        g.row0_first = 0; g.row0_stride = 0; g.m_lim = m_pad;
-        g.tri = 2; g.tiles_i = (m_pad + TM - 1) / TM; g.tiles_j = (n_pad + TM - 1) / TM; g.alpha = 1.0;
-        if (shard_cols) { // own columns only (tile-rounded outwards: a few columns of the neighbours are formed twice)
-            g.tj0 = col_rb[e->shard_rank] / TM;
-            g.tiles_j = (col_rb[e->shard_rank + 1] + TM - 1) / TM - g.tj0;
-        }
-        g.n_split = g.tiles_i / 2; // k-depth of row tile i is ~(i+1) TM: halve the units of the longer half
-        launch_xty(e, g, 1, sizeof(TB) == 4, s);
+        return;
     }
-    if (shard_cols) {
+    // B = inv(L) G = W' G : one GEMM, k <= row (W upper triangular)
+    const int TM = sizeof(TB) == 4 ? 128 : 64;
+    XtyArgs g{};
+    g.X = sizeof(TB) == 4 ? (const void *)Wf : (const void *)W; g.ldx = ldw;
+    g.Y = rows_of_G<TB>(e, r); g.ldy = ld;
+    g.C = e->d.A; g.ldc = ld;
+    g.M = m_pad; g.N = n_pad; g.K = m_pad;
+    g.row0_first = 0; g.row0_stride = 0; g.m_lim = m_pad;
+    g.tri = 2; g.tiles_i = (m_pad + TM - 1) / TM; g.tiles_j = (n_pad + TM - 1) / TM; g.alpha = 1.0;
+    if (r.shard_cols) { // own columns only (tile-rounded outwards: a few columns of the neighbours are formed twice)
+        g.tj0 = r.col_rb[e->shard_rank] / TM;
+        g.tiles_j = (r.col_rb[e->shard_rank + 1] + TM - 1) / TM - g.tj0;
+    }
+    g.n_split = g.tiles_i / 2; // k-depth of row tile i is ~(i+1) TM: halve the units of the longer half
+    launch_xty(e, g, 1, sizeof(TB) == 4, s);
+}
+
+// 5. dx = B'z and the state (which waits for the covariance tail where the route merges the two)
+template <typename T, typename TB, bool EXACT>
+static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
+{
+    hipStream_t s = e->stream;
+    const int m = r.m, n = r.n, ld = e->ldP;
+    if (r.shard_cols) {
         // every rank's column blocks of the digit planes to every rank: pack [column][plane][k group], row-block exchange, unpack;
         // dx = B'z then comes from the planes (the fp64 rows of B exist only for the own columns)
         const int m_k = round_up(m, 32), m16 = m_k / 16;
-        if (!planes_b && !gemm_planes) launch_slice_columns(e, m, col_rb[e->shard_rank], col_rb[e->shard_rank + 1]); // B came out of the GEMM in fp64
-        launch_planes_move(e, true, m_k, col_rb[e->shard_rank], col_rb[e->shard_rank + 1], 0, 0);
-        e->hook_rc = e->exchange_hook(e, EKF_XCHG_BPLANES, e->d.Bstage, (size_t)PX_S * m16 * 16, col_rb, "the digit planes of B");
-        if (e->hook_rc) return;
-        launch_planes_move(e, false, m_k, 0, n_pad, col_rb[e->shard_rank], col_rb[e->shard_rank + 1]);
+        const int c0 = r.col_rb[e->shard_rank], c1 = r.col_rb[e->shard_rank + 1];
+        if (!r.planes_b && !r.gemm_planes) launch_slice_columns(e, m, c0, c1); // B came out of the GEMM in fp64
+        launch_planes_move(e, true, m_k, c0, c1, 0, 0);
+        e->hook_rc = e->exchange_hook(e, EKF_XCHG_BPLANES, e->d.Bstage, (size_t)PX_S * m16 * 16, r.col_rb, "the digit planes of B");
+        if (e->hook_rc) return false;
+        launch_planes_move(e, false, m_k, 0, r.n_pad, c0, c1);
         launch_dx_planes(e, m_k);
-        const int nt = max(e->N * 6, 1);
-        if (!merged_tail)
-            k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
-                                                           e->N, e->d.dx_part, ld, update_cov ? 1 : 0, frz);
-    } else if (gemm_planes || planes_b) { // B exists as digit planes only
+    } else if (r.gemm_planes || r.planes_b) { // B exists as digit planes only
         launch_dx_planes(e, round_up(m, 32));
-        const int nt = max(e->N * 6, 1);
-        if (!merged_tail)
-            k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
-                                                           e->N, e->d.dx_part, ld, update_cov ? 1 : 0, frz);
     } else {
         dim3 grid((n + 255) / 256, DX_SPLIT);
-        const bool fix = update_cov && sizeof(T) == 4 && !EXACT; // (the exact downdate needs no fp64 repair of the diagonal / camera rows)
+        const bool fix = r.fix;
         const int avg = e->p_exact_sym ? 0 : 1; // an AVG downdate only exists on an unsharded engine: every row is local
+        const TB *A = (const TB *)e->d.A;
         const double *Bc = nullptr;
         const TB *Gy = nullptr;
         if (sizeof(TB) == 4) { // (with B in fp64 its camera columns and B'z need no fp64 side channel)
             Bc = e->d.Bc; // inv(L) Gc, produced by the right-hand-side blocks of k_chol_step
             // feature columns of dx: with the explicit inverse at hand, (H P)' y with y = inv(L)' z in fp64 (k_yvec);
             // on the sweep path B' z (fp32 B): the same to 1e-6 of the largest component of a block, see DESIGN.md section 6
-            Gy = need_inverse ? G : nullptr;
-            if (Gy) k_yvec<<<(m + 3) / 4, 256, 0, s>>>(W, ldw, m, e->d.zvec, e->d.yvec);
+            Gy = r.need_inverse ? rows_of_G<TB>(e, r) : nullptr;
+            if (Gy) k_yvec<<<(m + 3) / 4, 256, 0, s>>>(inv_W(e, r), e->ldW, m, e->d.zvec, e->d.yvec);
         }
 #define DX_LAUNCH(USEG) k_dx_partial<TB, USEG, T><<<grid, 256, 0, s>>>(A, ld, m, n, e->d.zvec, e->d.dx_part, ld, \
                                              fix ? e->d.sq_part : nullptr, fix ? e->d.cam_part : nullptr, Bc, (const T *)e->d.P, \
                                              e->rm, e->d.diag_save, fix ? e->d.cam_save : nullptr, avg, Gy, e->d.yvec, \
-                                             (EXACT && update_cov && !apriori) ? e->d.Bexp : nullptr, e->d.state);
+                                             (EXACT && r.update_cov && !r.apriori) ? e->d.Bexp : nullptr, e->d.state);
         if (Gy) { DX_LAUNCH(true) } else { DX_LAUNCH(false) }
 #undef DX_LAUNCH
-
-        const int nt = max(e->N * 6, 1);
-        if (!merged_tail)
-            k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos,
-                                                           e->N, e->d.dx_part, ld, update_cov ? 1 : 0, frz);
     }
+    if (!r.merged_tail) {
+        const int nt = max(e->N * 6, 1);
+        k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos, e->N, e->d.dx_part, ld,
+                                                       r.update_cov ? 1 : 0, r.fix_diag ? nullptr : e->d.counts);
+    }
+    return true;
+}
+
+// 6. the consistency record, the downdate of P and the covariance tail
+template <typename T, bool EXACT>
+static void downdate_and_tail(EkfEngine *e, const UpdateRoute &r)
+{
+    hipStream_t s = e->stream;
+    const int n = r.n, ld = e->ldP;
     // filter consistency: z is final in d.zvec and the error flag tells whether this sweep failed
-    if (e->consistency && update_cov) launch_consistency(e, M);
-    if (!update_cov) return;
-    const bool fix_diag = sizeof(T) == 4 && !EXACT;
-    if (EXACT) launch_p_update_exact(e, m, false, true, planes_b || shard_cols || gemm_planes); // (column scales: k_gather + k_dx_partial, or a-priori; planes: the sweep's / the GEMM's / the ranks')
-    else launch_p_update(e, m_pad, m);
-    if (fix_diag) {
+    if (e->consistency && r.update_cov) launch_consistency(e, r.M);
+    if (!r.update_cov) return;
+    // (column scales: k_gather + k_dx_partial, or a-priori; planes: the sweep's / the GEMM's / the ranks')
+    if (EXACT) launch_p_update_exact(e, r.m, false, true, r.planes_b || r.shard_cols || r.gemm_planes);
+    else launch_p_update(e, r.m_pad, r.m);
+    // the kernels behind the sweep that write x or P leave them alone when the sweep failed (filter_frozen, engine.h); the fast fp32
+    // configuration keeps its own tail (its sweep is never the persistent launch: nothing to retry)
+    if (r.fix_diag) {
         k_fix_normalize<T><<<(n + 255) / 256, 256, 0, s>>>((T *)e->d.P, ld, n, e->rm, e->d.diag_save, e->d.sq_part, e->d.cam_save,
                                                            e->d.cam_part, ld, e->d.state);
         return;
     }
     const int nb = 1 + (n > 7 ? (n - 7 + 255) / 256 : 0);
-    if (merged_tail) {
+    if (r.merged_tail) {
         const int nt = max(e->N * 6, 1);
         k_apply_normalize<T><<<max(nb, (nt + 255) / 256), 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, e->d.feat_pos, e->d.feat_type,
-                                                                       e->d.feat_covpos, e->N, e->d.dx_part, ld, frz);
+                                                                       e->d.feat_covpos, e->N, e->d.dx_part, ld, e->d.counts);
         return;
     }
-    k_normalize_cov<T><<<nb, 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, frz);
+    k_normalize_cov<T><<<nb, 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, e->d.counts);
+}
+
+// the route, the two effects it reports (back-off bookkeeping) with what a retry needs, then the launches
+template <typename T, typename TB, bool EXACT = false>
+static void update_impl(EkfEngine *e, int M, bool update_cov)
+{
+    UpdateRouteIn in;
+    in.M = M; in.n = e->n; in.update_cov = update_cov;
+    in.b_fp32 = sizeof(TB) == 4; in.p_fp32 = sizeof(T) == 4; in.exact = EXACT;
+    in.b_path = e->b_path; in.sweep_mode = e->sweep_mode; in.force_launches = e->force_launches > 0; in.ps_backoff = e->ps_backoff > 0;
+    in.shard_world = e->shard_world; in.shard_rank = e->shard_rank;
+    in.shard_row_begin = e->shard_row_begin.data(); in.n_shard_row_begin = e->shard_row_begin.size();
+    in.Lq = e->d.Lq != nullptr; in.Wq = e->d.Wq != nullptr; in.Bstage = e->d.Bstage != nullptr; in.bstage_rows = e->bstage_rows;
+    in.W = e->d.W != nullptr; in.Tbuf = e->d.Tbuf != nullptr; in.sweep_ctl = e->d.sweep_ctl != nullptr;
+    in.exchange_hook = e->exchange_hook != nullptr; in.after_gather = e->after_gather != nullptr;
+    in.shard_rb_ok = (int)e->shard_rb.size() == e->shard_world + 1;
+    in.n_cus = e->n_cus;
+    if (sizeof(TB) == 8) { // (the persistent sweep needs the fp64 arithmetic of B)
+        in.ps_cap[0] = persist_capacity<false>(e);
+        in.ps_cap[1] = persist_capacity<true>(e);
+    }
+    UpdateRoute r = choose_update_route(in);
+    if (r.refusal) {
+        e->err = r.refusal;
+        e->hook_rc = EKF_ERR_INVALID_ARG;
+        return;
+    }
+#ifdef EKF_SWEEP_TRACE // tuning runs and accuracy experiments of the debug build only
+    if (const char *ev = std::getenv("EKF_PS_NT"); ev && r.persist) ps_set_tile_workers(r.ps, std::max(1, std::min(r.ps.n_t, atoi(ev))), e->n_cus);
+    // B = inv(L) G above 2048 rows by the fp64 GEMM, cut into planes afterwards
+    if (std::getenv("EKF_DBG_FP64_GEMM") && !r.sharded) r.gemm_planes = false;
+#endif
+    if (r.consumed_backoff) --e->ps_backoff;
+    if (r.persist && ++e->ps_ok_streak >= 256) e->ps_backoff_len = 0;
+    if (!r.col_rb.empty()) e->last_col_rb = r.col_rb; // (ekf_shard_counters)
+    e->last_update_M = M; // what a retry needs (engine.cpp: recover_failed_update)
+    e->last_update_cov = update_cov;
+    e->last_update_sym = e->p_exact_sym;
+    e->last_update_persist = r.persist;
+    e->last_update_stage = e->cons_stage;
+
+    if (!exchange_p_diag(e, r)) return;
+    if (!gather_and_assemble<T, TB, EXACT>(e, r)) return;
+    if (!cholesky_sweep<TB, EXACT>(e, r)) return;
+    inverse_and_gemm<TB>(e, r);
+    if (!dx_and_state<T, TB, EXACT>(e, r)) return;
+    downdate_and_tail<T, EXACT>(e, r);
 }
 
 void launch_update(EkfEngine *e, int M, bool update_cov)

@@ -91,15 +91,37 @@ __host__ __device__ __forceinline__ void dir_vec(double theta, double phi, doubl
     m[2] = cp * cos(theta);
 }
 
+// sin and cos of an inverse-depth feature's two angles.  One evaluation is a few hundred fp64 instructions, and the compiler does
+// not merge the evaluations that the projection, the Jacobians' second projection, d h/d q and d h/d feature each asked for: they
+// are evaluated once per feature and handed on (the same functions of the same arguments: the same bits).
+struct AngleTrig {
+    double st, ct, sp, cp; // sin(theta), cos(theta), sin(phi), cos(phi)
+};
+__device__ __forceinline__ AngleTrig angle_trig(double theta, double phi)
+{
+    AngleTrig t;
+    t.cp = cos(phi);
+    t.st = sin(theta);
+    t.sp = sin(phi);
+    t.ct = cos(theta);
+    return t;
+}
+// dir_vec from them
+__device__ __forceinline__ void dir_vec_t(const AngleTrig &t, double *m)
+{
+    m[0] = t.cp * t.st;
+    m[1] = -t.sp;
+    m[2] = t.cp * t.ct;
+}
+
 // Point of a feature in "camera axes" using rotation M (R' or inv(R)):
 // MeasurementPrediction.cpp:127-140 (inverse depth), :147-156 (depth)
-__device__ __forceinline__ void to_camera(const double *fp, int type, const double *r, const double *M, double *h)
+// (m: the direction vector of an inverse-depth feature, not read for the other kind)
+__device__ __forceinline__ void to_camera_m(const double *fp, int type, const double *r, const double *M, const double *m, double *h)
 {
     double t[3];
     if (type == EKF_FEATURE_INVERSE_DEPTH) {
-        double m[3];
         const double rho = fp[5];
-        dir_vec(fp[3], fp[4], m);
         t[0] = rho * (fp[0] - r[0]) + m[0];
         t[1] = rho * (fp[1] - r[1]) + m[1];
         t[2] = rho * (fp[2] - r[2]) + m[2];
@@ -109,6 +131,12 @@ __device__ __forceinline__ void to_camera(const double *fp, int type, const doub
         t[2] = fp[2] - r[2];
     }
     mat3_vec(M, t, h);
+}
+__device__ __forceinline__ void to_camera(const double *fp, int type, const double *r, const double *M, double *h)
+{
+    double m[3] = {0.0, 0.0, 0.0};
+    if (type == EKF_FEATURE_INVERSE_DEPTH) dir_vec(fp[3], fp[4], m);
+    to_camera_m(fp, type, r, M, m, h);
 }
 
 // Radial distortion by 10 Newton iterations: MeasurementPrediction.cpp:47-83
@@ -135,11 +163,12 @@ __device__ __forceinline__ void distort(const CamD &c, double u, double v, doubl
 // One feature of predictMeasurementState (MeasurementPrediction.cpp:203-265): returns true and the distorted
 // pixel when the feature is inside the field of view (:162-171) and strictly inside the frame (:176-181).
 // Rt = R', Rinv = inv(R): inverse-depth features use R', depth features use inv(R) (:226,:230).
-__device__ __forceinline__ bool predict_pixel(const CamD &c, const double *r, const double *Rt, const double *Rinv,
-                                              const double *fp, int type, double *uv)
+// (m: see to_camera_m)
+__device__ __forceinline__ bool predict_pixel_m(const CamD &c, const double *r, const double *Rt, const double *Rinv,
+                                                const double *fp, int type, const double *m, double *uv)
 {
     double h[3];
-    to_camera(fp, type, r, type == EKF_FEATURE_INVERSE_DEPTH ? Rt : Rinv, h);
+    to_camera_m(fp, type, r, type == EKF_FEATURE_INVERSE_DEPTH ? Rt : Rinv, m, h);
     const double ax = atan2(h[0], h[2]) * 180.0 / EKF_PI;
     const double ay = atan2(h[1], h[2]) * 180.0 / EKF_PI;
     if (!(-c.avx < ax && ax < c.avx && -c.avy < ay && ay < c.avy)) return false;
@@ -147,6 +176,13 @@ __device__ __forceinline__ bool predict_pixel(const CamD &c, const double *r, co
     const double v = c.cy + (c.fy * h[1] / h[2]);
     distort(c, u, v, uv);
     return uv[0] > 0 && uv[0] < c.W && uv[1] > 0 && uv[1] < c.H;
+}
+__device__ __forceinline__ bool predict_pixel(const CamD &c, const double *r, const double *Rt, const double *Rinv,
+                                              const double *fp, int type, double *uv)
+{
+    double m[3] = {0.0, 0.0, 0.0};
+    if (type == EKF_FEATURE_INVERSE_DEPTH) dir_vec(fp[3], fp[4], m);
+    return predict_pixel_m(c, r, Rt, Rinv, fp, type, m, uv);
 }
 
 // d(R(q) a)/dq as a 3x4 matrix: EKF/CommonFunctions.cpp:87-145
@@ -162,10 +198,11 @@ __device__ __forceinline__ void jac_rot_by_quat(const double *q, const double *a
 
 // Measurement Jacobian blocks of one feature: Hs = d h/d(r,q) (2x7; the reference's 2x13 block has columns
 // 7..12 structurally zero, MeasurementPrediction.cpp:498-499,603) and Hf = d h/d(feature) (2x6, first d used).
-// x13 = camera state, Rinv = inv(R(q)), uvd = the predicted distorted pixel.  MeasurementPrediction.cpp:273-589.
+// x13 = camera state, Rinv = inv(R(q)), uvd = the predicted distorted pixel; tg, m = angle_trig / dir_vec_t of an inverse-depth
+// feature's angles (not read for the other kind).  MeasurementPrediction.cpp:273-589.
 __device__ __forceinline__ void measurement_jacobians(const CamD &c, const double *x13, const double *Rinv,
-                                                      const double *fp, int type, const double *uvd, double *Hs,
-                                                      double *Hf)
+                                                      const double *fp, int type, const double *uvd, const AngleTrig &tg,
+                                                      const double *m, double *Hs, double *Hf)
 {
     const bool invd = (type == EKF_FEATURE_INVERSE_DEPTH);
     // projection o distortion Jacobian, 2x3 (:343-362)
@@ -183,7 +220,7 @@ __device__ __forceinline__ void measurement_jacobians(const CamD &c, const doubl
         dj[2] = pdy * kk * (2 * pdx * c.dx * c.dx);
         inv2(dj, idj);
         double h[3];
-        to_camera(fp, type, x13, Rinv, h); // note: inv(R) for both feature kinds here (:284,:288)
+        to_camera_m(fp, type, x13, Rinv, m, h); // note: inv(R) for both feature kinds here (:284,:288)
         const double f0 = c.fx / h[2], f2 = -h[0] * c.fx / (h[2] * h[2]);
         const double f4 = c.fy / h[2], f5 = -h[1] * c.fy / (h[2] * h[2]);
         pj[0] = idj[0] * f0 + idj[1] * 0.0;
@@ -211,8 +248,6 @@ __device__ __forceinline__ void measurement_jacobians(const CamD &c, const doubl
     {
         double a[3] = {ymr[0], ymr[1], ymr[2]};
         if (invd) {
-            double m[3];
-            dir_vec(fp[3], fp[4], m);
             a[0] = a[0] * rho + m[0];
             a[1] = a[1] * rho + m[1];
             a[2] = a[2] * rho + m[2];
@@ -231,8 +266,7 @@ __device__ __forceinline__ void measurement_jacobians(const CamD &c, const doubl
     }
     // d h/d feature
     if (invd) {
-        const double theta = fp[3], phi = fp[4];
-        const double cp = cos(phi), ct = cos(theta), st = sin(theta), sp = sin(phi);
+        const double cp = tg.cp, ct = tg.ct, st = tg.st, sp = tg.sp;
         const double dth[3] = {cp * ct, 0.0, -cp * st};
         const double dph[3] = {-sp * st, -cp, -sp * ct};
         double rth[3], rph[3];

@@ -308,6 +308,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     ALLOC(d.msel, cap);
     ALLOC(d.mout, cap);
     ALLOC(d.match_of_feat, cap);
+    ALLOC(d.ransac_rec, mcap);
     // (a frame's first batch is ransac_batch hypotheses; the batches behind it -- a fresh map needs hundreds of hypotheses -- are
     // RANSAC_WIDE_FACTOR times wider: one workgroup per hypothesis, and 32 workgroups leave seven eighths of the chip idle)
     ALLOC(d.hyp_count, (size_t)e->cfg.ransac_batch * RANSAC_WIDE_FACTOR);

@@ -106,6 +106,17 @@ struct ExtResult {
     int verdict, pad;
 };
 
+// 1-point RANSAC: what a hypothesis needs of one match, gathered once per frame by the launch that writes the feature -> match index
+// (k_match_compact on the step path, k_match_index behind an arbitrary list) so that the hypotheses' workgroups read ONE contiguous
+// record per match instead of chasing match -> feature -> type / position / parameters through four tables each
+struct RansacRec {
+    double fp[6];  // the feature's parameters
+    double img[2]; // the matched image position
+    int f;         // feature index, -1: outside the map (such a match supports nothing)
+    int type, pos; // feature type, covariance position
+    int pad;
+};
+
 struct DeviceArrays {
     // map + state
     double *state = nullptr;    // ST_COUNT doubles: x13, R, F, GQG, Jnorm
@@ -171,6 +182,7 @@ struct DeviceArrays {
     EkfPrediction *preds_out = nullptr; // staging for prediction downloads
     int *match_of_feat = nullptr;
     // RANSAC
+    RansacRec *ransac_rec = nullptr; // mcap records, one per match of the list match_of_feat indexes
     int *hyp_count = nullptr;
     uint8_t *hyp_flags = nullptr;  // batch x mcap
     uint8_t *best_flags = nullptr; // mcap
@@ -428,6 +440,23 @@ void launch_xty(EkfEngine *e, const XtyArgs &a, int batch, bool f32, hipStream_t
 // there, i.e. K = 0 and an unchanged filter, EKF/Update.cpp:101-108).  counts == nullptr: no guard (stage calls that synchronise).
 #ifdef __HIPCC__
 __device__ __forceinline__ bool filter_frozen(const int *counts) { return counts != nullptr && counts[CNT_ERR] != 0; }
+
+// the RANSAC record of a match of feature f at pixel (u, v): see RansacRec
+__device__ __forceinline__ RansacRec load_ransac_rec(int f, int N, const double *feat_pos, const int *feat_type, const int *feat_covpos,
+                                                     double u, double v)
+{
+    RansacRec r;
+    const bool in_map = f >= 0 && f < N;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) r.fp[a] = in_map ? feat_pos[6 * f + a] : 0.0;
+    r.img[0] = u;
+    r.img[1] = v;
+    r.f = in_map ? f : -1;
+    r.type = in_map ? feat_type[f] : 0;
+    r.pos = in_map ? feat_covpos[f] : 0;
+    r.pad = 0;
+    return r;
+}
 
 // quaternion normalisation and its Jacobian (Update.cpp:45-62, 303-312), one thread: J from the un-normalised q, then q /= |q|
 // and R(q)

@@ -126,7 +126,8 @@ k_match(const int *plist, const double *uv_tab, const double *S_tab, const uint8
 __global__ void __launch_bounds__(1024)
 k_match_compact(const int *plist, int n_pred, const int *mt_valid, const int *mt_kp, const float *mt_dist,
                 const EkfKeypoint *kps, int by_slot, EkfMatch *out, int *out_count, const int *d_npred,
-                int *rs_counts, int *match_of_feat, uint8_t *best_flags, int N)
+                int *rs_counts, int *match_of_feat, uint8_t *best_flags, int N, RansacRec *rec, const double *feat_pos,
+                const int *feat_type, const int *feat_covpos)
 {
     if (d_npred) n_pred = *d_npred;
     __shared__ int wtot[16];
@@ -145,28 +146,51 @@ k_match_compact(const int *plist, int n_pred, const int *mt_valid, const int *mt
             match_of_feat[i] = 0x7fffffff;
             best_flags[i] = 0;
         }
-        __syncthreads();
     }
     const int per = (n_pred + 1023) / 1024;
     const int b = tid * per, e = min(n_pred, b + per);
-    int c = 0;
-    for (int i = b; i < e; ++i) c += mt_valid[i];
+    // One entry of the list with everything its stores need, in two rounds of loads: the slot's tables, then the keypoint and (for
+    // the RANSAC record) the feature.  A thread's FIRST entry -- its only one up to 1024 predictions -- is gathered before the scan,
+    // whose result only says where to store it: the launch is two dependent rounds deep instead of four.
+    struct Entry {
+        EkfMatch m;
+        RansacRec r;
+        int valid;
+    };
+    auto gather = [&](int i) {
+        Entry t;
+        t.valid = mt_valid[i];
+        t.m.featureIndex = plist[i];
+        // by_slot (NCC matcher): the matched pixel sits in kps[prediction slot]; there is no keypoint index
+        const int kp = by_slot ? i : mt_kp[i];
+        t.m.keypointIndex = by_slot ? -1 : kp;
+        t.m.distance = mt_dist[i];
+        t.m._pad = 0.f;
+        if (t.valid) {
+            t.m.imagePos[0] = (double)kps[kp].x;
+            t.m.imagePos[1] = (double)kps[kp].y;
+            // + the hypotheses' record of this match (engine.h: RansacRec)
+            if (rs_counts) t.r = load_ransac_rec(t.m.featureIndex, N, feat_pos, feat_type, feat_covpos, t.m.imagePos[0], t.m.imagePos[1]);
+        }
+        return t;
+    };
+    Entry first;
+    first.valid = 0;
+    if (b < e) first = gather(b);
+    if (rs_counts) __syncthreads(); // (match_of_feat is set to "none" above and written below)
+    int c = first.valid;
+    for (int i = b + 1; i < e; ++i) c += mt_valid[i];
     int total;
     int pos = block_exclusive_scan_1024(c, wtot, &total);
-    for (int i = b; i < e; ++i)
-        if (mt_valid[i]) {
-            EkfMatch m;
-            m.featureIndex = plist[i];
-            // by_slot (NCC matcher): the matched pixel sits in kps[prediction slot]; there is no keypoint index
-            const int kp = by_slot ? i : mt_kp[i];
-            m.keypointIndex = by_slot ? -1 : kp;
-            m.imagePos[0] = (double)kps[kp].x;
-            m.imagePos[1] = (double)kps[kp].y;
-            m.distance = mt_dist[i];
-            m._pad = 0.f;
-            if (rs_counts) match_of_feat[m.featureIndex] = pos;
-            out[pos++] = m;
+    for (int i = b; i < e; ++i) {
+        const Entry t = i == b ? first : gather(i);
+        if (!t.valid) continue;
+        if (rs_counts) {
+            match_of_feat[t.m.featureIndex] = pos;
+            rec[pos] = t.r;
         }
+        out[pos++] = t.m;
+    }
     if (tid == 1023) *out_count = total;
 }
 
@@ -184,7 +208,8 @@ void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, in
                                            d_nkp);
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
                                                kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
-                                               with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N);
+                                               with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N,
+                                               e->d.ransac_rec, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos);
 }
 
 // Sharded filter ("Matching: features/ellipses independent => shard by feature ... all-gather match lists"): a rank
@@ -206,31 +231,37 @@ void launch_match_compact(EkfEngine *e, const EkfKeypoint *kps, int n_pred)
         return;
     }
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, kps, 0, e->d.matches,
-                                               e->d.counts + CNT_NMATCH, nullptr, nullptr, nullptr, nullptr, 0);
+                                               e->d.counts + CNT_NMATCH, nullptr, nullptr, nullptr, nullptr, 0,
+                                               nullptr, nullptr, nullptr, nullptr);
 }
 
 void launch_match_compact_slots(EkfEngine *e, int n_pred, const EkfKeypoint *d_slot_xy)
 {
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, d_slot_xy,
-                                               1, e->d.matches, e->d.counts + CNT_NMATCH, nullptr, nullptr, nullptr, nullptr, 0);
+                                               1, e->d.matches, e->d.counts + CNT_NMATCH, nullptr, nullptr, nullptr, nullptr, 0,
+                                               nullptr, nullptr, nullptr, nullptr);
 }
 
 // match_of_feat[f] = smallest match index whose featureIndex is f, or -1 (the linear searches of
-// 1PointRansac.cpp:58-82 stop at the first hit)
-__global__ void __launch_bounds__(256) k_match_index(const EkfMatch *m, int M, int *match_of_feat, int N, const int *d_M)
+// 1PointRansac.cpp:58-82 stop at the first hit); + the hypotheses' record of every match (engine.h: RansacRec)
+__global__ void __launch_bounds__(256)
+k_match_index(const EkfMatch *m, int M, int *match_of_feat, int N, const int *d_M, RansacRec *rec, const double *feat_pos,
+              const int *feat_type, const int *feat_covpos)
 {
     if (d_M) M = *d_M;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
     const int f = m[i].featureIndex;
     if (f >= 0 && f < N) atomicMin(&match_of_feat[f], i);
+    rec[i] = load_ransac_rec(f, N, feat_pos, feat_type, feat_covpos, m[i].imagePos[0], m[i].imagePos[1]);
 }
 
 void launch_match_index(EkfEngine *e, int M, const int *d_M)
 {
     if (e->N <= 0) return;
     // match_of_feat was set to "none" by launch_ransac_init, which precedes this launch
-    if (M > 0) k_match_index<<<(M + 255) / 256, 256, 0, e->stream>>>(e->d.matches, M, e->d.match_of_feat, e->N, d_M);
+    if (M > 0) k_match_index<<<(M + 255) / 256, 256, 0, e->stream>>>(e->d.matches, M, e->d.match_of_feat, e->N, d_M,
+                                                                      e->d.ransac_rec, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos);
 }
 
 // Stable partition of src[0..M) by flags: dst1 receives the flagged matches, dst0 (optional) the others, both in
@@ -248,31 +279,46 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
     }
     const int per = (M + 1023) / 1024;
     const int b = tid * per, e = min(M, b + per);
+    // A thread's FIRST match -- its only one up to 1024 matches -- and its flag stay in registers from the first load to the map's
+    // bookkeeping: the scan only says where to store it.  (Reading flags and matches again behind the scan, and the selected list
+    // again behind a barrier for the bookkeeping, made this launch five dependent round trips deep.)
+    EkfMatch m0;
+    int f0 = 0;
+    if (b < e) m0 = src[b];
+    // rescueOutliers (EKF.cpp:84-97) in the same launch: the flags of this partition are nu' inv(S_i) nu < chi2 against
+    // the re-predicted measurements -- k_rescue's expression, thread-private entries of the mask
+    auto rescued = [&](const EkfMatch &m) {
+        const int fi = m.featureIndex;
+        const double d0 = m.imagePos[0] - uv_tab[2 * fi];
+        const double d1 = m.imagePos[1] - uv_tab[2 * fi + 1];
+        double Si[4];
+        inv2(S_tab + 4 * fi, Si);
+        const double t0 = d0 * Si[0] + d1 * Si[2];
+        const double t1 = d0 * Si[1] + d1 * Si[3];
+        const double v = t0 * d0 + t1 * d1;
+        return (vis[fi] && v < chi2) ? 1 : 0;
+    };
     if (rescue_mask) {
-        // rescueOutliers (EKF.cpp:84-97) in the same launch: the flags of this partition are nu' inv(S_i) nu < chi2 against
-        // the re-predicted measurements -- k_rescue's expression, thread-private entries of the mask
-        for (int i = b; i < e; ++i) {
-            const int fi = src[i].featureIndex;
-            const double d0 = src[i].imagePos[0] - uv_tab[2 * fi];
-            const double d1 = src[i].imagePos[1] - uv_tab[2 * fi + 1];
-            double Si[4];
-            inv2(S_tab + 4 * fi, Si);
-            const double t0 = d0 * Si[0] + d1 * Si[2];
-            const double t1 = d0 * Si[1] + d1 * Si[3];
-            const double v = t0 * d0 + t1 * d1;
-            rescue_mask[i] = (vis[fi] && v < chi2) ? 1 : 0;
-        }
+        if (b < e) rescue_mask[b] = (uint8_t)(f0 = rescued(m0));
+        for (int i = b + 1; i < e; ++i) rescue_mask[i] = (uint8_t)rescued(src[i]);
         flags = rescue_mask;
-    }
-    int c = 0;
-    for (int i = b; i < e; ++i) c += flags[i] ? 1 : 0;
+    } else if (b < e) f0 = flags[b] ? 1 : 0;
+    int c = f0;
+    for (int i = b + 1; i < e; ++i) c += flags[i] ? 1 : 0;
     int total;
     int p1 = block_exclusive_scan_1024(c, wtot, &total);
     int p0 = b - p1;
-    for (int i = b; i < e; ++i) {
+    if (b < e) {
+        if (f0) dst1[p1++] = m0;
+        else if (dst0) {
+            if (idx0) idx0[p0] = m0.featureIndex; // the work list of the outlier re-prediction (EKF.cpp:473)
+            dst0[p0++] = m0;
+        }
+    }
+    for (int i = b + 1; i < e; ++i) {
         if (flags[i]) dst1[p1++] = src[i];
         else if (dst0) {
-            if (idx0) idx0[p0] = src[i].featureIndex; // the work list of the outlier re-prediction (EKF.cpp:473)
+            if (idx0) idx0[p0] = src[i].featureIndex;
             dst0[p0++] = src[i];
         }
     }
@@ -280,16 +326,31 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
     if (publish_seq > 0) publish_counts_block(counts, mirror, publish_seq); // the count above is part of the block
     if (!times_matched) return;
     // updateMapFeatures for the selected matches (MapManagement.cpp:88-113), fused: timesMatched++ and the map descriptor
-    // replaced by the matched keypoint's (matcher mode B has no keypoint: keypointIndex < 0)
-    __syncthreads();
-    const int count = total;
-    for (int i = tid; i < count; i += 1024) {
-        const int fi = dst1[i].featureIndex, kp = dst1[i].keypointIndex;
+    // replaced by the matched keypoint's (matcher mode B has no keypoint: keypointIndex < 0); every thread for the matches it
+    // selected itself
+    for (int i = b; i < e; ++i) {
+        if (!(i == b ? f0 : (int)flags[i])) continue;
+        const int fi = i == b ? m0.featureIndex : src[i].featureIndex, kp = i == b ? m0.keypointIndex : src[i].keypointIndex;
         atomicAdd(&times_matched[fi], 1u); // one match per feature on every engine path; atomic all the same
         if (kp >= 0 && kdesc) {
             const uint32_t *sd = (const uint32_t *)(kdesc + (size_t)kp * desc_bytes);
             uint32_t *dd = (uint32_t *)(feat_desc + (size_t)fi * desc_bytes);
-            for (int w = 0; w < desc_bytes / 4; ++w) dd[w] = sd[w];
+            if (desc_bytes % 64 == 0 || desc_bytes == 32) {
+                // the keypoints' descriptors and the map's are different tables, but word by word the compiler must keep every load
+                // behind the store before it: eight dependent round trips for a 32-byte descriptor.  Up to 64 bytes are requested
+                // together as 16-byte loads, then stored (hipMalloc'ed tables, rows of a multiple of 16 bytes: aligned).
+                for (int o = 0; o < desc_bytes; o += 64) {
+                    uint4 v[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (o + 16 * q < desc_bytes) v[q] = *(const uint4 *)((const uint8_t *)sd + o + 16 * q);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (o + 16 * q < desc_bytes) *(uint4 *)((uint8_t *)dd + o + 16 * q) = v[q];
+                }
+            } else {
+                for (int w = 0; w < desc_bytes / 4; ++w) dd[w] = sd[w];
+            }
         }
     }
 }

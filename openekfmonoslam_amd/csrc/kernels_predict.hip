@@ -211,8 +211,15 @@ predict_features_body(const int bx, const double *st, const CamD &cam, const dou
         double fp[6];
         for (int i = 0; i < 6; ++i) fp[i] = feat_pos[6 * fi + i];
         const int type = feat_type[fi];
+        // sin / cos of an inverse-depth feature's angles once, for the projection and for the Jacobian blocks (device_math.h)
+        AngleTrig tg = {0.0, 0.0, 0.0, 0.0};
+        double m[3] = {0.0, 0.0, 0.0};
+        if (type == EKF_FEATURE_INVERSE_DEPTH) {
+            tg = angle_trig(fp[3], fp[4]);
+            dir_vec_t(tg, m);
+        }
         double uv[2];
-        ok = predict_pixel(cam, x, Rt, Rinv, fp, type, uv);
+        ok = predict_pixel_m(cam, x, Rt, Rinv, fp, type, m, uv);
         flag[w] = ok ? 1 : 0;
         vis[fi] = ok ? 1 : 0;
         // the list of unseen features the map management consumes is the one of the step's FULL prediction (EKF.cpp:277-284);
@@ -223,7 +230,7 @@ predict_features_body(const int bx, const double *st, const CamD &cam, const dou
             uv_tab[2 * fi + 1] = uv[1];
             if (Hs_tab) {
                 double Hs[14], Hf[12];
-                measurement_jacobians(cam, x, Rinv, fp, type, uv, Hs, Hf);
+                measurement_jacobians(cam, x, Rinv, fp, type, uv, tg, m, Hs, Hf);
                 for (int i = 0; i < 14; ++i) Hs_tab[14 * fi + i] = Hs[i];
                 for (int i = 0; i < 12; ++i) Hf_tab[12 * fi + i] = Hf[i];
             }

@@ -5,7 +5,8 @@
 // Update.cpp:105 via updateOnlyState).  Here the H_i P row pairs cached by k_hp_rows ARE those gain columns
 // (P symmetric), so a hypothesis costs no pass over P at all: one workgroup per hypothesis forms
 // dx = (H_i P)' inv(S_i) nu_i, applies it with the reference's dead-band to a private copy of the camera state and
-// to every feature, re-projects all N features and counts the matches inside the pixel threshold.  A batch of
+// to every matched feature (from the per-match records of engine.h: RansacRec), re-projects them and counts the matches inside
+// the pixel threshold.  A batch of
 // hypotheses runs in one launch; a single small block then replays the reference's sequential bookkeeping
 // (strict improvement, adaptive hypothesis bound) in hypothesis order, so the winner equals the sequential loop's.
 #include "engine.h"
@@ -14,12 +15,33 @@ namespace ekf {
 
 constexpr int HYP_THREADS = 512;  // threads of a hypothesis' workgroup
 
+// One item of the support loop: match k's record, whether k is the first match of its feature (only that one can add support,
+// 1PointRansac.cpp:60-82) and the feature's own entries of the two gain rows -- everything a thread needs from memory, requested
+// together: record, then (index, gains), then arithmetic only.
+template <typename T>
+struct HypItem {
+    RansacRec r;
+    double ga[6], gb[6];
+    bool live;
+    __device__ __forceinline__ void fetch(const RansacRec *rec, const int *match_of_feat, const T *g0, const T *g1, int k)
+    {
+        r = rec[k];
+        live = r.f >= 0 && match_of_feat[r.f] == k;
+        const int d = feat_dim(r.type);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            const bool use = live && a < d;
+            ga[a] = use ? (double)g0[r.pos + a] : 0.0;
+            gb[a] = use ? (double)g1[r.pos + a] : 0.0;
+        }
+    }
+};
+
 template <typename T>
 __global__ void __launch_bounds__(HYP_THREADS)
-k_ransac_hyp(const double *st, CamD cam, double thr, const double *feat_pos, const int *feat_type,
-             const int *feat_covpos, int N, const T *HP, int ld, const double *uv_tab, const double *S_tab,
-             const EkfMatch *matches, int M, const int *match_of_feat, int h0, int *hyp_count, uint8_t *hyp_flags,
-             int mcap, const int *d_M, int h_lo, int h_hi)
+k_ransac_hyp(const double *st, CamD cam, double thr, const RansacRec *rec, const T *HP, int ld, const double *uv_tab,
+             const double *S_tab, const EkfMatch *matches, int M, const int *match_of_feat, int h0, int *hyp_count,
+             uint8_t *hyp_flags, int mcap, const int *d_M, int h_lo, int h_hi)
 {
     __shared__ double sx[13], sRt[9], sRinv[9], sw[2];
     __shared__ int s_cnt[HYP_THREADS / 64];
@@ -30,61 +52,79 @@ k_ransac_hyp(const double *st, CamD cam, double thr, const double *feat_pos, con
     // columns) it holds; the others' support counts and masks arrive by an all-gather (engine.cpp: ransac_dev)
     if (h < h_lo || h >= h_hi) return;
     const int tid = threadIdx.x;
+    const int nthr = blockDim.x; // 256 for small maps, HYP_THREADS otherwise
     const int fi = matches[h].featureIndex;
     const T *g0 = HP + (size_t)(2 * fi) * ld;
     const T *g1 = g0 + ld;
-    if (tid == 0) {
-        // S = H (P H') + R with R = I * pixelErrorX (Update.cpp:95-107); S_tab holds H P H' + I
-        double S[4] = {S_tab[4 * fi] - 1.0 + cam.pixelErrorX, S_tab[4 * fi + 1], S_tab[4 * fi + 2],
-                       S_tab[4 * fi + 3] - 1.0 + cam.pixelErrorX};
-        double Si[4];
-        inv2(S, Si);
-        const double ax = matches[h].imagePos[0] - uv_tab[2 * fi];
-        const double ay = matches[h].imagePos[1] - uv_tab[2 * fi + 1];
-        const double n0 = fabs(ax) > EKF_DELTA ? ax : 0.0; // Update.cpp:133-134
-        const double n1 = fabs(ay) > EKF_DELTA ? ay : 0.0;
-        const double w0 = Si[0] * n0 + Si[1] * n1;
-        const double w1 = Si[2] * n0 + Si[3] * n1;
-        sw[0] = w0;
-        sw[1] = w1;
-        double x[13];
-        for (int i = 0; i < 13; ++i) {
-            const double dx = (double)g0[i] * w0 + (double)g1[i] * w1;
-            x[i] = st[ST_X + i] + (fabs(dx) > EKF_DELTA ? dx : 0.0); // Update.cpp:150-186
-            sx[i] = x[i];
+    // the first item's loads do not depend on the hypothesis' state: they fly while the first wavefront forms it
+    HypItem<T> it;
+    int k = tid;
+    if (k < M) it.fetch(rec, match_of_feat, g0, g1, k);
+    if (tid < 64) {
+        // lanes 0..12: the camera entries of the two gain rows and of the state, requested before the weights are known
+        const int i = tid < 13 ? tid : 0;
+        const double gi0 = (double)g0[i], gi1 = (double)g1[i], xi = st[ST_X + i];
+        double w0 = 0.0, w1 = 0.0;
+        if (tid == 0) {
+            // S = H (P H') + R with R = I * pixelErrorX (Update.cpp:95-107); S_tab holds H P H' + I
+            double S[4] = {S_tab[4 * fi] - 1.0 + cam.pixelErrorX, S_tab[4 * fi + 1], S_tab[4 * fi + 2],
+                           S_tab[4 * fi + 3] - 1.0 + cam.pixelErrorX};
+            double Si[4];
+            inv2(S, Si);
+            const double ax = matches[h].imagePos[0] - uv_tab[2 * fi];
+            const double ay = matches[h].imagePos[1] - uv_tab[2 * fi + 1];
+            const double n0 = fabs(ax) > EKF_DELTA ? ax : 0.0; // Update.cpp:133-134
+            const double n1 = fabs(ay) > EKF_DELTA ? ay : 0.0;
+            w0 = Si[0] * n0 + Si[1] * n1;
+            w1 = Si[2] * n0 + Si[3] * n1;
+            sw[0] = w0;
+            sw[1] = w1;
         }
-        double R[9];
-        quat_to_rot(x + 3, R); // setOrientation without normalising, Update.cpp:168
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) sRt[j * 3 + i] = R[i * 3 + j];
-        inv3(R, sRinv);
+        w0 = __shfl(w0, 0, 64);
+        w1 = __shfl(w1, 0, 64);
+        const double dx = gi0 * w0 + gi1 * w1;
+        const double x = xi + (fabs(dx) > EKF_DELTA ? dx : 0.0); // Update.cpp:150-186
+        if (tid < 13) sx[tid] = x;
+        double q[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) q[a] = __shfl(x, 3 + a, 64);
+        if (tid == 0) {
+            double R[9];
+            quat_to_rot(q, R); // setOrientation without normalising, Update.cpp:168
+            for (int i2 = 0; i2 < 3; ++i2)
+                for (int j = 0; j < 3; ++j) sRt[j * 3 + i2] = R[i2 * 3 + j];
+            inv3(R, sRinv);
+        }
     }
     __syncthreads();
     const double w0 = sw[0], w1 = sw[1];
-    uint8_t *flags = hyp_flags + (size_t)blockIdx.x * mcap;
-    const int nthr = blockDim.x; // 256 for small maps, HYP_THREADS otherwise
-    for (int k = tid; k < M; k += nthr) flags[k] = 0; // this hypothesis' support mask (only matched features are written below)
-    __syncthreads();
-    int cnt = 0;
-    for (int f = tid; f < N; f += nthr) { // the loop body is a chain of dependent loads: few iterations per thread (1024 threads would spill)
-        const int mi = match_of_feat[f];
-        if (mi >= M) continue; // features without a match cannot add support (1PointRansac.cpp:60-82)
-        const int type = feat_type[f], pos = feat_covpos[f], d = feat_dim(type);
+    uint8_t *flags = hyp_flags + (size_t)blockIdx.x * mcap; // this hypothesis' support mask: every entry k < M is written once below
+    // does this hypothesis support the item's match?
+    auto supports = [&](const HypItem<T> &it) {
+        if (!it.live) return 0;
+        const int type = it.r.type, d = feat_dim(type);
         double fp[6];
-        for (int a = 0; a < 6; ++a) fp[a] = feat_pos[6 * f + a];
-        for (int a = 0; a < d; ++a) {
-            const double dx = (double)g0[pos + a] * w0 + (double)g1[pos + a] * w1;
-            if (fabs(dx) > EKF_DELTA) fp[a] += dx; // Update.cpp:190-204
-        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) fp[a] = it.r.fp[a];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+            if (a < d) {
+                const double dx = it.ga[a] * w0 + it.gb[a] * w1;
+                if (fabs(dx) > EKF_DELTA) fp[a] += dx; // Update.cpp:190-204
+            }
         double uv[2];
-        int ok = 0;
-        if (predict_pixel(cam, sx, sRt, sRinv, fp, type, uv)) {
-            const double xd = matches[mi].imagePos[0] - uv[0];
-            const double yd = matches[mi].imagePos[1] - uv[1];
-            ok = sqrt(xd * xd + yd * yd) < thr ? 1 : 0;
-        }
-        flags[mi] = (uint8_t)ok;
+        if (!predict_pixel(cam, sx, sRt, sRinv, fp, type, uv)) return 0;
+        const double xd = it.r.img[0] - uv[0];
+        const double yd = it.r.img[1] - uv[1];
+        return sqrt(xd * xd + yd * yd) < thr ? 1 : 0;
+    };
+    int cnt = 0;
+    while (k < M) {
+        const int ok = supports(it);
+        flags[k] = (uint8_t)ok;
         cnt += ok;
+        k += nthr;
+        if (k < M) it.fetch(rec, match_of_feat, g0, g1, k);
     }
     cnt = wave_sum_i(cnt);
     if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
@@ -167,17 +207,17 @@ void launch_ransac_init(EkfEngine *e, int M)
 // the hypotheses [h0, h0 + batch) restricted to [h_lo, h_hi) (whole batch: 0, INT_MAX)
 void launch_ransac_hyp(EkfEngine *e, int M, int h0, int batch, const int *d_M, int h_lo, int h_hi)
 {
-    const int nb = batch; // hyp_flags rows are zeroed by their workgroups, hyp_count[b] is only read for launched hypotheses
+    const int nb = batch; // hyp_flags rows are written whole by their workgroups, hyp_count[b] is only read for launched hypotheses
     const double thr = e->cfg.par.ransacThresholdPredictDistance;
     if (e->f32 && !e->exact) // (EKF_PRECISION_F32_EXACT keeps H P in fp64)
-        k_ransac_hyp<float><<<nb, e->N > 256 ? HYP_THREADS : 256, 0, e->stream>>>(e->d.state, e->cam, thr, e->d.feat_pos, e->d.feat_type,
-                                                       e->d.feat_covpos, e->N, (const float *)e->d.HP, e->ldP,
+        k_ransac_hyp<float><<<nb, e->N > 256 ? HYP_THREADS : 256, 0, e->stream>>>(e->d.state, e->cam, thr, e->d.ransac_rec,
+                                                       (const float *)e->d.HP, e->ldP,
                                                        e->d.pred_uv, e->d.pred_S, e->d.matches, M,
                                                        e->d.match_of_feat, h0, e->d.hyp_count, e->d.hyp_flags,
                                                        e->mcap, d_M, h_lo, h_hi);
     else
-        k_ransac_hyp<double><<<nb, e->N > 256 ? HYP_THREADS : 256, 0, e->stream>>>(e->d.state, e->cam, thr, e->d.feat_pos, e->d.feat_type,
-                                                        e->d.feat_covpos, e->N, (const double *)e->d.HP, e->ldP,
+        k_ransac_hyp<double><<<nb, e->N > 256 ? HYP_THREADS : 256, 0, e->stream>>>(e->d.state, e->cam, thr, e->d.ransac_rec,
+                                                        (const double *)e->d.HP, e->ldP,
                                                         e->d.pred_uv, e->d.pred_S, e->d.matches, M,
                                                         e->d.match_of_feat, h0, e->d.hyp_count, e->d.hyp_flags,
                                                         e->mcap, d_M, h_lo, h_hi);

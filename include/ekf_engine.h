@@ -231,6 +231,42 @@ int ekf_fuse_camera_position(EkfEngine *e, const double r[3], const double R[9],
 int ekf_fuse_feature_distance(EkfEngine *e, int feat_i, int feat_j, double distance, double sigma, double gate_nis,
                               EkfExternalUpdate *out);
 
+/* Localisation on a fixed map: the Schmidt-Kalman ("consider") update.  The gain rows of the map states are
+ * zero; the map still enters S = H P H' + R with its full uncertainty and its correlations, and only the camera state and the
+ * camera's rows and columns of P move.  With B = inv(L) H P, B_c its first 13 columns and z = inv(L) nu:
+ *     x[0:13]   += B_c' z   (dead-band EKF_DELTA per component, then the quaternion is normalised)
+ *     P[0:13,:] <- (0.5 P + 0.5 P')[0:13,:] - B_c' B,   P[:,0:13] = its transpose,   then normalizeCovariance on rows / columns 3..6
+ * -- the camera strip of the full update and nothing else: P stays a valid joint covariance, never smaller than the full update's
+ * result, and mapping can resume from it.  P[13:,13:], the feature parameters, their types and the layout are not written at all
+ * (an uploaded asymmetric map block stays asymmetric and is still symmetrised by the next full update).  The n x n x m downdate
+ * is not launched: what is left behind the Cholesky sweep is a 13 x n strip (above 2048 measurement rows, and on maps of 8192 state
+ * columns or more, B is not formed either: the inverse of L and two m x 13 tables).  fp64 arithmetic in every supported configuration; P
+ * is rounded to its storage type after the downdate and after the normalisation, as by ekf_update_external; the 13 x 13 block is
+ * bitwise symmetric afterwards and P[j][i] == P[i][j] bitwise for i < 13.
+ *
+ * ekf_update_fixed_map is the stage, whatever the mode: arguments, validation, preconditions (one match per featureIndex, the
+ * predictions of the last full ekf_predict_measurements) and failure as ekf_update -- S not positive definite returns
+ * EKF_ERR_NOT_POSITIVE_DEFINITE with nothing changed, a timed-out persistent sweep is run again on the launch-per-panel sweep;
+ * S, L, nu, z and therefore the consistency record (stage 0 here, 1 or 2 inside a step) are those of ekf_update on the same
+ * inputs.  The tables of the last prediction are left as after ekf_update.  ekf_set_update_path and ekf_set_sweep_mode reach it.
+ *
+ * ekf_set_fixed_map with on != 0 turns BOTH covariance updates inside ekf_step, ekf_step_frame, ekf_step_image and
+ * ekf_step_staged_image into fixed-map updates.  Prediction, matching, RANSAC (its hypotheses keep the full gain: selection is
+ * unchanged), the rescue and the bookkeeping of the map features (descriptors, timesPredicted, timesMatched) run as always; a step
+ * gains no read-back and no allocation, ekf_set_async_errors, ekf_set_consistency and ekf_set_measurement_budget work unchanged.
+ * The mode can be switched between frames; off is the engine without it, bit for bit.  NOT affected by the mode: ekf_update,
+ * ekf_update_only_state, ekf_update_external with its two helpers, and map management (add, remove, convert) -- a caller who
+ * fuses a position fix or adds features while the mode is on moves the map and should know it.
+ *
+ * EKF_ERR_INVALID_ARG with nothing changed, for the stage and for the setter with on != 0: a sharded engine, and
+ * EKF_PRECISION_F32 (the fast configuration: its fp32 rows of B with the fp64 repair of the camera rows are a separate design;
+ * AUTO never resolves to it).  The first use allocates 256 bytes of scratch per measurement row of the engine's capacity.
+ * ekf_get_fixed_map: the mode, and the fixed-map updates applied since the engine was created (counted on the device; asking
+ * for it synchronises the stream); either pointer may be NULL. */
+int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M);
+int ekf_set_fixed_map(EkfEngine *e, int on);
+int ekf_get_fixed_map(const EkfEngine *e, int *on, int64_t *updates);
+
 /* -- stages ---------------------------------------------------------------------------------------------- */
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);

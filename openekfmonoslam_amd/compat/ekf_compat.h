@@ -722,6 +722,23 @@ inline void update(State &state, Matd &covariance, const VectorFeatureMatch &mea
     c.changed(state, &covariance);
 }
 
+// update() on a fixed map (ekf_update_fixed_map; no counterpart in the reference): the Schmidt-Kalman update -- the
+// camera state and the camera's rows and columns of the covariance move, the map features and the map block of the covariance keep
+// their bits.  Same arguments and preconditions as update().
+inline void updateFixedMap(State &state, Matd &covariance, const VectorFeatureMatch &measurementMatchedFeatures,
+                           const VectorImageFeaturePrediction &predictedDistortedFeatures, const VectorMatd &predictedFeatureJacobians)
+{
+    (void)predictedFeatureJacobians;
+    if (measurementMatchedFeatures.empty()) return;
+    ekf_compat::Context &c = ekf_compat::Context::instance();
+    c.ensure(state, &covariance);
+    EkfEngine *e = c.engine();
+    ekf_compat::refreshTables(e, predictedDistortedFeatures);
+    std::vector<EkfMatch> m = ekf_compat::packMatches(measurementMatchedFeatures);
+    c.check(ekf_update_fixed_map(e, m.data(), (int)m.size()), "ekf_update_fixed_map");
+    c.changed(state, &covariance);
+}
+
 inline void updateOnlyState(const VectorImageFeaturePrediction &predictedDistortedFeatures, const VectorFeatureMatch &measurementMatchedFeatures,
                             const VectorMatd &predictedFeatureJacobians, State &state, Matd &covariance)
 {

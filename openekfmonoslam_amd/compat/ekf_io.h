@@ -560,7 +560,7 @@ public:
     ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
-          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0)
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -603,6 +603,7 @@ public:
         if (log_.is_open()) {
             log_ << std::endl << std::endl;
             log_ << "~~~~~~~~~~~~ STEP " << steps_ << " ~~~~~~~~~~~~" << std::endl;
+            if (fixedMap_) log_ << "Fixed map: on" << std::endl;
         }
         EkfStepInfo info;
         if (out_.isOpened()) ekf_timing_reset(e_);
@@ -615,8 +616,8 @@ public:
         }
         const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
         const int inliers = info.n_inliers + info.n_rescued;
-        // EKF.cpp:574-612 (updateMapFeatures already ran inside the step)
-        if (run_.mapManagementFrequency > 0 && steps_ % run_.mapManagementFrequency == 0) {
+        // EKF.cpp:574-612 (updateMapFeatures already ran inside the step); a fixed map is not managed: nothing removed, converted or added
+        if (!fixedMap_ && run_.mapManagementFrequency > 0 && steps_ % run_.mapManagementFrequency == 0) {
             const int needed = run_.minMatchesPerImage - inliers;
             const int N = ekf_num_features(e_);
             std::vector<uint8_t> drop(N, 0);
@@ -714,6 +715,18 @@ public:
         out.resize((size_t)n);
         if (n > 0) chk(ekf_get_measurement_ranks(e_, out.data(), n, &n), "ekf_get_measurement_ranks");
     }
+    // Localisation on a fixed map (ekf_set_fixed_map): while on, both updates of a step move the camera state and the
+    // camera's rows and columns of P alone (the Schmidt-Kalman update), and step() skips the whole map-management block -- nothing
+    // is removed, converted or added -- so the number of features and their parameters stay as they are; at any time, it takes
+    // effect with the next step, and mapping resumes from the same P when it is switched off.  With the mode on log.txt gains one
+    // line per step, "Fixed map: on"; output.yml does not change.  updateExternal and the two fuse helpers are NOT affected: a
+    // position fix fused while the mode is on still moves the map.  Throws in EKF_PRECISION_F32 (the fast configuration).
+    void setFixedMap(bool on)
+    {
+        chk(ekf_set_fixed_map(e_, on ? 1 : 0), "ekf_set_fixed_map");
+        fixedMap_ = on;
+    }
+    bool fixedMap() const { return fixedMap_; }
     // External measurements between steps (ekf_update_external and its helpers): H by rows in CSR form over state
     // indices; a fix of the camera position; a measured distance between two map features.  They return the record (NIS, whitened
     // residual, applied) and throw on an error code.  output.yml and log.txt do not change.
@@ -841,6 +854,7 @@ private:
     bool keypoints_; // EKF_IMAGE_MATCHER_KEYPOINTS: new features keep a BRIEF-32 descriptor, no templates
     bool patchNormals_; // setPatchNormals(true): writeMapPly adds the normals
     int budget_;        // setMeasurementBudget(K)
+    bool fixedMap_;     // setFixedMap(on)
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

@@ -1335,7 +1335,7 @@ static int lean_gather_exchange(EkfEngine *e, int M)
 }
 
 // update with the matches in e->d.msel[0..M); lean: see lean_gather_exchange
-static int update_dev(EkfEngine *e, int M, bool update_cov, bool lean = false)
+static int update_dev(EkfEngine *e, int M, int kind, bool lean = false)
 {
     if (M <= 0) return EKF_OK; // Update.cpp:292
     lean = lean && e->shard_world > 1 && !e->hp_complete;
@@ -1353,7 +1353,7 @@ static int update_dev(EkfEngine *e, int M, bool update_cov, bool lean = false)
     EkfMatch *save = e->d.matches;
     e->d.matches = e->d.msel;
     e->after_gather = lean ? lean_gather_exchange : nullptr;
-    launch_update(e, M, update_cov);
+    launch_update(e, M, kind);
     e->after_gather = nullptr;
     e->d.matches = save;
     if (e->hook_rc) return e->hook_rc;
@@ -1382,7 +1382,7 @@ static int recover_failed_update(EkfEngine *e, int *status)
         e->ps_ok_streak = 0;
         ++e->force_launches;
         e->cons_stage = e->last_update_stage; // (filter consistency: the retry records the stage of the update it repeats)
-        int rc = update_dev(e, e->last_update_M, e->last_update_cov, false);
+        int rc = update_dev(e, e->last_update_M, e->last_update_kind, false);
         --e->force_launches;
         ++e->sweep_retries;
         if (rc) return rc;
@@ -1422,7 +1422,7 @@ int ekf_update(EkfEngine *e, const EkfMatch *matches, int M)
     if ((rc = complete_hp_table(e))) return rc;
     if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
     e->cons_stage = 0;
-    rc = update_dev(e, M, true);
+    rc = update_dev(e, M, UPDATE_COV);
     if (rc) return rc;
     return finish_update(e);
 }
@@ -1436,9 +1436,84 @@ int ekf_update_only_state(EkfEngine *e, const EkfMatch *matches, int M)
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     if ((rc = complete_hp_table(e))) return rc;
-    rc = update_dev(e, M, false);
+    rc = update_dev(e, M, UPDATE_STATE_ONLY);
     if (rc) return rc;
     return finish_update(e);
+}
+
+// ------------------------------------------------------------------------------ fixed map
+// why the fixed-map update is not available on this engine, or null
+static const char *fixed_map_refusal(const EkfEngine *e)
+{
+    if (e->shard_world > 1) return "not available on a sharded engine";
+    if (e->f32 && !e->exact) return "not available in EKF_PRECISION_F32";
+    return nullptr;
+}
+
+// the mode's scratch, on its first use: the control block and the two m x 13 gain tables of updates above B_SWEEP_MAX rows (the
+// partial sums of the strip share d.cam_part with the fast fp32 configuration's repair, which the mode refuses)
+static int fixed_map_scratch(EkfEngine *e)
+{
+    if (e->d.fm_ctl) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    e->fm_rows = round_up(e->mcap, 128) + 128;
+    auto g = e->bufs.group();
+    g.alloc(&e->d.fm_ctl, 1);
+    g.alloc(&e->d.fm_gain, (size_t)2 * e->fm_rows * FM_LD);
+    if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "fixed-map update scratch");
+    return EKF_OK;
+}
+
+int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (const char *why = fixed_map_refusal(e)) {
+        e->err = std::string("ekf_update_fixed_map: ") + why;
+        return EKF_ERR_INVALID_ARG;
+    }
+    int rc = validate_matches(e, matches, M);
+    if (rc) return rc;
+    if (M == 0) return EKF_OK;
+    if ((rc = fixed_map_scratch(e))) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
+    if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
+    e->cons_stage = 0;
+    rc = update_dev(e, M, UPDATE_FIXED_MAP);
+    if (rc) return rc;
+    return finish_update(e);
+}
+
+int ekf_set_fixed_map(EkfEngine *e, int on)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (on) {
+        if (const char *why = fixed_map_refusal(e)) {
+            e->err = std::string("ekf_set_fixed_map: ") + why;
+            return EKF_ERR_INVALID_ARG;
+        }
+        int rc = fixed_map_scratch(e);
+        if (rc) return rc;
+    }
+    e->fixed_map = on != 0;
+    return EKF_OK;
+}
+
+int ekf_get_fixed_map(const EkfEngine *e, int *on, int64_t *updates)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (on) *on = e->fixed_map ? 1 : 0;
+    if (updates) {
+        *updates = 0;
+        if (e->d.fm_ctl) { // (never allocated: no fixed-map update ran)
+            long long v = 0;
+            if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
+                hipMemcpy(&v, &e->d.fm_ctl->updates, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return EKF_ERR_HIP;
+            *updates = (int64_t)v;
+        }
+    }
+    return EKF_OK;
 }
 
 // ------------------------------------------------------------------------- external measurements
@@ -1693,6 +1768,7 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
     const bool budget_active = e->budget_K > 0 && e->budget_K < e->N; // measurement budget: with K >= N it cannot bind
     const bool dev_counts = !use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1 && !budget_active;
     const bool lean = e->shard_world > 1; // sharded: rows of H.P travel when consumed, not after every prediction
+    const int step_kind = e->fixed_map ? UPDATE_FIXED_MAP : UPDATE_COV; // ekf_set_fixed_map: both updates move the camera alone
     int *cnt = e->d.counts;
     EkfStepInfo li;
     std::memset(&li, 0, sizeof(li));
@@ -1779,7 +1855,7 @@ restart:
     tm.mark();
     // 7. low-innovation update (:430)
     e->cons_stage = 1;
-    if ((rc = update_dev(e, ni, true, lean))) return rc;
+    if ((rc = update_dev(e, ni, step_kind, lean))) return rc;
     tm.mark();
     // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
     // (EKF.cpp:552-556).  An outlier that is not re-predicted has pred_vis = 0 and is not rescued.
@@ -1818,7 +1894,7 @@ restart:
         HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     // 10. high-innovation update (:529-532)
     e->cons_stage = 2;
-    if ((rc = update_dev(e, nr, true, lean))) return rc;
+    if ((rc = update_dev(e, nr, step_kind, lean))) return rc;
     tm.mark();
     if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
     if (dev_counts && e->async_errors) {

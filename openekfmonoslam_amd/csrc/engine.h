@@ -106,6 +106,14 @@ struct ExtResult {
     int verdict, pad;
 };
 
+// fixed-map update: x_save is written by the strip kernel for the tail, whose workgroups each need the camera state
+// as it was while one of them rewrites it; updates is incremented by the tail of every update that was applied
+constexpr int FM_LD = 16; // leading dimension of the m x 13 tables B_c and K_c'
+struct FmCtl {
+    double x_save[13];
+    long long updates;
+};
+
 // 1-point RANSAC: what a hypothesis needs of one match, gathered once per frame by the launch that writes the feature -> match index
 // (k_match_compact on the step path, k_match_index behind an arbitrary list) so that the hypotheses' workgroups read ONE contiguous
 // record per match instead of chasing match -> feature -> type / position / parameters through four tables each
@@ -204,7 +212,8 @@ struct DeviceArrays {
     double *dx_part = nullptr; // DX_SPLIT x ldP (+ 4: the quaternion as it was before the update)
     double *sq_part = nullptr; // DX_SPLIT x ldP: partial sums of squares of the columns of B (fp64 diagonal of B'B)
     double *diag_save = nullptr; // ldP: diagonal of P before a downdate
-    double *cam_part = nullptr;  // DX_SPLIT x 13 x ldP: partial sums of the camera rows of B'B (fp64)
+    double *cam_part = nullptr;  // DX_SPLIT x 13 x ldP: partial sums of the camera rows of B'B (fp64): the fast fp32 configuration's repair,
+                                 // and the fixed-map update's strip (never both: that configuration refuses the fixed-map update)
     double *cam_save = nullptr;  // 13 x ldP: camera rows of P before a downdate
     double *HPc = nullptr;       // [2 cap x 16]: fp64 camera columns of the H P rows
     double *Gc = nullptr;        // [(mcap + slack) x 16]: those of the gathered rows (working right-hand sides of the sweep)
@@ -229,6 +238,9 @@ struct DeviceArrays {
     double *ext_sel = nullptr;    // EXT_ROWS x EXT_ENTRIES: A[i, col_e] for every entry e of H, what S = A H' + R reads
     ExtCtl *ext_ctl = nullptr;
     ExtResult *ext_res = nullptr;
+    // fixed-map update (ekf_update_fixed_map / ekf_set_fixed_map; one group, allocated by the first use)
+    FmCtl *fm_ctl = nullptr;      // the camera state as it was before the update, and the count of updates applied
+    double *fm_gain = nullptr;    // 2 x [mw x FM_LD]: B_c = inv(L) G[:, 0:13] and K_c' = inv(L)' B_c (updates whose route forms no rows of B)
     ConsCtl *cons_ctl = nullptr;        // filter consistency (ekf_set_consistency; allocated by its first call)
     EkfInnovation *cons_recs = nullptr; // CONS_SLOTS x cap records: the matches of record s from s * cap on, update order
     // measurement budget (ekf_set_measurement_budget; allocated by its first call with K > 0): per slot of the full
@@ -328,7 +340,7 @@ struct EkfEngine {
     // 4096), and 256 persistent sweeps in a row without one forget the history
     int ps_backoff = 0, ps_backoff_len = 0, ps_ok_streak = 0;
     int last_update_M = 0;                // matches of the last update enqueued (its list is still in d.msel)
-    bool last_update_cov = true;          // ... a covariance update (false: updateOnlyState)
+    int last_update_kind = 1;             // ... its kind, ekf::UPDATE_* (a retry runs the same kind again)
     bool last_update_sym = false;         // p_exact_sym as it was before that update
     bool last_update_persist = false;     // that update's sweep was the persistent launch
     int ps_cap[2] = {0, 0};    // resident workgroups of k_chol_persist<false / true> on this device (0: not asked yet, -1: unusable)
@@ -355,6 +367,8 @@ struct EkfEngine {
     double distinct_coef = 0.0;    // ekf_set_ncc_distinct: 0 = off, else an NCC match with a rival peak is kept when d1 < d2 * coef
     int distinct_counts[2] = {0, 0}; // accepted matches with a rival / rejected by the test in the last NCC match
     int rival_slots = 0;           // prediction slots of the last NCC match that ran with the test on (records of d.mt_rival)
+    bool fixed_map = false;        // ekf_set_fixed_map: the covariance updates of the step functions are fixed-map updates
+    int fm_rows = 0;               // rows of each of the two tables in d.fm_gain
     bool consistency = false;      // ekf_set_consistency: every covariance update is followed by k_consistency
     int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
     int cons_stage = 0;            // stage the next covered update records: 0 ekf_update, 1 a step's first update, 2 its second
@@ -529,7 +543,15 @@ void launch_ransac_select(EkfEngine *e, int M, int h0, int batch, const int *d_M
 // publish_seq > 0: the batch's bookkeeping kernel also publishes the counter block (see publish_counts_block)
 void launch_ransac_batch(EkfEngine *e, int M, int h0, int batch, const int *d_M = nullptr, int publish_seq = 0);
 void launch_ransac_init(EkfEngine *e, int M);
-void launch_update(EkfEngine *e, int M, bool update_cov);
+// kind of an update: the state alone (updateOnlyState), state and covariance, or the Schmidt-Kalman update of a fixed map (state
+// and covariance strip of the camera alone)
+enum { UPDATE_STATE_ONLY = 0, UPDATE_COV = 1, UPDATE_FIXED_MAP = 2 };
+void launch_update(EkfEngine *e, int M, int kind);
+// fixed-map update (kernels_fixedmap.hip), fp64 arithmetic, unsharded engines.  _gain: where the route forms no rows of B, behind the inverse of
+// L -- B_c = W' G[:, 0:13] and K_c' = W B_c into d.fm_gain.  _strip: the partial sums of the 13 x n strip Y' X (Y = B[:, 0:13] and
+// X = B, m rows in d.A; or from_gain: Y = K_c' and X = G) into d.cam_part, then the tail: strip downdate, camera state, normalisation
+void launch_fixed_map_gain(EkfEngine *e, int m, const double *G);
+void launch_fixed_map_strip(EkfEngine *e, int m, const double *X, bool from_gain);
 void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready = false, bool planes_ready = false); // kernels_pexact.hip
 void launch_round_P_f32(EkfEngine *e);                        // kernels_map.hip
 void launch_diag_extract(EkfEngine *e, float *diag);          // kernels_pexact.hip: sharded exact configuration

@@ -1739,6 +1739,11 @@ static void inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
         k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 0);
         k_triinv_level<<<npairs * tiles, 256, 0, s>>>(e->d.LL, ldS, m, m_pad, V, W, Wf, e->d.Tbuf, ldw, sz, 1);
     }
+    if (r.fixed_map) {
+        // no m x m x n product: the camera's 13 columns of B = W' G and of the gain K' = W B are all the strip needs
+        launch_fixed_map_gain(e, m, (const double *)rows_of_G<TB>(e, r));
+        return;
+    }
     if (r.gemm_planes) {
         const int c_lo = r.shard_cols ? r.col_rb[e->shard_rank] : 0, c_hi = r.shard_cols ? r.col_rb[e->shard_rank + 1] : n_pad;
         launch_b_gemm_planes(e, m, c_lo, c_hi);
@@ -1767,6 +1772,7 @@ static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
 {
     hipStream_t s = e->stream;
     const int m = r.m, n = r.n, ld = e->ldP;
+    if (r.fixed_map) return true; // dx of the camera alone: formed by the strip's tail (k_fm_tail); k_state_apply must not run
     if (r.shard_cols) {
         // every rank's column blocks of the digit planes to every rank: pack [column][plane][k group], row-block exchange, unpack;
         // dx = B'z then comes from the planes (the fp64 rows of B exist only for the own columns)
@@ -1810,13 +1816,19 @@ static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
 }
 
 // 6. the consistency record, the downdate of P and the covariance tail
-template <typename T, bool EXACT>
+template <typename T, typename TB, bool EXACT>
 static void downdate_and_tail(EkfEngine *e, const UpdateRoute &r)
 {
     hipStream_t s = e->stream;
     const int n = r.n, ld = e->ldP;
     // filter consistency: z is final in d.zvec and the error flag tells whether this sweep failed
-    if (e->consistency && r.update_cov) launch_consistency(e, r.M);
+    if (e->consistency && (r.update_cov || r.fixed_map)) launch_consistency(e, r.M);
+    if (r.fixed_map) {
+        // the camera's strip of P and the camera state (kernels_fixedmap.hip): Y' X with Y = B[:, 0:13], X = B where the sweep formed
+        // the rows of B, Y = K_c', X = G (the gathered rows of H P) where it did not
+        if constexpr (sizeof(TB) == 8) launch_fixed_map_strip(e, r.m, r.b_in_sweep ? (const double *)e->d.A : (const double *)rows_of_G<TB>(e, r), !r.b_in_sweep);
+        return;
+    }
     if (!r.update_cov) return;
     // (column scales: k_gather + k_dx_partial, or a-priori; planes: the sweep's / the GEMM's / the ranks')
     if (EXACT) launch_p_update_exact(e, r.m, false, true, r.planes_b || r.shard_cols || r.gemm_planes);
@@ -1840,10 +1852,10 @@ static void downdate_and_tail(EkfEngine *e, const UpdateRoute &r)
 
 // the route, the two effects it reports (back-off bookkeeping) with what a retry needs, then the launches
 template <typename T, typename TB, bool EXACT = false>
-static void update_impl(EkfEngine *e, int M, bool update_cov)
+static void update_impl(EkfEngine *e, int M, int kind)
 {
     UpdateRouteIn in;
-    in.M = M; in.n = e->n; in.update_cov = update_cov;
+    in.M = M; in.n = e->n; in.update_cov = kind == UPDATE_COV; in.fixed_map = kind == UPDATE_FIXED_MAP;
     in.b_fp32 = sizeof(TB) == 4; in.p_fp32 = sizeof(T) == 4; in.exact = EXACT;
     in.b_path = e->b_path; in.sweep_mode = e->sweep_mode; in.force_launches = e->force_launches > 0; in.ps_backoff = e->ps_backoff > 0;
     in.shard_world = e->shard_world; in.shard_rank = e->shard_rank;
@@ -1872,7 +1884,7 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
     if (r.persist && ++e->ps_ok_streak >= 256) e->ps_backoff_len = 0;
     if (!r.col_rb.empty()) e->last_col_rb = r.col_rb; // (ekf_shard_counters)
     e->last_update_M = M; // what a retry needs (engine.cpp: recover_failed_update)
-    e->last_update_cov = update_cov;
+    e->last_update_kind = kind;
     e->last_update_sym = e->p_exact_sym;
     e->last_update_persist = r.persist;
     e->last_update_stage = e->cons_stage;
@@ -1882,16 +1894,16 @@ static void update_impl(EkfEngine *e, int M, bool update_cov)
     if (!cholesky_sweep<TB, EXACT>(e, r)) return;
     inverse_and_gemm<TB>(e, r);
     if (!dx_and_state<T, TB, EXACT>(e, r)) return;
-    downdate_and_tail<T, EXACT>(e, r);
+    downdate_and_tail<T, TB, EXACT>(e, r);
 }
 
-void launch_update(EkfEngine *e, int M, bool update_cov)
+void launch_update(EkfEngine *e, int M, int kind)
 {
     if (M <= 0) return;
-    if (e->exact && e->f32) update_impl<float, double, true>(e, M, update_cov);
-    else if (e->exact) update_impl<double, double, true>(e, M, update_cov);
-    else if (e->f32) update_impl<float, float>(e, M, update_cov);
-    else update_impl<double, double>(e, M, update_cov);
+    if (e->exact && e->f32) update_impl<float, double, true>(e, M, kind);
+    else if (e->exact) update_impl<double, double, true>(e, M, kind);
+    else if (e->f32) update_impl<float, float>(e, M, kind);
+    else update_impl<double, double>(e, M, kind);
 }
 
 } // namespace ekf

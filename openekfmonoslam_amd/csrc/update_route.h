@@ -25,6 +25,7 @@ struct PsLayout {
 struct UpdateRouteIn {
     int M = 0, n = 0; // matches (two rows each), state columns
     bool update_cov = true;
+    bool fixed_map = false; // Schmidt-Kalman update (ekf_update_fixed_map): the camera's strip of P alone; update_cov is not read
     bool b_fp32 = false; // sizeof(TB) == 4: H P, G and B = inv(L) G in fp32 (the fast fp32 configuration)
     bool p_fp32 = false; // sizeof(T) == 4: P stored in fp32
     bool exact = false;  // EKF_PRECISION_F32_EXACT / _F64_EXACT
@@ -46,6 +47,8 @@ struct UpdateRoute {
     const char *refusal = nullptr; // not null: the update is refused with this message (EKF_ERR_INVALID_ARG), nothing else is set
     int M = 0, n = 0, m = 0, m_pad = 0, n_pad = 0;
     bool update_cov = false, b_fp32 = false;
+    bool fixed_map = false;    // the 13 x n strip of the camera instead of the downdate (kernels_fixedmap.hip); update_cov is false then.
+                               // need_inverse with it: inv(L) is formed but NOT the GEMM -- the camera's gain columns come from W alone
     bool b_in_sweep = false;   // row block k of B = inv(L) G is formed inside the launch of panel k
     bool sharded = false;
     bool shard_cols = false;   // every rank forms its own columns of B
@@ -100,11 +103,29 @@ inline bool persist_layout(int cap, int n_cus, bool sweep_ctl, int m, int n_bcol
 inline UpdateRoute choose_update_route(const UpdateRouteIn &in)
 {
     UpdateRoute r;
+    // fixed map: fp64 rows of B (or of G) in a one-GPU engine -- the fast fp32 configuration's fp32 rows of B with their fp64 repair
+    // of the camera rows, and a row-sharded P, are separate designs
+    if (in.fixed_map && in.shard_world > 1) {
+        r.refusal = "the fixed-map update is not available on a sharded engine";
+        return r;
+    }
+    if (in.fixed_map && in.b_fp32) {
+        r.refusal = "the fixed-map update is not available in EKF_PRECISION_F32";
+        return r;
+    }
+    // the stages in front of the strip are those of a state-only update: nothing of the downdate's machinery (digit planes, a-priori
+    // column scales, the fp64 repair, the merged tail) is chosen
+    const bool update_cov = in.update_cov && !in.fixed_map;
     const int m = 2 * in.M, m_pad = round_up(m, NB), n_pad = round_up(in.n, LD_ALIGN);
     // B = inv(L) G: up to B_SWEEP_MAX rows, row block k is formed inside the launch of panel k (forward substitution beside the
     // look-ahead factorisation: no explicit inverse, no GEMM launch); above it the per-launch row block becomes longer than the
     // factorisation it hides behind, and the explicit inverse + one big-tile GEMM is the better use of the MFMA pipe.
-    const bool b_in_sweep = in.b_path == EKF_UPDATE_PATH_SWEEP || (in.b_path == EKF_UPDATE_PATH_AUTO && m_pad <= B_SWEEP_MAX);
+    // Fixed map: the strip needs the 13 camera columns of the gain, not B.  Below 8192 state columns the rows of B ride behind the
+    // latency-bound chain of the persistent sweep and cost nothing (N = 1000: 0.73 ms per frame against 0.98 through the inverse);
+    // from there on -- where the sweep leaves the persistent launch and the rows of B are its longest role -- the m^2 n flops of B
+    // are the frame, and the inverse with the two m x 13 tables is taken at every size (N = 2000: 2.25 against 3.07 ms)
+    const bool fm_no_b = in.fixed_map && n_pad >= 8192;
+    const bool b_in_sweep = in.b_path == EKF_UPDATE_PATH_SWEEP || (in.b_path == EKF_UPDATE_PATH_AUTO && m_pad <= B_SWEEP_MAX && !fm_no_b);
     if (in.b_fp32 && b_in_sweep && m_pad > B_SWEEP_MAX) {
         // fp32 forward substitution over more than 64 panels changes the filter's decisions (measured at N = 5000, DESIGN.md
         // section 6): the size switch to inverse + GEMM is an accuracy boundary -- EKF_UPDATE_PATH_SWEEP is refused there
@@ -112,9 +133,9 @@ inline UpdateRoute choose_update_route(const UpdateRouteIn &in)
         return r;
     }
     r.M = in.M; r.n = in.n; r.m = m; r.m_pad = m_pad; r.n_pad = n_pad;
-    r.update_cov = in.update_cov; r.b_fp32 = in.b_fp32; r.n_cus = in.n_cus;
+    r.update_cov = update_cov; r.fixed_map = in.fixed_map; r.b_fp32 = in.b_fp32; r.n_cus = in.n_cus;
     r.b_in_sweep = b_in_sweep; r.need_inverse = !b_in_sweep; r.sharded = in.shard_world > 1;
-    const bool exact_cov = in.exact && in.update_cov;
+    const bool exact_cov = in.exact && update_cov;
     r.shard_cols = exact_cov && r.sharded && in.exchange_hook && in.Bstage && m_pad + NB <= in.bstage_rows &&
                    (int)in.n_shard_row_begin == in.shard_world + 1;
     // exact configuration, B in the sweep: its rows are formed from int8 digit planes, in single-panel launches (the planes of L
@@ -131,8 +152,8 @@ inline UpdateRoute choose_update_route(const UpdateRouteIn &in)
     // covariance updates of the exact and the fp64 configuration: the state update waits behind the downdate and shares a launch
     // with the normalisation of the covariance; the fast fp32 configuration keeps its own tail (k_fix_normalize)
     r.fix_diag = in.p_fp32 && !in.exact; // (the exact downdate needs no fp64 repair of the diagonal / camera rows)
-    r.fix = in.update_cov && r.fix_diag;
-    r.merged_tail = in.update_cov && !r.fix_diag;
+    r.fix = update_cov && r.fix_diag;
+    r.merged_tail = update_cov && !r.fix_diag;
     // sharded: this rank forms the column blocks [cb0, cb1) of B -- the blocks whose first column lies in its share of the state
     // rows (rank 0: from column 0) -- and receives the others' digit planes afterwards (the B role divided by the ranks)
     r.cb1 = n_pad / NB;

@@ -108,6 +108,9 @@ ABI = {
     "ekf_update_external": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, C.POINTER(EkfExternalUpdate)]),
     "ekf_fuse_camera_position": (_i, [_vp, _vp, _vp, C.c_double, C.POINTER(EkfExternalUpdate)]),
     "ekf_fuse_feature_distance": (_i, [_vp, _i, _i, C.c_double, C.c_double, C.c_double, C.POINTER(EkfExternalUpdate)]),
+    "ekf_update_fixed_map": (_i, [_vp, _vp, _i]),
+    "ekf_set_fixed_map": (_i, [_vp, _i]),
+    "ekf_get_fixed_map": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
     "ekf_rescue": (_i, [_vp, _vp, _i, _vp]),
     "ekf_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(EkfStepInfo)]),
     "ekf_frames_upload": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -591,6 +594,23 @@ class EkfEngine:
     def update_only_state(self, matches):
         matches = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
         self._chk(self.L.ekf_update_only_state(self.h, _p(matches), len(matches)))
+
+    def update_fixed_map(self, matches, allow_errors=()):
+        """The Schmidt-Kalman update of a fixed map (ekf_update_fixed_map): the camera state and the camera's rows
+        and columns of P move, the map block of P and the features keep their bits.  Arguments and errors as update()."""
+        matches = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        return self._chk(self.L.ekf_update_fixed_map(self.h, _p(matches), len(matches)), allow_errors)
+
+    def set_fixed_map(self, on=True):
+        """on: both covariance updates of every step become fixed-map updates (ekf_set_fixed_map); update(), update_only_state(),
+        update_external() and map management are not affected.  Refused on a sharded engine and in EKF_PRECISION_F32."""
+        self._chk(self.L.ekf_set_fixed_map(self.h, 1 if on else 0))
+
+    def fixed_map(self):
+        """(mode on?, fixed-map updates applied since the engine was created); synchronises the stream"""
+        on, k = _i(0), C.c_int64(0)
+        self._chk(self.L.ekf_get_fixed_map(self.h, C.byref(on), C.byref(k)))
+        return bool(on.value), int(k.value)
 
     def rescue(self, outliers):
         outliers = np.ascontiguousarray(outliers, dtype=MATCH_DTYPE)

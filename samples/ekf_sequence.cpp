@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -19,6 +19,9 @@
 // --position-fixes FILE (likewise): fixes of the camera position from outside the filter (mocap, GPS, odometry), one per line as
 // "frame x y z sigma" (# starts a comment; frame = the number in the step line); after that frame's step the fix is fused with
 // R = sigma^2 I and no gate (ImageEKF::fuseCameraPosition) and its NIS is printed under the step line.
+// --fixed-map-from FRAME (likewise): map as always up to FRAME, then localise -- from the step that prints "step FRAME" on the map
+// is fixed (ImageEKF::setFixedMap): both updates move the camera alone, map management is skipped, "fixed map: on" is printed under
+// the step line; the covariance carries over from the mapping frames as it is.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -58,12 +61,13 @@ int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
-    int budget = 0;
+    int budget = 0, fixedFrom = -1;
     std::string fixesFile;
     for (int i = 1; i < argc; ++i)
-        if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes") &&
-            i + 1 < argc) { // the flag and its value
+        if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes" ||
+             std::string(argv[i]) == "--fixed-map-from") && i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
+            else if (std::string(argv[i]) == "--fixed-map-from") fixedFrom = std::max(std::atoi(argv[i + 1]), 0);
             else if (std::string(argv[i]) == "--position-fixes") fixesFile = argv[i + 1];
             else distinct = std::atof(argv[i + 1]);
             for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
@@ -79,7 +83,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -94,7 +98,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty()) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -112,7 +116,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget or position fixes asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes or a fixed map asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -130,12 +134,14 @@ int main(int argc, const char *argv[])
         std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
         image = generator.getNextImage();
         while (!image.empty()) {
+            if (fixedFrom >= 0 && extendedKalmanFilter.steps() + 1 >= fixedFrom && !extendedKalmanFilter.fixedMap()) extendedKalmanFilter.setFixedMap(true);
             const EkfStepInfo info = extendedKalmanFilter.step(image);
             double x[13];
             ekf_get_state(extendedKalmanFilter.engine(), x, 0, 0);
             std::printf("step %d: predicted %d matches %d li %d hi %d features %d  r = %.6f %.6f %.6f\n", extendedKalmanFilter.steps(),
                         info.n_predicted, info.n_matches, info.n_inliers, info.n_rescued, ekf_num_features(extendedKalmanFilter.engine()),
                         x[0], x[1], x[2]);
+            if (extendedKalmanFilter.fixedMap()) std::printf("        fixed map: on\n");
             for (size_t k = 0; k < fixes.size(); ++k)
                 if (fixes[k].frame == extendedKalmanFilter.steps()) {
                     const double s2 = fixes[k].sigma * fixes[k].sigma, R[9] = {s2, 0, 0, 0, s2, 0, 0, 0, s2};

@@ -22,7 +22,7 @@ using namespace ekf;
 namespace ekf {
 void launch_partition(EkfEngine *e, const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, EkfMatch *dst0,
                       int *cnt1, bool map_update = false, const uint8_t *d_kdesc = nullptr, int *d_idx0 = nullptr,
-                      int publish_seq = 0, bool rescue = false);
+                      int publish_seq = 0, bool rescue = false, const int *d_M = nullptr, bool behind_ransac = false);
 void launch_outlier_idx(EkfEngine *e, const EkfMatch *src, int M, int *idx);
 } // namespace ekf
 
@@ -1783,6 +1783,7 @@ static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_des
         if ((rc = recover_failed_update(e, &status))) return rc;
     }
     bool restarted = false;
+    bool partitioned = false; // the low-innovation partition has run (see the RANSAC stage)
 restart:
     if (e->consistency) ++e->cons_epoch; // filter consistency: the records of this step
     StageTimer tm(e);
@@ -1814,6 +1815,13 @@ restart:
         const int batch = e->cfg.ransac_batch;
         const int seq_r = next_publish_seq(e);
         launch_ransac_batch(e, e->N, 0, batch, cnt + CNT_NMATCH, seq_r);
+        // The partition behind the loop is enqueued before the host polls for the batch's outcome, so the GPU does not wait for the
+        // host between the two: sized by N, it reads the match count on the device and does nothing unless this batch ended the loop
+        // and the filter is not frozen (k_partition: behind_ransac) -- the restart below sees no side effect.
+        const bool early = e->N > 0;
+        if (early)
+            launch_partition(e, e->d.matches, e->N, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx, 0, false,
+                             cnt + CNT_NMATCH, true);
         if ((rc = wait_counts(e, seq_r))) return rc;
         if (e->h_counts[CNT_ERR] && !restarted) {
             // the previous step's last update failed and its final read-back was skipped: this step's prediction did not touch
@@ -1824,6 +1832,7 @@ restart:
         }
         np = e->n_pred = e->h_counts[CNT_NPRED];
         M = e->h_counts[CNT_NMATCH];
+        partitioned = early && e->h_counts[CNT_RS_DONE] && !e->h_counts[CNT_ERR]; // what the early launch saw (same counter block)
         for (int h0 = batch, nb = batch * RANSAC_WIDE_FACTOR; !e->h_counts[CNT_RS_DONE] && h0 < M; h0 += nb) {
             launch_ransac_batch(e, M, h0, nb); // (wide batches behind the first: see ransac_dev)
             if ((rc = read_counts(e))) return rc;
@@ -1843,7 +1852,8 @@ restart:
         ni = e->h_counts[CNT_RS_BEST];
         no = M - ni;
         // + updateMapFeatures for the low-innovation inliers (MapManagement.cpp:88-113), same launch
-        launch_partition(e, e->d.matches, M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx);
+        // (device-count step whose first batch ended the loop: the launch enqueued behind that batch has done this)
+        if (!partitioned) launch_partition(e, e->d.matches, M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx);
     }
     // patch normals: the estimator runs behind the frame's last update on the inliers and the rescued; d.msel is
     // overwritten by the rescue, so each list is copied behind its partition

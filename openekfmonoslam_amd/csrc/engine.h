@@ -474,21 +474,21 @@ __device__ __forceinline__ RansacRec load_ransac_rec(int f, int N, const double 
 
 // quaternion normalisation and its Jacobian (Update.cpp:45-62, 303-312), one thread: J from the un-normalised q, then q /= |q|
 // and R(q)
-__device__ inline void quat_norm_dev(double *st)
+// (q: the un-normalised quaternion in, the normalised one out; J: the 4 x 4 Jacobian of the normalisation; R: the rotation of the result)
+__device__ inline void quat_norm_parts(double *q, double *J, double *R)
 {
-    double *q = st + ST_X + 3;
     const double r = q[0], x = q[1], y = q[2], z = q[3];
     const double nrm = sqrt(r * r + x * x + y * y + z * z);
     const double a = 1.0 / (nrm * nrm * nrm);
-    double *J = st + ST_JN;
     const double M[16] = {x * x + y * y + z * z, -r * x, -r * y, -r * z,
                           -x * r, r * r + y * y + z * z, -x * y, -x * z,
                           -y * r, -y * x, r * r + x * x + z * z, -y * z,
                           -z * r, -z * x, -z * y, r * r + x * x + y * y};
     for (int i = 0; i < 16; ++i) J[i] = M[i] * a;
     q[0] = r / nrm; q[1] = x / nrm; q[2] = y / nrm; q[3] = z / nrm;
-    quat_to_rot(q, st + ST_R);
+    quat_to_rot(q, R);
 }
+__device__ inline void quat_norm_dev(double *st) { quat_norm_parts(st + ST_X + 3, st + ST_JN, st + ST_R); }
 #endif
 
 // Exclusive prefix sum of one int per thread over a 1024-thread workgroup (and the total): inside a wavefront by shuffles,

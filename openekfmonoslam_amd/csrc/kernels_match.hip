@@ -269,7 +269,8 @@ void launch_match_index(EkfEngine *e, int M, const int *d_M)
 __global__ void __launch_bounds__(1024)
 k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, EkfMatch *dst0, int *cnt1, const uint8_t *kdesc,
             uint8_t *feat_desc, unsigned *times_matched, int desc_bytes, int *idx0, const int *counts, int *mirror,
-            int publish_seq, uint8_t *rescue_mask, const int *vis, const double *uv_tab, const double *S_tab, double chi2)
+            int publish_seq, uint8_t *rescue_mask, const int *vis, const double *uv_tab, const double *S_tab, double chi2, const int *d_M,
+            int behind_ransac)
 {
     __shared__ int wtot[16];
     const int tid = threadIdx.x;
@@ -277,6 +278,10 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
         if (publish_seq > 0) publish_counts_block(counts, mirror, publish_seq);
         return;
     }
+    // behind_ransac: enqueued behind a frame's FIRST batch of hypotheses, before the host has seen its outcome (launch_partition):
+    // the match count is the device's, and a loop that batch did not finish leaves everything to the launch behind the loop
+    if (behind_ransac && !counts[CNT_RS_DONE]) return;
+    if (d_M) M = *d_M;
     const int per = (M + 1023) / 1024;
     const int b = tid * per, e = min(M, b + per);
     // A thread's FIRST match -- its only one up to 1024 matches -- and its flag stay in registers from the first load to the map's
@@ -356,8 +361,10 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
 }
 
 void launch_partition(EkfEngine *e, const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, EkfMatch *dst0,
-                      int *cnt1, bool map_update, const uint8_t *d_kdesc, int *d_idx0, int publish_seq, bool rescue)
+                      int *cnt1, bool map_update, const uint8_t *d_kdesc, int *d_idx0, int publish_seq, bool rescue, const int *d_M,
+                      bool behind_ransac)
 {
+    // d_M: M is an upper bound for the launch, the kernel reads the count (see k_partition for behind_ransac)
     if (M <= 0) {
         if (cnt1) (void)hipMemsetAsync(cnt1, 0, sizeof(int), e->stream);
         return;
@@ -365,7 +372,7 @@ void launch_partition(EkfEngine *e, const EkfMatch *src, int M, const uint8_t *f
     k_partition<<<1, 1024, 0, e->stream>>>(src, M, flags, dst1, dst0, cnt1, d_kdesc, e->d.feat_desc,
                                            map_update ? e->d.feat_times_matched : nullptr, e->desc_bytes, d_idx0, e->d.counts,
                                            e->d_mirror, e->d_mirror ? publish_seq : 0, rescue ? e->d.mask : nullptr, e->d.pred_vis,
-                                           e->d.pred_uv, e->d.pred_S, e->cfg.par.ransacChi2Threshold);
+                                           e->d.pred_uv, e->d.pred_S, e->cfg.par.ransacChi2Threshold, d_M, behind_ransac ? 1 : 0);
 }
 
 

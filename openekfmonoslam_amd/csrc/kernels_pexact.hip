@@ -199,15 +199,48 @@ k_dx_planes(const int8_t *Bq, size_t b_stride, int ldq, int m16, int n, const in
 #pragma unroll
             for (int s = 0; s < PX_S; ++s) nx[s] = *(const uint4 *)(Bq + (size_t)s * b_stride + ((size_t)(kb + 1) * ldq + j) * 16);
         }
+        // The element's integer as a double from its digit word (px_word_value: no 64-bit integer chain, the kernel was bound by its
+        // issue rate): element i's low word is byte i % 4 of the words i / 4 of planes 1 .. 4 -- a 4 x 4 byte transpose, two
+        // v_perm_b32 per element -- and its top digit the same byte of plane 0.
+        double Xv[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsigned hi[4], lo[4];
+#if PX_S_VALUE == 5
+            const unsigned p0 = q == 0 ? d[0].x : (q == 1 ? d[0].y : (q == 2 ? d[0].z : d[0].w));
+            const unsigned p1 = q == 0 ? d[1].x : (q == 1 ? d[1].y : (q == 2 ? d[1].z : d[1].w));
+            const unsigned p2 = q == 0 ? d[2].x : (q == 1 ? d[2].y : (q == 2 ? d[2].z : d[2].w));
+            const unsigned p3 = q == 0 ? d[3].x : (q == 1 ? d[3].y : (q == 2 ? d[3].z : d[3].w));
+            const unsigned p4 = q == 0 ? d[4].x : (q == 1 ? d[4].y : (q == 2 ? d[4].z : d[4].w));
+            // (selector bytes 0 .. 3: bytes of the second operand, 4 .. 7: of the first)
+            const unsigned a_lo = __builtin_amdgcn_perm(p1, p2, 0x05010400u), a_hi = __builtin_amdgcn_perm(p1, p2, 0x07030602u);
+            const unsigned b_lo = __builtin_amdgcn_perm(p3, p4, 0x05010400u), b_hi = __builtin_amdgcn_perm(p3, p4, 0x07030602u);
+            lo[0] = __builtin_amdgcn_perm(a_lo, b_lo, 0x05040100u);
+            lo[1] = __builtin_amdgcn_perm(a_lo, b_lo, 0x07060302u);
+            lo[2] = __builtin_amdgcn_perm(a_hi, b_hi, 0x05040100u);
+            lo[3] = __builtin_amdgcn_perm(a_hi, b_hi, 0x07060302u);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) hi[c] = (p0 >> (8 * c)) & 255u;
+#else
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                unsigned long long W = 0;
+#pragma unroll
+                for (int s = 0; s < PX_S; ++s) {
+                    const unsigned w = q == 0 ? d[s].x : (q == 1 ? d[s].y : (q == 2 ? d[s].z : d[s].w));
+                    W = (W << 8) | ((w >> (8 * c)) & 255u);
+                }
+                hi[c] = (unsigned)(W >> 32);
+                lo[c] = (unsigned)W;
+            }
+#endif
+#pragma unroll
+            for (int c = 0; c < 4; ++c) Xv[4 * q + c] = px_word_value(hi[c], lo[c]);
+        }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            long long X = 0;
-#pragma unroll
-            for (int s = 0; s < PX_S; ++s) {
-                const unsigned w = i < 4 ? d[s].x : (i < 8 ? d[s].y : (i < 12 ? d[s].z : d[s].w));
-                X = X * 256 + (long long)(signed char)((w >> (8 * (i & 3))) & 255u);
-            }
-            sum += (double)X * z[16 * kb + i];
+            const double Xd = Xv[i]; // = (double)X, bit for bit
+            sum += Xd * z[16 * kb + i];
         }
     }
     part[(size_t)ks * ldpart + j] = ldexp(sum, (bexp[j] - 1022) - (8 * PX_S - 2));

@@ -1228,30 +1228,44 @@ k_apply_normalize(T *P, int ld, int n, double *st, RowMap rm, double *feat_pos, 
 {
     __shared__ double J[16];
     __shared__ double C[7][7];
-    __shared__ double cam[13];
+    __shared__ double cam[13], xold[13];
     const int tid = threadIdx.x;
     if (filter_frozen(counts)) return; // the update's sweep failed: x and P stay as they were (engine.h)
     const int t = blockIdx.x * 256 + tid;
-    const bool live = t < N * 6 && (t % 6) < feat_dim(feat_type[t / 6]);
-    const int jf = live ? feat_covpos[t / 6] + t % 6 : 0;
+    // Everything the tail reads that nothing in it computes is requested up front, in as few dependent trips as the data allows (the
+    // launch is a chain of round trips, not of arithmetic): the feature's type and position together, then the k-splits of dx, and
+    // beside them this thread's feature parameter and workgroup 0's camera state.
+    const bool in_map = t < N * 6;
+    const int ftype = in_map ? feat_type[t / 6] : 0, fpos = in_map ? feat_covpos[t / 6] : 0;
+    const double fp_old = in_map ? feat_pos[6 * (t / 6) + t % 6] : 0.0;
+    const bool live = in_map && (t % 6) < feat_dim(ftype);
+    const int jf = live ? fpos + t % 6 : 0;
     double pv[DX_SPLIT];
 #pragma unroll
     for (int ks = 0; ks < DX_SPLIT; ++ks) pv[ks] = part[(size_t)ks * ldpart + jf];
     if (tid < 13 && (blockIdx.x == 0 || (tid >= 3 && tid < 7))) {
+        const double xo = blockIdx.x == 0 ? st[ST_X + tid] : 0.0;
         double s = 0.0;
 #pragma unroll
         for (int ks = 0; ks < DX_SPLIT; ++ks) s += part[(size_t)ks * ldpart + tid];
         cam[tid] = s;
+        xold[tid] = xo;
     }
     if (blockIdx.x == 0 && tid < 49) C[tid / 7][tid % 7] = (double)P[(size_t)(tid / 7) * ld + tid % 7];
     __syncthreads();
     if (tid == 0) {
         if (blockIdx.x == 0) {
-            double *x = st + ST_X;
-            for (int i = 0; i < 13; ++i)
-                if (fabs(cam[i]) > EKF_DELTA) x[i] += cam[i];
-            quat_norm_dev(st);
-            for (int i = 0; i < 16; ++i) J[i] = st[ST_JN + i];
+            // x += dx, the normalisation and its Jacobian on values in registers (quat_norm_parts is quat_norm_dev's body): the
+            // stores below wait for nothing, where updating st in place read every value back behind its own store
+            double xn[13], Jn[16], Rn[9];
+            for (int i = 0; i < 13; ++i) {
+                xn[i] = xold[i];
+                if (fabs(cam[i]) > EKF_DELTA) xn[i] += cam[i];
+            }
+            quat_norm_parts(xn + 3, Jn, Rn);
+            for (int i = 0; i < 13; ++i) st[ST_X + i] = xn[i];
+            for (int i = 0; i < 16; ++i) st[ST_JN + i] = J[i] = Jn[i];
+            for (int i = 0; i < 9; ++i) st[ST_R + i] = Rn[i];
         } else {
             const double *q0 = part + (size_t)DX_SPLIT * ldpart;
             double q[4];
@@ -1273,7 +1287,7 @@ k_apply_normalize(T *P, int ld, int n, double *st, RowMap rm, double *feat_pos, 
         double s = 0.0;
 #pragma unroll
         for (int ks = 0; ks < DX_SPLIT; ++ks) s += pv[ks];
-        if (fabs(s) > EKF_DELTA) feat_pos[6 * (t / 6) + t % 6] += s;
+        if (fabs(s) > EKF_DELTA) feat_pos[6 * (t / 6) + t % 6] = fp_old + s;
     }
     __syncthreads();
     if (blockIdx.x == 0) {

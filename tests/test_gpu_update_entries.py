@@ -6,7 +6,7 @@ update_ref's docstring and DESIGN.md, "Stage tests of the update").  No exclusio
 Each case: set_state (-> a position fix without information, so that the engine knows P as symmetric and the downdate is
 k_p_update_i8p in fp32 storage too: fresh_engine) -> predict -> predict_measurements -> update(the first M predictions, a fraction of a pixel off); the
 reference starts from what the engine holds after the two predictions (get_state, feature_layout, its own Hs and Hf) and is
-cached per (map, M, stored bits), so one longdouble update serves every configuration and route that starts from the same bits.
+cached per (map, M, stored bits), so one long-double update (compiled: tests/update_ref_fast.py) serves every configuration and route that starts from the same bits.
 
 Maps.  Column edges: the mixed depth / inverse-depth maps of predict_ref.types_for_n at n = 85 ... 514 with a covariance built
 by synth.seed_map on those scenes (update_ref.spiky_scene: variance 1 beside 2e-16; predict_ref.make_P0 is flat to three orders
@@ -14,13 +14,15 @@ and would hide the entries this file is about), M = 17.  Row edges and routes: S
 map: the same sequence after CONVERGED_FRAMES steps.
 
 EKF_PRECISION_F32 (the fast configuration) is out of scope: it is documented not to meet component-wise parity
-(parity_metric.FAST_COMPONENT_CEILING).  Updates above 2048 rows and sharded engines: DESIGN.md names them as the remaining gap."""
+(parity_metric.FAST_COMPONENT_CEILING).  Updates around 2048 rows: tests/test_gpu_update_entries_large.py.  Sharded engines:
+DESIGN.md names them among the remaining gaps."""
 import hashlib
 
 import numpy as np
 import pytest
 
 import update_ref as ur
+import update_ref_fast as uf
 from parity_metric import F32_TOL, F64_TOL, over_tolerance, parity_report
 from openekfmonoslam_amd.synth import SyntheticSequence
 
@@ -78,16 +80,16 @@ def predicted_inputs(e, cam, M):
     return m, (x, fp, t, c, P, rows, res, cam.pixelErrorX * np.eye(len(res)))
 
 
-def reference(label, inputs, precision, update_cov=True, exact=None, min_spread=1e6):
+def reference(label, inputs, precision, update_cov=True, exact=None, min_spread=1e6, c_arith=ur.C_ARITH):
     x, fp, t, c, P, rows, res, R = inputs
     h = hashlib.sha1()
     for a in (x, fp, t, c, P, *rows, res):
         h.update(np.ascontiguousarray(a).tobytes())
     key = (label, h.hexdigest())
     if key not in _CORES:
-        _CORES[key] = ur.update_core(x, fp, P, rows, res, R)
+        _CORES[key] = uf.update_core(x, fp, P, rows, res, R)  # (the compiled restatement: the same bits at these sizes, asserted on the CPU)
     exact = precision in (2, 3) if exact is None else exact
-    ref = ur.with_bounds(_CORES[key], t, c, storage_of(precision), exact, update_cov)
+    ref = ur.with_bounds(_CORES[key], t, c, storage_of(precision), exact, update_cov, c_arith)
     cond = float(np.linalg.cond(ref["S"].astype(np.float64)))
     sd = np.sqrt(np.diag(P))
     # the case's input conditions (tests/test_update_ref_cpu.py asserts the same from the oracle's state)

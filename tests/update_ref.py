@@ -39,6 +39,11 @@ Tolerance of an entry of P_downdated (prior P-, posterior reference `ref`):
   (d) exact="gemm" (EKF_UPDATE_PATH_GEMM, k_b_gemm_i8p): B = inv(L) G is one int8 GEMM from the planes of W = inv(L)' and of G under
       their columns' TRUE scales (k_col_exp: the largest exponent field): Delta_rc = sum_k (|W_kr| qG_c + qW_r |G_kc| + qW_r qG_c)
       + the dropped levels of that product.
+  (e) exact="measured" (EKF_UPDATE_PATH_SWEEP above 2048 rows: update_route.h leaves planes_b, gemm_planes and apriori false).  The
+      rows of B are fp64 (their error is C_ARITH's), dx = B'z is formed from them (k_dx_partial: no digit term in the state), and the
+      downdate cuts them into planes under MEASURED scales: k_dx_partial leaves the largest exponent field of column j in Bexp (the
+      rule of k_col_exp: |B_kj| < 2^e_j, e_j = Bexp_j - 1022) and k_slice_B forms X_kj = rint(B_kj 2^(38 - e_j)).  (a) + (b) with these
+      e_j; neither (c) nor (d).  An all-zero column has no scale and no digits.
   An error Delta of the rows of B costs the downdate |B|' Delta + Delta' |B| + Delta' Delta and the state Delta' |z|.
   Nothing of the kernels' int32 accumulation, unit lists or plane layouts is restated: dig is a bound, not an emulation.
   C_ARITH cannot be counted by rule (it depends on cond S through the factorisation): it is the worst
@@ -74,6 +79,8 @@ PX_BITS = 8 * PX_S - 2       # 38
 ARITH_MARGIN = 8.0
 C_ARITH_MEASURED = 578.0     # worst figure of tests/test_update_ref_cpu.py (printed there; the test asserts it is not exceeded)
 C_ARITH = ARITH_MARGIN * C_ARITH_MEASURED
+C_ARITH_LARGE_MEASURED = 358.0  # worst figure of tests/test_update_ref_fast_cpu.py at the large cases (n = 3157, m = 2048 and 2050)
+C_ARITH_LARGE = ARITH_MARGIN * C_ARITH_LARGE_MEASURED
 K_NORM = 32.0
 DEPTH_RHO_SD = 0.01
 
@@ -110,22 +117,24 @@ def digit_bound(B, e):
     D = np.abs(balanced_digits(X.astype(np.int64))).astype(np.float64)  # products and sums below 2^53: exact in fp64
     assert np.array_equal((balanced_digits(X.astype(np.int64)) * (256 ** np.arange(PX_S - 1, -1, -1))[:, None, None]).sum(axis=0),
                           X.astype(np.int64))
-    drop = np.zeros((n, n), LD)
-    for s in range(PX_S):
-        for t in range(PX_S):
-            if s + t >= PX_S:
-                drop += LD(256.0 ** (2 * (PX_S - 1) - s - t)) * (D[s].T @ D[t]).astype(LD)
+    drop = _dropped_levels(D.transpose(0, 2, 1), D).astype(LD)
     scale = np.ldexp(LD(1), (e[:, None] + e[None, :] - 2 * PX_BITS).astype(np.int64))
     return dig + drop * scale, q
 
 
 def _dropped_levels(DA, DB):
-    """sum over the pairs s + t >= PX_S of 256^(2 (PX_S - 1) - s - t) DA_s @ DB_t (digit magnitudes, fp64: exact below 2^53)"""
+    """sum over the pairs s + t >= PX_S of 256^(2 (PX_S - 1) - s - t) DA_s @ DB_t (digit magnitudes [PX_S, rows, k] and [PX_S, k, cols]),
+    regrouped as sum_s DA_s @ (sum_{t >= PX_S - s} 256^(2 (PX_S - 1) - s - t) DB_t): PX_S - 1 products instead of ten.  Integers in fp64:
+    exact while every partial sum stays below 2^53, which is asserted (m <= 2080 rows of 128 256^3 (1 + 1/256 + ...) 128: 2^50)"""
     out = np.zeros((DA.shape[1], DB.shape[2]))
-    for s in range(PX_S):
-        for t in range(PX_S):
-            if s + t >= PX_S:
-                out += 256.0 ** (2 * (PX_S - 1) - s - t) * (DA[s] @ DB[t])
+    total = 0.0
+    for s in range(1, PX_S):
+        T = np.zeros(DB.shape[1:])
+        for t in range(PX_S - s, PX_S):
+            T += 256.0 ** (2 * (PX_S - 1) - s - t) * DB[t]
+        total += DA.shape[2] * DA[s].max(initial=0) * T.max(initial=0)
+        out += DA[s] @ T
+    assert total < 2.0 ** 53, "the dropped levels' sums leave the integers fp64 holds exactly"
     return out
 
 
@@ -207,13 +216,38 @@ def rounded(A, storage):
     return np.asarray(A).astype(storage).astype(LD)
 
 
+class _Routes:
+    """route -> (bound of B'B, bound of B'z) for the rows of B formed from digit planes; a route's bound is evaluated when it is
+    first asked for (at 2050 rows each costs seconds, and a case asks for one)"""
+
+    def __init__(self, S, L, B, e_col, W, A, z):
+        self._in, self._done = (S, L, B, e_col, W, A, z), {}
+
+    def __getitem__(self, route):
+        if route not in self._done:
+            S, L, B, e_col, W, A, z = self._in
+            assert route in ("sweep", "gemm"), route
+            Delta = sweep_plane_bound(S, L, B, e_col, W) if route == "sweep" else gemm_plane_bound(W, A)
+            self._done[route] = _through_b(Delta, B, z)
+        return self._done[route]
+
+
+def core_of(x13, feature_pos, P, A, S, L, W, B, z, dx, P6):
+    """the dict of update_core from the arithmetic's results (longdouble), with the digit bound of the downdate and the routes' bounds
+    (numpy, shared by the interpreted and the compiled reference: tests/update_ref_fast.py)"""
+    P64 = np.asarray(P, dtype=np.float64)
+    sd = np.sqrt(np.maximum(np.diag(P64).astype(LD), 0))
+    e_col = column_exponents(np.diag(P64))
+    dig, q = digit_bound(B, e_col)
+    return {"route": _Routes(S, L, B, e_col, W, A, z), "x": np.asarray(x13, dtype=np.float64).astype(LD),
+            "fp": np.asarray(feature_pos, dtype=np.float64).reshape(-1, 6).astype(LD), "Pm": P64.astype(LD), "B": B, "z": z, "S": S, "L": L,
+            "dx": dx, "sd": sd, "dig": dig, "q": q, "P6": P6, "W": W, "A": A}
+
+
 def update_core(x13, feature_pos, P, rows, residual, R):
     """the arithmetic of the update in longdouble, before any rounding or dead-band (what the storage type and the configuration do
     not change: tests share it) -> dict"""
-    x = np.asarray(x13, dtype=np.float64).astype(LD)
-    fp = np.asarray(feature_pos, dtype=np.float64).reshape(-1, 6).astype(LD)
-    P64 = np.asarray(P, dtype=np.float64)
-    Pm = P64.astype(LD)
+    Pm = np.asarray(P, dtype=np.float64).astype(LD)
     n = len(Pm)
     H = dense_rows(rows, n)
     m = len(H)
@@ -227,35 +261,35 @@ def update_core(x13, feature_pos, P, rows, residual, R):
     for i in range(m):
         z[i] = (res[i] - L[i, :i] @ z[:i]) / L[i, i]
         B[i] = (A[i] - L[i, :i] @ B[:i]) / L[i, i]
-    sd = np.sqrt(np.maximum(np.diag(P64).astype(LD), 0))
-    e_col = column_exponents(np.diag(P64))
-    dig, q = digit_bound(B, e_col)
     W = lower_inverse(L)
-    route = {"sweep": _through_b(sweep_plane_bound(S, L, B, e_col, W), B, z), "gemm": _through_b(gemm_plane_bound(W, A), B, z)}
-    return {"route": route, "x": x, "fp": fp, "Pm": Pm, "B": B, "z": z, "S": S, "L": L, "dx": B.T @ z, "sd": sd, "dig": dig, "q": q,
-            "P6": xr.mirror_upper(LD(0.5) * Pm + LD(0.5) * Pm.T - B.T @ B)}
+    return core_of(x13, feature_pos, P, A, S, L, W, B, z, B.T @ z, xr.mirror_upper(LD(0.5) * Pm + LD(0.5) * Pm.T - B.T @ B))
 
 
 def update_ref(x13, feature_pos, feature_type, covpos, P, rows, residual, R, storage=np.float64, exact=False, update_cov=True):
     return with_bounds(update_core(x13, feature_pos, P, rows, residual, R), feature_type, covpos, storage, exact, update_cov)
 
 
-def with_bounds(core, feature_type, covpos, storage=np.float64, exact=False, update_cov=True):
+def with_bounds(core, feature_type, covpos, storage=np.float64, exact=False, update_cov=True, c_arith=C_ARITH):
     """-> dict: x13, feature_pos, P, P_downdated (rounded to `storage` where the engine rounds), P_cmp / tol_P (what the engine's P
     is compared with and by how much, see the module docstring), P_downdated_cmp / tol_P_downdated, tol_x13 / tol_feature_pos,
     deadband_margin, B, z, S, L, dx (longdouble), scale (sqrt(P-_ii P-_jj)), dig (zeros unless exact), q.  Nothing is modified.
-    exact: False (fp64 configuration), True or "sweep" (rows of B from digit planes inside the sweep), "gemm" (from the int8 GEMM).
+    exact: False (fp64 configuration), True or "sweep" (rows of B from digit planes inside the sweep), "gemm" (from the int8 GEMM),
+    "measured" (EKF_UPDATE_PATH_SWEEP above 2048 rows: terms (a) + (b) under the columns' true scales, see (e) of the module docstring).
     update_cov False: the state-only update -- q is not normalised, P returned as given."""
     x, fp, Pm, B, z, S, L, dx, sd, P6 = (core[k] for k in ("x", "fp", "Pm", "B", "z", "S", "L", "dx", "sd", "P6"))
     n = len(Pm)
     u = u_store_of(storage)
     scale = np.outer(sd, sd)
     dig, q, dx_b = (core["dig"], core["q"], np.zeros(n, LD)) if exact else (np.zeros((n, n), LD), np.zeros(n, LD), np.zeros(n, LD))
-    if exact:  # True: the default route at these sizes, the rows of B inside the sweep
+    if exact == "measured":  # fp64 rows of B cut by the downdate under measured column scales; dx from the fp64 rows
+        if "dig_measured" not in core:
+            core["dig_measured"] = digit_bound(B, _true_exponents(B, 0))[0]
+        dig, q = core["dig_measured"], np.zeros(n, LD)
+    elif exact:  # True: the default route at these sizes, the rows of B inside the sweep
         dig_b, dx_b = core["route"]["sweep" if exact is True else exact]
         dig = dig + dig_b
     # ---- state
-    tol_dx = q * np.abs(z).sum() + dx_b + C_ARITH * U64 * sd * np.sqrt(z @ z)
+    tol_dx = q * np.abs(z).sum() + dx_b + c_arith * U64 * sd * np.sqrt(z @ z)
     tol_dx[~np.any(B != 0, axis=0)] = 0  # a structurally zero column of B (see the module docstring): dx_i = 0 in any order of summation
     margin = float((np.abs(np.abs(dx) - EKF_DELTA) / np.where(tol_dx > 0, tol_dx, LD(1e-300))).min())
     dxb = np.where(np.abs(dx) > EKF_DELTA, dx, LD(0))
@@ -279,7 +313,7 @@ def with_bounds(core, feature_type, covpos, storage=np.float64, exact=False, upd
         out["P"] = out["P_cmp"] = Pm
         return out
     # ---- covariance
-    tol6 = u * np.abs(P6) + (1 + u) * (dig + C_ARITH * U64 * scale)
+    tol6 = u * np.abs(P6) + (1 + u) * (dig + c_arith * U64 * scale)
     P6r = rounded(P6, storage)
     Pn = normalize_covariance(P6r, J)
     strip = np.zeros((n, n), dtype=bool)
@@ -314,14 +348,43 @@ def spiky_scene(n):
     correlated with nothing, so this is one diagonal entry).  With sigma = 1 m along the ray, the state correction of an unmeasured
     point (1e-14, through the camera's 2e-16 alone: dead-banded) would lie within the exact configurations' digit term of the
     dead-band and the case would be invalid (module docstring)."""
+    from predict_ref import types_for_n
+
+    return spiky_scene_of_types(("spiky", n), types_for_n(n))
+
+
+LARGE_FEATURES = 1032
+LARGE_N = 3157          # 13 + 16 x 6 + 1016 x 3; n_pad = 3200: 25 tiles of 128, the last with 85 live columns
+LARGE_M = (1024, 1025)  # m = 2048: the last size with B in the sweep; m = 2050: m_pad = 2080, 65 steps, the second mask chunk
+# The features that M = 1024 leaves unmeasured.  As points of the spiky scene (correlated with the camera through its 2e-16 alone)
+# their correction is 1e-14 .. 1e-13, dead-banded, while sum |z| over 2048 rows is 316 and the exact configurations' state terms are
+# 1e-12 .. 9e-12 (q_i sum |z|) and 1e-10 (rows of B from the planes in the sweep): deadband_margin 0.004 / 0.1, the case invalid.  They
+# are held as uncorrelated landmarks instead, whose correction is a sum of zeros until they are measured (M = 1025 measures the first).
+LARGE_UNCORRELATED = tuple(range(1024, 1032))
+LARGE_CASES = [("large", LARGE_N, M) for M in LARGE_M]
+
+
+def large_types():
+    """1032 features, all in view: feature f is an inverse-depth feature where f % 64 == 31 (16 of them), every other one XYZ --
+    close to the smallest map that allows M = 1025 (all XYZ: n = 3088) with both kinds and a ragged last tile"""
+    from openekfmonoslam_amd.ekftypes import FEATURE_DEPTH
+
+    return np.where(np.arange(LARGE_FEATURES) % 64 == 31, FEATURE_INVERSE_DEPTH, FEATURE_DEPTH).astype(np.int32)
+
+
+def spiky_scene_of_types(key, types, uncorrelated=()):
+    """spiky_scene for an explicit list of feature types (cached under `key`); an inverse-depth feature keeps seed_map's sigma = 1 on
+    its inverse depth, an XYZ feature gets DEPTH_RHO_SD before the conversion.  uncorrelated: features whose covariances with the
+    camera and with every other feature are stored zeros (a landmark taken over from a prior map): while such a feature is not
+    measured its columns of B are sums of products with stored zeros, so its state correction is zero in any order of summation."""
     import map_points_ref as mp
     import predict_ref as pr
     from openekfmonoslam_amd import synth
 
-    key = ("spiky", n)
     if key in pr._SCENES:
         return pr._SCENES[key]
-    types = pr.types_for_n(n)
+    types = np.asarray(types, dtype=np.int32)
+    n = 13 + int(sum(6 if t == FEATURE_INVERSE_DEPTH else 3 for t in types))
     s = pr.make_scene(types, vis=np.ones(len(types), dtype=bool), with_P0=False)
     R = synth.quat_to_rot(s.x13[3:7])
     world = np.array([mp.world_point(y, t)[0] for y, t in zip(s.feature_pos, types)])
@@ -344,6 +407,12 @@ def spiky_scene(n):
             T[c:c + 3, 13 + 6 * f:19 + 6 * f] = mp.world_point(pos6[f], FEATURE_INVERSE_DEPTH)[1]
     P0 = T @ P6 @ T.T
     s.P0 = 0.5 * (P0 + P0.T)
+    for f in uncorrelated:  # (a principal block cut loose from the rest: still symmetric positive semi-definite)
+        c, k = int(s.covpos[f]), 6 if types[f] == FEATURE_INVERSE_DEPTH else 3
+        own = s.P0[c:c + k, c:c + k].copy()
+        s.P0[c:c + k, :] = 0.0
+        s.P0[:, c:c + k] = 0.0
+        s.P0[c:c + k, c:c + k] = own
     pr._SCENES[key] = s
     return s
 
@@ -370,8 +439,9 @@ _SEQ = {}
 
 def case_map(kind, n):
     """-> (cam, par, x13, feature_pos, feature_type, desc, P0) of a case's map before the prediction"""
-    if kind == "mixed":
-        s = spiky_scene(n)
+    if kind in ("mixed", "large"):
+        s = spiky_scene(n) if kind == "mixed" else spiky_scene_of_types(("spiky", "large"), large_types(), LARGE_UNCORRELATED)
+        assert s.n == n
         return s.cam, s.par, s.x13, s.feature_pos, s.feature_type, s.desc, s.P0
     from openekfmonoslam_amd.synth import SyntheticSequence
 

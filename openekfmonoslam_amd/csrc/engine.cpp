@@ -288,6 +288,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     ALLOC(d.pred_vis2, cap);
     ALLOC(d.pred_uv2, 2 * cap);
     ALLOC(d.pred_S, 4 * cap);
+    if (world == 1) ALLOC(d.match_gates, 5 * cap);
     ALLOC(d.Hs, 14 * cap);
     ALLOC(d.Hf, 12 * cap);
     ALLOC(d.work_idx, cap);
@@ -498,6 +499,7 @@ int ekf_device_copy(EkfEngine *e, void *dst, const void *src, size_t bytes)
 static void refresh_row_map(EkfEngine *e)
 {
     const int W = e->shard_world, N = e->N;
+    e->match_gates_valid = false; // set_state, reset and map management end here: the matcher's gate table describes the map before them
     if (W == 1) {
         e->rm = RowMap{13, e->n, 13};
         e->shard_feat_begin.assign(2, 0);
@@ -1085,7 +1087,8 @@ static int predict_measurements_dev(EkfEngine *e, const int *d_idx, int count, i
         e->slot_rb.assign(e->shard_world + 1, 0);
         for (int r = 0; r <= e->shard_world; ++r) e->slot_rb[r] = e->h_counts[CNT_SHARD0 + r];
     } else if (!d_idx) e->slot_rb.clear();
-    launch_hp_rows(e, d_idx ? e->d.plist_sub : e->d.plist, np, count_predicted);
+    // (the whole map, all of its predictions: the matcher's gates ride along)
+    launch_hp_rows(e, d_idx ? e->d.plist_sub : e->d.plist, np, count_predicted, nullptr, false, !d_idx && !budgeted);
     if (!d_idx) e->n_pred = np;
     *n_out = np;
     if (e->shard_world > 1 && np > 0) {
@@ -1757,8 +1760,13 @@ static int detect_step_keypoints(EkfEngine *e);
 // features were predicted, how many matches there are and how many outliers were re-predicted only decide launch sizes, so the
 // launches use upper bounds (N, N, the outlier count) and the kernels read the counts on the device.  What the host still needs
 // to know -- the RANSAC result (loop state and inlier count: the size of the first update), the rescued count (the size of the
-// second), the error flag -- comes from three read-backs instead of six (two with ekf_set_async_errors); each one idles the GPU
-// for ~10-15 us.  Every other step reads the counts back after each stage, because the host sizes or records launches by them:
+// second), the error flag -- comes from three read-backs instead of six (two with ekf_set_async_errors).  A read-back idles the GPU
+// for as long as the host needs to see the counters and enqueue the next launch, a few us; behind the first two the next stage's
+// first launch is therefore enqueued BEFORE the poll, sized by an upper bound and reading its count on the device: the
+// low-innovation partition behind the first RANSAC batch (28.2 against 36.0 us per frame in ransac_ms) and the second update's
+// gather / assembly behind the rescue partition (2-3 us per frame).  What follows them -- the sweeps, whose grid
+// layout the host decides from the size -- still waits.
+// Every other step reads the counts back after each stage, because the host sizes or records launches by them:
 // with an image loaded the prediction's gates are snapshotted for the detectors (n_gates), kept predictions are packed for
 // ekf_get_step_predictions, the NCC matcher is launched per prediction, and a sharded engine divides predictions, matches and
 // updates between the ranks by owner.
@@ -1793,7 +1801,7 @@ restart:
     if (dev_counts) { // covariance strips and pixel predictions in one launch; with more than 256 features the compaction of
                       // the predicted list rides in the launch of the H P rows
         const bool deferred = launch_predict_with_features(e, e->N);
-        launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred);
+        launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred, true); // + the matcher's gates
     } else {
         launch_predict(e);
         if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean, budget_active ? e->budget_K : 0))) return rc;
@@ -1870,6 +1878,7 @@ restart:
     // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
     // (EKF.cpp:552-556).  An outlier that is not re-predicted has pred_vis = 0 and is not rescued.
     int nr = 0;
+    bool early_ga = false; // the second update's gather / assembly is already enqueued, for the count this stage left on the device
     if (no > 0) {
         int nop = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1879,11 +1888,18 @@ restart:
                 const int seq_p = next_publish_seq(e);
                 // rescueOutliers (EKF.cpp:84-97) and the partition it feeds in one launch
                 launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc, nullptr, seq_p, true);
+                // The second update's first launch goes behind the partition before the host polls for the rescued count, so the GPU
+                // does not wait for the host between the two: sized by the outlier count, it reads the rescued count on the device
+                // and writes update scratch only -- nothing at all behind a failed first update, where this stage runs again below.
+                // (Only where the partition publishes the counters itself: a copy of the counter block made behind this launch could show
+                // the error flag of the SECOND update's first diagonal block as if the first update had failed.)
+                early_ga = seq_p > 0 && launch_early_gather(e, no, cnt + CNT_NRESC, step_kind);
                 rc = wait_counts(e, seq_p);
             } else {
                 rc = predict_measurements_dev(e, e->d.work_idx, no, &nop, false, lean);
             }
             if (rc) return rc;
+            early_ga = early_ga && !e->h_counts[CNT_ERR];
             if (!e->h_counts[CNT_ERR]) break;
             // the first update failed (seen at this stage's read-back; everything behind it was frozen, a fused partition did
             // nothing and the inliers are still in d.msel): run it again or skip it (recover_failed_update), then this stage again
@@ -1904,7 +1920,10 @@ restart:
         HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     // 10. high-innovation update (:529-532)
     e->cons_stage = 2;
-    if ((rc = update_dev(e, nr, step_kind, lean))) return rc;
+    e->early_ga.armed = early_ga; // (this update's route decides whether the early launch serves it: launch_update)
+    rc = update_dev(e, nr, step_kind, lean);
+    e->early_ga.armed = false;
+    if (rc) return rc;
     tm.mark();
     if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
     if (dev_counts && e->async_errors) {

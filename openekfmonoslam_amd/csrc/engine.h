@@ -147,6 +147,7 @@ struct DeviceArrays {
     int *pred_vis2 = nullptr;    // scratch copies for state-only predictions
     double *pred_uv2 = nullptr;
     double *pred_S = nullptr;  // 4 per feature
+    double *match_gates = nullptr; // 5 per feature: the descriptor matcher's Gate (gate.h) of the last full prediction, see match_gates_valid
     double *Hs = nullptr;      // 2x7 per feature
     double *Hf = nullptr;      // 2x6 per feature
     void *HP = nullptr;        // T [2*cap x ldP]: rows 2f, 2f+1 = H_f P   (fp64 in EKF_PRECISION_F32_EXACT)
@@ -293,6 +294,13 @@ struct Frames {
     uint8_t *desc = nullptr;
 };
 
+// the gather / assembly launch a step enqueued ahead of its second update (launch_early_gather): what it assumed of the route, and
+// whether the update about to be launched is the one it was made for (set by the step around that one call)
+struct EarlyGather {
+    bool armed = false;
+    bool planes_b = false, apriori = false, persist = false, b_in_sweep = false;
+};
+
 } // namespace ekf
 
 struct EkfEngine {
@@ -343,6 +351,10 @@ struct EkfEngine {
     int last_update_kind = 1;             // ... its kind, ekf::UPDATE_* (a retry runs the same kind again)
     bool last_update_sym = false;         // p_exact_sym as it was before that update
     bool last_update_persist = false;     // that update's sweep was the persistent launch
+    // d.match_gates holds the gates of the predictions now in pred_S / pred_uv: set by the launch_hp_rows that wrote them, cleared by
+    // everything else that rewrites those tables or the map under them
+    bool match_gates_valid = false;
+    ekf::EarlyGather early_ga;            // step path: the second update's gather / assembly enqueued before the rescued count is read
     int ps_cap[2] = {0, 0};    // resident workgroups of k_chol_persist<false / true> on this device (0: not asked yet, -1: unusable)
     bool async_errors = false; // ekf_set_async_errors: no read-back at the end of a step
     bool err_unread = false;   // the last step returned without reading the error flag back (cleared by recover_failed_update)
@@ -523,7 +535,8 @@ void launch_predict(EkfEngine *e);
 bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool state_only, bool defer_compact = false);
 bool launch_predict_with_features(EkfEngine *e, int count); // step path: prepare, then covariance strips + all features in one launch
 // d_count != nullptr: n_list is an upper bound, the list's length is read on the device
-void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false);
+void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false,
+                    bool gates = false);
 // keypoints kps / kdesc; d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device; d_nkp
 // likewise for n_kp
 void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_pred, int n_kp, const int *d_npred = nullptr,
@@ -547,6 +560,9 @@ void launch_ransac_init(EkfEngine *e, int M);
 // and covariance strip of the camera alone)
 enum { UPDATE_STATE_ONLY = 0, UPDATE_COV = 1, UPDATE_FIXED_MAP = 2 };
 void launch_update(EkfEngine *e, int M, int kind);
+// the merged gather / assembly launch of an update of the matches in d.msel whose count (at most M_max) is still on the device at
+// d_M; false: the route does not allow it, nothing was launched (kernels_update.hip)
+bool launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind);
 // fixed-map update (kernels_fixedmap.hip), fp64 arithmetic, unsharded engines.  _gain: where the route forms no rows of B, behind the inverse of
 // L -- B_c = W' G[:, 0:13] and K_c' = W B_c into d.fm_gain.  _strip: the partial sums of the 13 x n strip Y' X (Y = B[:, 0:13] and
 // X = B, m rows in d.A; or from_gain: Y = K_c' and X = G) into d.cam_part, then the tail: strip downdate, camera state, normalisation

@@ -60,6 +60,17 @@ __device__ inline void gate_from_ellipse(float cx, float cy, int aw, int ah, dou
     g->two_major = 2 * major;
 }
 
+// the descriptor matcher's gate of one prediction, from its S_f (4 doubles) and predicted pixel (2): computed by the matcher itself
+// or, once per prediction, by the launch that forms S_f (k_hp_rows) -- one sequence of calls, so the two agree to the bit
+__device__ inline void gate_from_prediction(const double *S, const double *uv, Gate *g)
+{
+    float axes[2];
+    double angle;
+    ellipse_from_cov(S, axes, &angle);
+    const int aw = (int)rintf(axes[0]), ah = (int)rintf(axes[1]); // cv::Size(Size2f): round half to even
+    gate_from_ellipse((float)uv[0], (float)uv[1], aw, ah, angle, g);
+}
+
 __device__ inline bool gate_contains(const Gate &g, double px, double py)
 {
     const double a1x = px - g.f1x, a1y = py - g.f1y, a2x = px - g.f2x, a2y = py - g.f2y;

@@ -151,6 +151,7 @@ k_budget_rank(const double *key, const int *plist, int np, int K, double pixel_e
 // d.bud_flag and a copy of the list in d.bud_all (the compaction writes d.plist itself)
 void launch_budget_select(EkfEngine *e, int np, int K)
 {
+    e->match_gates_valid = false; // pred_S is rewritten here
     if (np <= 0) return;
     const int gs = (np + SCORE_WAVES - 1) / SCORE_WAVES;
 #define SCORE_ARGS e->ldP, e->d.plist, np, e->d.feat_type, e->d.feat_covpos, e->d.Hs, e->d.Hf, e->cfg.cam.pixelErrorX, e->d.pred_S, e->d.bud_key, e->d.counts

@@ -13,8 +13,10 @@ namespace ekf {
 __global__ void __launch_bounds__(256)
 k_match(const int *plist, const double *uv_tab, const double *S_tab, const uint8_t *feat_desc,
         const EkfKeypoint *kps, const uint8_t *kdesc, int n_kp, double coef, int *mt_valid, int *mt_kp,
-        float *mt_dist, int desc_bytes, int desc_f32, const int *d_npred, int slot0, const int *d_nkp)
+        float *mt_dist, int desc_bytes, int desc_f32, const int *d_npred, int slot0, const int *d_nkp, const Gate *gate_tab)
 {
+    // gate_tab != nullptr: the gates of this predicted list were formed where its S_f were (k_hp_rows, from the same four doubles by
+    // the same calls): read, not computed again by one thread while 255 wait
     // slot0: first prediction slot of this launch (a rank of a sharded filter matches the predictions of ITS features only)
     if (d_npred && slot0 + (int)blockIdx.x >= *d_npred) return; // grid = upper bound, count on the device
     if (d_nkp) n_kp = min(*d_nkp, n_kp); // keypoints detected on the device: n_kp = the capacity, the count is read here
@@ -32,11 +34,8 @@ k_match(const int *plist, const double *uv_tab, const double *S_tab, const uint8
     const int k = slot0 + (int)blockIdx.x, tid = threadIdx.x;
     const int fi = plist[k];
     if (tid == 0) {
-        float axes[2];
-        double angle;
-        ellipse_from_cov(S_tab + 4 * fi, axes, &angle);
-        const int aw = (int)rintf(axes[0]), ah = (int)rintf(axes[1]); // cv::Size(Size2f): round half to even
-        gate_from_ellipse((float)uv_tab[2 * fi], (float)uv_tab[2 * fi + 1], aw, ah, angle, &g);
+        if (gate_tab) g = gate_tab[fi];
+        else gate_from_prediction(S_tab + 4 * fi, uv_tab + 2 * fi, &g);
         s_list_n = 0; s_front = -1; s_dfront = 0.f; s_dback = 0.f; s_min = -1.0;
     }
     const int words = desc_bytes / 4;
@@ -55,6 +54,8 @@ k_match(const int *plist, const double *uv_tab, const double *S_tab, const uint8
         bool inside[PASS];
         double dist[PASS];
         int rank[PASS];
+        // (A cheap reject in front of the foci test -- 4 |p - c|^2 > two_major^2, c the midpoint of the foci -- was measured and lost:
+        // twelve more registers take the kernel from four to three workgroups per CU)
 #pragma unroll
         for (int i = 0; i < PASS; ++i) {
             const int j = base + i * 256 + tid;
@@ -205,7 +206,7 @@ void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, in
     k_match<<<n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, kps,
                                            kdesc, n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
                                            e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, d_npred, 0,
-                                           d_nkp);
+                                           d_nkp, e->match_gates_valid ? (const Gate *)e->d.match_gates : nullptr);
     k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
                                                kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
                                                with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N,
@@ -221,7 +222,7 @@ void launch_match_slots(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kde
     if (s_hi <= s_lo) return;
     k_match<<<s_hi - s_lo, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, kps, kdesc, n_kp,
                                                 e->cfg.par.matchingCompCoefSecondBestVSFirst, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
-                                                e->desc_bytes, e->desc_f32 ? 1 : 0, nullptr, s_lo, nullptr);
+                                                e->desc_bytes, e->desc_f32 ? 1 : 0, nullptr, s_lo, nullptr, nullptr);
 }
 
 void launch_match_compact(EkfEngine *e, const EkfKeypoint *kps, int n_pred)

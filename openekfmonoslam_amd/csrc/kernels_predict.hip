@@ -5,6 +5,7 @@
 // All of it is HBM/latency-bound strip work over the (13+6N)-wide covariance: coalesced row reads, fp64 math,
 // no GEMM shapes.
 #include "engine.h"
+#include "gate.h"
 
 namespace ekf {
 
@@ -272,6 +273,7 @@ k_predict_cov_features(int nb_cov, T *P, int ld, int n, RowMap rm, const double 
 // four); returns whether the compaction of the predicted list is left to launch_hp_rows(..., from_flags = true)
 bool launch_predict_with_features(EkfEngine *e, int count)
 {
+    e->match_gates_valid = false; // pred_uv is rewritten: the gates come with the H P rows of this prediction
     if (count <= 0) {
         launch_predict(e);
         return launch_predict_features(e, nullptr, count, false, true);
@@ -318,6 +320,7 @@ void launch_compact(EkfEngine *e, const int *flag, const int *idx, int count, in
 bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool state_only, bool defer_compact)
 {
     const bool sub = state_only || d_idx != nullptr;
+    e->match_gates_valid = false; // (a state-only prediction leaves pred_uv alone; the next matcher launch forms its own gates all the same)
     if (count <= 0) {
         (void)hipMemsetAsync(e->d.counts + (sub ? CNT_NPRED_SUB : CNT_NPRED), 0, sizeof(int), e->stream);
         return false;
@@ -354,7 +357,8 @@ template <typename T, typename TO>
 __global__ void __launch_bounds__(256)
 k_hp_rows(const T *P, int ld, int n, const int *list, const int *feat_type, const int *feat_covpos,
           const double *Hs_tab, const double *Hf_tab, TO *HP, double *S_tab, RowMap rm, double *HPc, unsigned *times_predicted,
-          const int *d_count, const int *flag, int n_items, int *list_out, int *count_out, const int *counts)
+          const int *d_count, const int *flag, int n_items, int *list_out, int *count_out, const int *counts, Gate *gate_tab,
+          const double *uv_tab)
 {
     const int tid = threadIdx.x;
     if (flag) {
@@ -477,20 +481,39 @@ k_hp_rows(const T *P, int ld, int n, const int *list, const int *feat_type, cons
     }
     if (!first) return;
     __syncthreads();
+    __shared__ double sS[4];
     if (tid < 4) {
         const int r = tid >> 1, c = tid & 1;
         double s1 = 0.0, s2 = 0.0;
         for (int a = 0; a < 7; ++a) s1 += sHP[r][a] * sH[c * 7 + a];
         for (int a = 0; a < d; ++a) s2 += sHP[r][7 + a] * sH[14 + c * 6 + a];
-        S_tab[4 * fi + tid] = s1 + s2 + (r == c ? 1.0 : 0.0);
+        S_tab[4 * fi + tid] = sS[tid] = s1 + s2 + (r == c ? 1.0 : 0.0);
+    }
+    if (!gate_tab) return;
+    // the descriptor matcher's gate of this prediction (gate.h), once, from the four doubles just stored and the predicted pixel:
+    // k_match reads it instead of running this chain on one thread of every workgroup while the other 255 wait
+    __syncthreads(); // (gate_tab is the launch's: every thread of the workgroup is here)
+    if (tid == 0) {
+        Gate gt;
+        gate_from_prediction(sS, uv_tab + 2 * fi, &gt);
+        gate_tab[fi] = gt;
     }
 }
 
 // from_flags: the step's full prediction when launch_predict_features left the compaction to this launch (deferred_compact): the
 // workgroups go by k_predict_features' flags, one more workgroup writes the compacted list and its length
-void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted, const int *d_count, bool from_flags)
+// gates (a full prediction of an unsharded engine: d_list is the predicted list the matcher will walk): chunk 0 also writes the
+// descriptor matcher's gate of every feature into d.match_gates, and the table is valid until something rewrites pred_S or pred_uv
+// -- every other launch of this kernel, every pixel prediction, the measurement budget's selector (match_gates_valid, engine.h)
+void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted, const int *d_count, bool from_flags, bool gates)
 {
     unsigned *tp = count_predicted ? e->d.feat_times_predicted : nullptr;
+    // (Only above 256 listed features: there the launch is several rounds of workgroups bound by the pass over P, and chunk 0's serial
+    // chain hides behind the other workgroups' loads (N = 1000: k_match 15.1 -> 12.9 us, this kernel's full pass + 0.4).  A small
+    // map's launch is one round, the chain is its critical path, and it loses here what the matcher gains -- N = 200: the full
+    // pass + 2.4 us against k_match 8.9 -> 6.8.)
+    Gate *gt = gates && e->shard_world == 1 && n_list > 256 ? (Gate *)e->d.match_gates : nullptr;
+    e->match_gates_valid = gt != nullptr;
     if (n_list <= 0) return;
     const int chunks_f = (e->n + 256 * 4 - 1) / (256 * 4), chunks_d = (e->n + 256 * 2 - 1) / (256 * 2);
     const int *flag = from_flags ? e->d.work_flag : nullptr;
@@ -499,15 +522,15 @@ void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_pred
     if (e->exact && e->f32)
         k_hp_rows<float, double><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, d_list, e->d.feat_type,
                                                         e->d.feat_covpos, e->d.Hs, e->d.Hf, (double *)e->d.HP,
-                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts);
+                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
     else if (e->f32)
         k_hp_rows<float, float><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, d_list, e->d.feat_type,
                                                         e->d.feat_covpos, e->d.Hs, e->d.Hf, (float *)e->d.HP,
-                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts);
+                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
     else
         k_hp_rows<double, double><<<dim3(gx, chunks_d), 256, 0, e->stream>>>((const double *)e->d.P, e->ldP, e->n, d_list,
                                                          e->d.feat_type, e->d.feat_covpos, e->d.Hs, e->d.Hf,
-                                                         (double *)e->d.HP, e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts);
+                                                         (double *)e->d.HP, e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
 }
 
 // predictMeasurementState on the current state into an EkfPrediction array (device), all features.

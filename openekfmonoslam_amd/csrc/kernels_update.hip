@@ -247,9 +247,22 @@ k_gather_assemble(int mb, int gxg, const EkfMatch *matches, int M, int m_pad, co
                   const double *Hs_tab, const double *Hf_tab, const int *feat_type, const int *feat_covpos, double *nu,
                   double *mHs, double *mHf, int *mpos, int *mdim, const double *HPc, double *Gc, int *bexp, const TP *Pdiag, int ldpd,
                   int n, int *grow, double pixel_err, double *S, int ldS, double *V, double *W, float *Wf, int ldw, int *counts, int *lexp,
-                  int duties, int scale_shift)
+                  int duties, int scale_shift, const int *d_M)
 {
+    // d_M (the step's rescue stage, launch_early_gather): enqueued before the host has seen the count of selected matches -- the grid
+    // is sized by the upper bound M, the count and everything derived from it (m_pad, mb: the decoding of the workgroup id) are the
+    // device's.  Workgroups beyond the device extents return, as does every workgroup behind a failed update (filter_frozen: the
+    // count is stale then, and the stage runs again after the recovery).  What is written for a count is what the host-sized launch
+    // of that count writes.
+    if (d_M) {
+        if (filter_frozen(counts)) return;
+        M = min(*d_M, M);
+        if (M <= 0) return;
+        m_pad = (2 * M + NB - 1) / NB * NB;
+        mb = (M + 15) / 16;
+    }
     const int id = (int)blockIdx.x;
+    if (d_M && id - mb * mb >= gxg * m_pad) return;
     if (id < mb * mb) {
         const AssembleDirect dr{matches, Hs_tab, Hf_tab, feat_type, feat_covpos};
         assemble_body<T>(id % mb, id / mb, HP, ld, M, nullptr, nullptr, nullptr, nullptr, pixel_err, S, ldS, V, W, Wf, ldw, counts, lexp, nullptr, 0, M,
@@ -1579,27 +1592,47 @@ static bool exchange_p_diag(EkfEngine *e, const UpdateRoute &r)
     return e->hook_rc == 0;
 }
 
-// 2. the gathered rows G of H P and S = H P H' + R
+#define GATHER_ARGS e->d.matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
+                    e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->d.HPc, e->d.Gc, EXACT ? e->d.Bexp : nullptr
+
+// grid.x of the gather: 16 bytes of a row per thread -- or one workgroup per row where nothing is copied (bookkeeping, row map, its
+// share of the column scales)
+template <typename TB>
+static int gather_grid_x(const UpdateRoute &r)
+{
+    return (r.planes_b && !r.sharded) || r.sym_g ? 1 : (r.n_pad / (int)(16 / sizeof(TB)) + 255) / 256;
+}
+
+// gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output), for the matches in
+// e->d.matches.  d_M: r.M is an upper bound and the kernel reads the count (k_gather_assemble)
 template <typename T, typename TB, bool EXACT>
-static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r)
+static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const int *d_M)
+{
+    const int M = r.M, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
+    double *V = e->d.Dinv, *W = inv_W(e, r);
+    float *Wf = inv_Wf<TB>(e, r);
+    const int mb = (M + 15) / 16, gx = gather_grid_x<TB>(r);
+    int *gr = r.planes_b ? e->d.Grow : nullptr;
+#define GA_TAIL n, gr, e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts, r.planes_b ? e->d.Lexp : nullptr, r.persist ? 0 : 1, e->px_scale_shift, d_M
+    if (r.apriori) k_gather_assemble<TB, T><<<mb * mb + gx * m_pad, 256, 0, e->stream>>>(mb, gx, GATHER_ARGS, (const T *)e->d.P, ld, GA_TAIL);
+    else k_gather_assemble<TB, float><<<mb * mb + gx * m_pad, 256, 0, e->stream>>>(mb, gx, GATHER_ARGS, (const float *)nullptr, 0, GA_TAIL);
+#undef GA_TAIL
+}
+
+// 2. the gathered rows G of H P and S = H P H' + R
+// early_done: the step enqueued this update's merged launch behind its rescue stage, with the count on the device
+// (launch_early_gather), under the same route: nothing is launched here
+template <typename T, typename TB, bool EXACT>
+static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r, bool early_done)
 {
     hipStream_t s = e->stream;
     const int M = r.M, m = r.m, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
     const bool planes_b = r.planes_b, sharded = r.sharded, sym_g = r.sym_g, apriori = r.apriori;
     double *V = e->d.Dinv, *W = inv_W(e, r);
     float *Wf = inv_Wf<TB>(e, r);
-    dim3 grid((n_pad / (int)(16 / sizeof(TB)) + 255) / 256, m_pad);
-    if ((planes_b && !sharded) || sym_g) grid.x = 1; // no copy: one workgroup per row (bookkeeping, row map, its share of the column scales)
-#define GATHER_ARGS e->d.matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
-                    e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->d.HPc, e->d.Gc, EXACT ? e->d.Bexp : nullptr
+    dim3 grid(gather_grid_x<TB>(r), m_pad);
     if (r.merged_ga) {
-        // gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output)
-        const int mb = (M + 15) / 16;
-        int *gr = planes_b ? e->d.Grow : nullptr;
-#define GA_TAIL n, gr, e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts, planes_b ? e->d.Lexp : nullptr, r.persist ? 0 : 1, e->px_scale_shift
-        if (apriori) k_gather_assemble<TB, T><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const T *)e->d.P, ld, GA_TAIL);
-        else k_gather_assemble<TB, float><<<mb * mb + (int)(grid.x * grid.y), 256, 0, s>>>(mb, (int)grid.x, GATHER_ARGS, (const float *)nullptr, 0, GA_TAIL);
-#undef GA_TAIL
+        if (!early_done) launch_gather_assemble<T, TB, EXACT>(e, r, nullptr);
     } else if (apriori && !sharded) // a-priori column scales from the diagonal of the covariance itself
         k_gather<TB, T><<<grid, 256, 0, s>>>(GATHER_ARGS, (const T *)e->d.P, ld, n, planes_b || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
     else
@@ -1864,9 +1897,9 @@ static void downdate_and_tail(EkfEngine *e, const UpdateRoute &r)
     k_normalize_cov<T><<<nb, 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, e->d.counts);
 }
 
-// the route, the two effects it reports (back-off bookkeeping) with what a retry needs, then the launches
-template <typename T, typename TB, bool EXACT = false>
-static void update_impl(EkfEngine *e, int M, int kind)
+// what choose_update_route reads of the engine, for an update of M matches
+template <typename T, typename TB, bool EXACT>
+static UpdateRouteIn route_input(EkfEngine *e, int M, int kind)
 {
     UpdateRouteIn in;
     in.M = M; in.n = e->n; in.update_cov = kind == UPDATE_COV; in.fixed_map = kind == UPDATE_FIXED_MAP;
@@ -1883,7 +1916,49 @@ static void update_impl(EkfEngine *e, int M, int kind)
         in.ps_cap[0] = persist_capacity<false>(e);
         in.ps_cap[1] = persist_capacity<true>(e);
     }
-    UpdateRoute r = choose_update_route(in);
+    return in;
+}
+
+// The gather / assembly launch of the update that follows a step's rescue stage, enqueued BEFORE the host knows how many matches
+// were rescued (engine.cpp step_dev): M_max bounds the grid, d_M is the count on the device, the matches are in d.msel.  The
+// launch depends on the route only through same_gather_launch's fields (update_route.h), so it goes ahead when the route of the
+// largest and of the smallest possible update agree in them; the route is computed without its side effects (the back-off
+// bookkeeping stays in update_impl).  Returns whether it launched and records what it assumed: update_impl skips its own launch
+// when the real route agrees (e->early_ga, armed by the step).
+template <typename T, typename TB, bool EXACT>
+static bool early_gather_impl(EkfEngine *e, int M_max, const int *d_M, int kind)
+{
+    e->early_ga = EarlyGather();
+    UpdateRouteIn in = route_input<T, TB, EXACT>(e, M_max, kind);
+    const UpdateRoute hi = choose_update_route(in);
+    in.M = 1;
+    const UpdateRoute lo = choose_update_route(in);
+    if (hi.refusal || lo.refusal || !hi.merged_ga || !same_gather_launch(hi, lo)) return false;
+    EkfMatch *save = e->d.matches;
+    e->d.matches = e->d.msel;
+    launch_gather_assemble<T, TB, EXACT>(e, hi, d_M);
+    e->d.matches = save;
+    e->early_ga.planes_b = hi.planes_b; e->early_ga.apriori = hi.apriori; e->early_ga.persist = hi.persist; e->early_ga.b_in_sweep = hi.b_in_sweep;
+    return true;
+}
+
+bool launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind)
+{
+    if (M_max <= 0) return false;
+    if (e->exact && e->f32) return early_gather_impl<float, double, true>(e, M_max, d_M, kind);
+    if (e->exact) return early_gather_impl<double, double, true>(e, M_max, d_M, kind);
+    if (e->f32) return early_gather_impl<float, float, false>(e, M_max, d_M, kind);
+    return early_gather_impl<double, double, false>(e, M_max, d_M, kind);
+}
+
+// the route, the two effects it reports (back-off bookkeeping) with what a retry needs, then the launches
+template <typename T, typename TB, bool EXACT = false>
+static void update_impl(EkfEngine *e, int M, int kind)
+{
+    // (armed by the step for the one update behind its rescue stage; every other update launches its own gather)
+    const bool early_armed = e->early_ga.armed;
+    e->early_ga.armed = false;
+    UpdateRoute r = choose_update_route(route_input<T, TB, EXACT>(e, M, kind));
     if (r.refusal) {
         e->err = r.refusal;
         e->hook_rc = EKF_ERR_INVALID_ARG;
@@ -1904,7 +1979,9 @@ static void update_impl(EkfEngine *e, int M, int kind)
     e->last_update_stage = e->cons_stage;
 
     if (!exchange_p_diag(e, r)) return;
-    if (!gather_and_assemble<T, TB, EXACT>(e, r)) return;
+    const bool early_done = early_armed && r.merged_ga && r.planes_b == e->early_ga.planes_b && r.apriori == e->early_ga.apriori &&
+                            r.persist == e->early_ga.persist && r.b_in_sweep == e->early_ga.b_in_sweep;
+    if (!gather_and_assemble<T, TB, EXACT>(e, r, early_done)) return;
     if (!cholesky_sweep<TB, EXACT>(e, r)) return;
     inverse_and_gemm<TB>(e, r);
     if (!dx_and_state<T, TB, EXACT>(e, r)) return;

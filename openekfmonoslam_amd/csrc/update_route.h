@@ -192,6 +192,17 @@ inline UpdateRoute choose_update_route(const UpdateRouteIn &in)
     return r;
 }
 
+// Everything the merged gather / assembly launch takes from the route besides the number of matches: which tables it writes
+// (planes_b: row map and row scales of L; b_in_sweep: no transposed inverse), where the column scales come from (apriori) and
+// whether it factorises the first diagonal block (not for a persistent sweep).  Two routes that agree here differ, for that
+// launch, in the count alone -- a launch that reads the count on the device serves both.
+inline bool same_gather_launch(const UpdateRoute &a, const UpdateRoute &b)
+{
+    return !a.refusal && !b.refusal && a.merged_ga == b.merged_ga && a.planes_b == b.planes_b && a.apriori == b.apriori &&
+           a.persist == b.persist && a.b_in_sweep == b.b_in_sweep && a.sharded == b.sharded && a.sym_g == b.sym_g &&
+           a.b_fp32 == b.b_fp32 && a.n == b.n && a.n_pad == b.n_pad;
+}
+
 // One launch of the launch-per-panel sweep, panels from row k0 on; have_pair: an earlier launch of this sweep was a pair launch
 // (once the 64 x 64 look-ahead inverse exists the sweep stays in pairs).
 // One panel per launch (k_chol_step) while the launch is as long as its look-ahead workgroup; two panels per launch (chol_pair.h)

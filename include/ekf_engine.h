@@ -140,6 +140,19 @@ int ekf_remove_bad_features(EkfEngine *e, int *n_removed);
 /* convertMapFeaturesInverseDepthToDepth(state, P)         EKF/MapManagement.cpp:494-521 (at most one per call;
  * converted_index receives the feature index or -1) */
 int ekf_convert_inverse_depth_to_depth(EkfEngine *e, int *converted_index);
+/* Converts EVERY inverse-depth feature whose linearity index (computeLinearityIndex, on the current state and P) is below
+ * inverseDepthLinearityIndexThreshold, in one pass; the reference converts one per call (MapManagement.cpp:494-521).
+ * *count receives the number of features converted; the first min(count, capacity) of their indices are written to
+ * converted_idx in ascending order (converted_idx may be NULL; a small capacity never prevents the conversion).  With R the
+ * block-diagonal matrix of I for kept rows and the 3x6 Jacobian of each converted feature, P' = R P R' is formed in one
+ * out-of-place pass in fp64 from the upper triangle of P (row transform, then column transform; each computed entry is
+ * rounded to the storage type once and copied to its mirror; kept x kept entries are moved bit for bit); the state dimension
+ * falls by 3 * count and no feature index changes, so descriptors, counters, templates, source patches, capture poses, patch
+ * normals and the unseen list stay where they are.  For a bitwise symmetric P the result is that of the single conversions
+ * applied in ascending order, up to rounding.  Synchronises the stream and first reports a pending
+ * asynchronous error as ekf_update_external does (then nothing is converted).  Nothing below the threshold, or an empty map:
+ * EKF_OK, *count = 0 and no byte of the engine changes.  A sharded engine: EKF_ERR_INVALID_ARG. */
+int ekf_convert_all_inverse_depth_to_depth(EkfEngine *e, int32_t *converted_idx, int capacity, int *count);
 /* the 13x13 camera block of the covariance, row-major: what EKF::step logs as StateCovarianceMatrixEstimation
  * (EKF/EKF.cpp:626) -- without moving the whole matrix */
 int ekf_get_camera_covariance(EkfEngine *e, double P13[169]);

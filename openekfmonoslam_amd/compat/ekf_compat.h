@@ -860,6 +860,15 @@ public:
         stateCovarianceMatrix.markStale(e_, ekf_state_dim(e_));
         return k;
     }
+    // every inverse-depth feature below the threshold in one pass (ekf_convert_all_inverse_depth_to_depth; the reference converts
+    // one per call); returns how many were converted
+    int convertAllMapFeaturesInverseDepthToDepth()
+    {
+        int k = 0;
+        ekf_compat::chk(e_, ekf_convert_all_inverse_depth_to_depth(e_, 0, 0, &k), "ekf_convert_all_inverse_depth_to_depth");
+        stateCovarianceMatrix.markStale(e_, ekf_state_dim(e_));
+        return k;
+    }
     // ---- external measurements between steps (ekf_update_external and its helpers): H by rows in CSR form over
     // state indices, m <= EKF_EXT_MAX_ROWS rows of <= EKF_EXT_MAX_NNZ entries.  Returns the record (NIS, whitened residual,
     // applied); throws on an error code, EKF_ERR_NOT_POSITIVE_DEFINITE included.  Resident mode: `state` is current after the

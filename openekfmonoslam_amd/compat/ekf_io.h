@@ -560,7 +560,7 @@ public:
     ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
-          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false)
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false), convertAll_(false)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -645,8 +645,14 @@ public:
             for (int i = 0; i < N; ++i)
                 if (drop[i]) idx.push_back(i);
             if (!idx.empty()) chk(ekf_remove_features(e_, idx.data(), (int)idx.size()), "ekf_remove_features");
-            int conv = -1;
-            chk(ekf_convert_inverse_depth_to_depth(e_, &conv), "ekf_convert_inverse_depth_to_depth");
+            if (convertAll_) {
+                int converted = 0;
+                chk(ekf_convert_all_inverse_depth_to_depth(e_, 0, 0, &converted), "ekf_convert_all_inverse_depth_to_depth");
+                if (log_.is_open()) log_ << "Converted to depth: " << converted << std::endl;
+            } else {
+                int conv = -1;
+                chk(ekf_convert_inverse_depth_to_depth(e_, &conv), "ekf_convert_inverse_depth_to_depth");
+            }
             if (needed > 0) addNewFeatures(needed);
         }
         if (out_.isOpened()) {
@@ -715,6 +721,10 @@ public:
         out.resize((size_t)n);
         if (n > 0) chk(ekf_get_measurement_ranks(e_, out.data(), n, &n), "ekf_get_measurement_ranks");
     }
+    // Map management converts EVERY inverse-depth feature below the linearity threshold per tick instead of the reference's one
+    // (ekf_convert_all_inverse_depth_to_depth); at any time, it takes effect with the next tick.  With it on log.txt
+    // gains one line per map-management step, "Converted to depth: K"; output.yml does not change.
+    void setConvertAll(bool on) { convertAll_ = on; }
     // Localisation on a fixed map (ekf_set_fixed_map): while on, both updates of a step move the camera state and the
     // camera's rows and columns of P alone (the Schmidt-Kalman update), and step() skips the whole map-management block -- nothing
     // is removed, converted or added -- so the number of features and their parameters stay as they are; at any time, it takes
@@ -855,6 +865,7 @@ private:
     bool patchNormals_; // setPatchNormals(true): writeMapPly adds the normals
     int budget_;        // setMeasurementBudget(K)
     bool fixedMap_;     // setFixedMap(on)
+    bool convertAll_;   // setConvertAll(on)
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

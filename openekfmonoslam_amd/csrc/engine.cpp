@@ -816,6 +816,16 @@ int ekf_add_features(EkfEngine *e, const double *uv, const uint8_t *desc32, int 
     return check_async(e);
 }
 
+// the out-of-place passes over P (compaction, batch conversion) write d.P2, allocated by the first of them
+static int second_P(EkfEngine *e)
+{
+    if (e->d.P2) return EKF_OK;
+    const size_t bytes = (size_t)round_up(e->ncap, LD_ALIGN) * e->ldP * (e->f32 ? 4 : 8);
+    const hipError_t st = e->bufs.alloc_bytes(&e->d.P2, bytes); // zeroed, or not kept
+    if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc P2");
+    return EKF_OK;
+}
+
 // drop the listed rows (sorted row flags) from P and the listed features from the SoA arrays
 static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, const std::vector<uint8_t> &drop_row)
 {
@@ -825,11 +835,7 @@ static int compact_map(EkfEngine *e, const std::vector<uint8_t> &drop_feature, c
     for (int i = 0; i < n; ++i)
         if (!drop_row[i]) new2old.push_back(i);
     const int n_new = (int)new2old.size();
-    if (!e->d.P2) {
-        const size_t bytes = (size_t)round_up(e->ncap, LD_ALIGN) * e->ldP * (e->f32 ? 4 : 8);
-        const hipError_t st = e->bufs.alloc_bytes(&e->d.P2, bytes); // zeroed, or not kept
-        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc P2");
-    }
+    if (const int rc = second_P(e)) return rc;
     HIPCHK(hipMemcpyAsync(e->d.mm_index, new2old.data(), (size_t)n_new * sizeof(int), hipMemcpyHostToDevice, e->stream));
     launch_compact_P(e, n_new, e->d.mm_index);
     // SoA arrays: small, compacted through the host
@@ -962,6 +968,83 @@ int ekf_convert_inverse_depth_to_depth(EkfEngine *e, int *converted_index)
     dr[pos + 3] = dr[pos + 4] = dr[pos + 5] = 1;
     if (converted_index) *converted_index = fi;
     return compact_map(e, df, dr);
+}
+
+// Every inverse-depth feature below the threshold in one pass.  No feature index changes, so the tables keyed by
+// feature index stay where they are: only types, positions, covpos and P are rewritten.
+int ekf_convert_all_inverse_depth_to_depth(EkfEngine *e, int32_t *converted_idx, int capacity, int *count)
+{
+    if (!e || !count || capacity < 0) return EKF_ERR_INVALID_ARG;
+    *count = 0;
+    NOT_WHEN_SHARDED(e)
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc = take_pending_error(e); // as ekf_update_external: the failed update it reports is not this call's
+    if (rc) return rc;
+    const int N = e->N;
+    if (N == 0) return EKF_OK;
+    double *d_li = e->d.mm_scratch;
+    launch_linearity(e, d_li);
+    std::vector<double> li(N);
+    HIPCHK(hipMemcpyAsync(li.data(), d_li, (size_t)N * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<int> sel;
+    for (int i = 0; i < N; ++i) // the comparison of the single conversion (:494-521), without its "first one only"
+        if (e->h_type[i] == EKF_FEATURE_INVERSE_DEPTH && li[i] < e->cfg.par.inverseDepthLinearityIndexThreshold) sel.push_back(i);
+    const int K = (int)sel.size();
+    if (K == 0) return EKF_OK;
+    if ((rc = second_P(e))) return rc;
+    if (!e->d.ca_rows) {
+        auto g = e->bufs.group();
+        g.alloc(&e->d.ca_rows, (size_t)2 * e->ncap);
+        g.alloc(&e->d.ca_J, (size_t)18 * e->cap);
+        g.alloc(&e->d.ca_sel, (size_t)e->cap);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "batch conversion tables");
+    }
+    // the row table of the new matrix and the new layout, from the host mirrors
+    std::vector<int> rows, covpos(N);
+    rows.reserve(2 * (size_t)e->n);
+    for (int i = 0; i < 13; ++i) {
+        rows.push_back(i);
+        rows.push_back(-1);
+    }
+    for (int f = 0, k = 0; f < N; ++f) {
+        covpos[f] = (int)(rows.size() / 2);
+        const bool conv = k < K && sel[k] == f;
+        const int d = conv ? 3 : dims_of(e->h_type[f]);
+        for (int a = 0; a < d; ++a) {
+            rows.push_back(conv ? e->h_covpos[f] : e->h_covpos[f] + a);
+            rows.push_back(conv ? 3 * k + a : -1);
+        }
+        if (conv) ++k;
+    }
+    const int n_new = (int)(rows.size() / 2);
+    if (n_new != e->n - 3 * K) {
+        e->err = "batch conversion: layout mismatch";
+        return EKF_ERR_INVALID_ARG;
+    }
+    for (int v0 = 0; v0 < n_new; v0 += CA_TILE) { // the old columns a tile of the kernel reads must fit its LDS rows
+        const int vl = std::min(v0 + CA_TILE, n_new) - 1;
+        if (rows[2 * vl] + (rows[2 * vl + 1] >= 0 ? 6 : 1) - rows[2 * v0] > CA_CW) {
+            e->err = "batch conversion: a tile spans more old columns than the kernel holds";
+            return EKF_ERR_INVALID_ARG;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(e->d.ca_sel, sel.data(), (size_t)K * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d.ca_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d.feat_covpos, covpos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    launch_convert_all(e, K, n_new);
+    HIPCHK(hipStreamSynchronize(e->stream)); // (the host vectors above are the sources of the copies)
+    for (int k = 0; k < K; ++k) e->h_type[sel[k]] = EKF_FEATURE_DEPTH;
+    e->h_covpos = covpos;
+    e->n = n_new;
+    refresh_row_map(e);
+    e->n_pred = 0;
+    e->last_match_warped = false; // as a compaction leaves it
+    *count = K;
+    if (converted_idx)
+        for (int k = 0; k < K && k < capacity; ++k) converted_idx[k] = sel[k];
+    return check_async(e);
 }
 
 // ----------------------------------------------------------------------------------------------- utilities

@@ -135,9 +135,13 @@ struct DeviceArrays {
     unsigned *feat_times_predicted = nullptr; // MapFeature::timesPredicted / timesMatched (EKF/MapFeature.h:72-73)
     unsigned *feat_times_matched = nullptr;
     void *P = nullptr; // T [ncap x ldP]
-    void *P2 = nullptr; // second buffer of the same size, allocated on the first removal (compaction target)
+    void *P2 = nullptr; // second buffer of the same size, allocated by the first out-of-place pass (compaction, batch conversion: its target)
     double *mm_scratch = nullptr; // map management scratch: Jpo/Jhr of a batch, 3 x ldP conversion rows, N linearity values
     int *mm_index = nullptr;      // new2old row map (ncap ints)
+    // batch conversion (ekf_convert_all_inverse_depth_to_depth; allocated by its first conversion)
+    int *ca_rows = nullptr;       // per row u of the new matrix: first source row s(u), then row 3 k + a of ca_J or -1 for a kept row (2 x ncap ints)
+    double *ca_J = nullptr;       // the 3 x 6 Jacobian of the k-th converted feature, in ascending feature order (18 x cap doubles)
+    int *ca_sel = nullptr;        // the converted feature indices, ascending (cap ints)
     EkfMapPoint *map_points = nullptr; // ekf_get_map_points: cap records, allocated by its first call
     // prediction tables, keyed by feature index
     int *pred_vis = nullptr;      // visibility per feature, latest prediction (full or subset)
@@ -581,6 +585,12 @@ void launch_add_features(EkfEngine *e, const double *d_uv, int count, double *d_
 void launch_compact_P(EkfEngine *e, int n_new, const int *d_new2old);
 void launch_linearity(EkfEngine *e, double *d_out);
 void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3);
+// k_convert_all_P: tiles of CA_TILE x CA_TILE entries of the new matrix; the old columns one tile's columns read fit CA_CW (22 converted
+// features at most: 1 + 20 x 3 + 3 new columns), which the host checks on the row table it builds
+constexpr int CA_TILE = 64, CA_CW = 132;
+// batch conversion: X, J and the type of the `count` features in d.ca_sel, then P' = R P R' from d.P into d.P2 by the row table in
+// d.ca_rows (n_new rows), and the swap of the two buffers
+void launch_convert_all(EkfEngine *e, int count, int n_new);
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
 // external measurement update (kernels_external.hip): the call's ExtCtl is in d.ext_ctl; enqueues A = H P, the solve, the state
 // update, the downdate and the normalisation of the covariance, and leaves the record in d.ext_res

@@ -254,6 +254,128 @@ __global__ void __launch_bounds__(256) k_convert_apply(T *P, int ld, int n, int 
     }
 }
 
+// ---------------------------------------------------------------- every linear feature at once
+// k_convert_prepare for the count features listed in sel (ascending): J of the k-th one to J + 18 k; one thread per feature.
+__global__ void __launch_bounds__(64) k_convert_all_prepare(double *feat_pos, int *feat_type, const int *sel, int count, double *J)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= count) return;
+    const int fi = sel[k];
+    double *p = feat_pos + 6 * (size_t)fi;
+    const double theta = p[3], phi = p[4], rho = p[5];
+    double mi[3];
+    dir_vec(theta, phi, mi);
+    inverse_depth_to_xyz_jacobian(theta, phi, rho, mi, J + 18 * (size_t)k);
+    p[0] += mi[0] / rho; p[1] += mi[1] / rho; p[2] += mi[2] / rho;
+    p[3] = p[4] = p[5] = 0.0;
+    feat_type[fi] = EKF_FEATURE_DEPTH;
+}
+
+// P2 = R P R', R block diagonal: 1 for a kept row, the 3 x 6 Jacobian of every converted feature.  rows[2 u], rows[2 u + 1]: the
+// first source row s(u) of new row u and its row of Jtab (6 weights over rows s(u) .. s(u) + 5), or -1 for a kept row (weight 1).
+// One workgroup per 64 x 64 tile (ty, tx), tx >= ty, of the new matrix, and its mirror image:
+//   1. CA_ROWS new rows at a time, T[u][c] = sum_a w_u[a] P[s(u) + a][c] over the old columns c the tile's columns read (at most
+//      CA_CW of them: 64 new columns touch at most 22 converted features), consecutive threads along c, into LDS as doubles;
+//   2. P'[u][v] = sum_b T[u][s(v) + b] w_v[b] (T[u][s(v)] for a kept column), lane = column, rounded to T once, stored along the
+//      row where u <= v and kept in LDS;
+//   3. the mirror image (tile (tx, ty); in the diagonal tile the entries below the diagonal) is stored along ITS rows: a kept x
+//      kept entry is moved from P[s(v)][s(u)], every other entry is the LDS copy of its twin.
+// Kept x kept entries pass through a double and back, which is the identity for a float and for a double.  Only the upper
+// triangle of P and the diagonal blocks of the converted features reach a computed entry that is stored.  All arithmetic is fp64.
+constexpr int CA_ROWS = 16, CA_BATCH = 4, CA_LDT = CA_CW + 1, CA_LDO = CA_TILE + 1; // (CA_TILE, CA_CW: engine.h)
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_convert_all_P(const T *__restrict__ P, T *__restrict__ P2, int ld, int n_new, const int *__restrict__ rows, const double *__restrict__ Jtab)
+{
+    const int ty = blockIdx.y, tx = blockIdx.x;
+    if (tx < ty) return; // (the whole workgroup: no barrier is skipped)
+    __shared__ double sT[CA_ROWS * CA_LDT];
+    __shared__ T sO[CA_TILE * CA_LDO];
+    __shared__ int sS[2][CA_TILE], sJ[2][CA_TILE]; // s(.) and the Jtab row of the tile's rows [0] and columns [1]
+    __shared__ double sW[CA_TILE][6];              // the weights of the tile's converted rows
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int u0 = ty * CA_TILE, v0 = tx * CA_TILE;
+    if (t < 2 * CA_TILE) {
+        const int g = (w ? v0 : u0) + lane;
+        sS[w][lane] = g < n_new ? rows[2 * g] : 0;
+        sJ[w][lane] = g < n_new ? rows[2 * g + 1] : -1;
+    }
+    __syncthreads();
+    for (int i = t; i < CA_TILE * 6; i += 256)
+        sW[i / 6][i % 6] = sJ[0][i / 6] >= 0 ? Jtab[6 * (size_t)sJ[0][i / 6] + i % 6] : 0.0;
+    __syncthreads();
+    const int vl = min(CA_TILE, n_new - v0) - 1; // the tile's last live column
+    const int c0 = sS[1][0], cw = sS[1][vl] + (sJ[1][vl] >= 0 ? 6 : 1) - c0; // the old columns c0 .. c0 + cw - 1; cw <= CA_CW
+    const int v = v0 + lane, cs = sS[1][lane] - c0, jv = sJ[1][lane];
+    double wv[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) wv[b] = jv >= 0 ? Jtab[6 * (size_t)jv + b] : 0.0;
+    for (int h = 0; h < CA_TILE; h += CA_ROWS) {
+        // entry e = r cw + cc of the strip to thread e mod 256: CA_BATCH entries per thread with all their loads issued before the
+        // first sum (each entry alone would leave one DRAM latency per six loads exposed)
+        const int total = min(CA_ROWS, n_new - u0 - h) * cw; // (<= 0 behind the last row)
+        for (int e0 = t; e0 < total; e0 += 256 * CA_BATCH) {
+            T pv[CA_BATCH][6];
+            int at[CA_BATCH], row[CA_BATCH];
+#pragma unroll
+            for (int k = 0; k < CA_BATCH; ++k) {
+                const int e = e0 + 256 * k;
+                row[k] = -1;
+                if (e >= total) continue;
+                const int r = e / cw, cc = e - r * cw;
+                row[k] = h + r;
+                at[k] = r * CA_LDT + cc;
+                const T *p = P + (size_t)sS[0][h + r] * ld + c0 + cc;
+                pv[k][0] = p[0];
+                if (sJ[0][h + r] >= 0) {
+#pragma unroll
+                    for (int a = 1; a < 6; ++a) pv[k][a] = p[(size_t)a * ld];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CA_BATCH; ++k) {
+                if (row[k] < 0) continue;
+                double s;
+                if (sJ[0][row[k]] < 0) {
+                    s = (double)pv[k][0];
+                } else {
+                    s = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) s += sW[row[k]][a] * (double)pv[k][a];
+                }
+                sT[at[k]] = s;
+            }
+        }
+        __syncthreads();
+        for (int r = w; r < CA_ROWS; r += 4) {
+            const int u = u0 + h + r;
+            if (u >= n_new || v >= n_new) break;
+            const double *tr = sT + r * CA_LDT + cs;
+            double s;
+            if (jv < 0) {
+                s = tr[0];
+            } else {
+                s = 0.0;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) s += tr[b] * wv[b];
+            }
+            const T o = (T)s;
+            sO[(h + r) * CA_LDO + lane] = o;
+            if (u <= v) P2[(size_t)u * ld + v] = o;
+        }
+        __syncthreads();
+    }
+    const int c2 = u0 + lane; // the mirror image: row v0 + i, lanes along its columns
+    for (int i = w; i < CA_TILE; i += 4) {
+        const int r2 = v0 + i;
+        if (r2 >= n_new) break;
+        if (c2 >= n_new || r2 <= c2) continue; // (r2 <= c2 only in the diagonal tile)
+        const bool moved = sJ[1][i] < 0 && sJ[0][lane] < 0;
+        P2[(size_t)r2 * ld + c2] = moved ? P[(size_t)sS[1][i] * ld + sS[0][lane]] : sO[lane * CA_LDO + i];
+    }
+}
+
 // ------------------------------------------------------------------------------------ map export (read-only)
 // ekf_get_map_points: every feature as a world point X with its 3x3 covariance, the same point in the camera's axes with
 // a covariance that includes the pose uncertainty, and the linearity index.  z = (r, q, y) with y the feature's d = 6 or
@@ -413,6 +535,19 @@ void launch_convert(EkfEngine *e, int fi, int pos, double *d_J, double *d_T3)
         k_convert_rows<double><<<nb, 256, 0, s>>>((const double *)e->d.P, e->ldP, e->n, pos, d_J, d_T3);
         k_convert_apply<double><<<nb, 256, 0, s>>>((double *)e->d.P, e->ldP, e->n, pos, d_J, d_T3);
     }
+}
+
+void launch_convert_all(EkfEngine *e, int count, int n_new)
+{
+    hipStream_t s = e->stream;
+    k_convert_all_prepare<<<(count + 63) / 64, 64, 0, s>>>(e->d.feat_pos, e->d.feat_type, e->d.ca_sel, count, e->d.ca_J);
+    const int nt = (n_new + CA_TILE - 1) / CA_TILE;
+    dim3 g(nt, nt);
+    if (e->f32) k_convert_all_P<float><<<g, 256, 0, s>>>((const float *)e->d.P, (float *)e->d.P2, e->ldP, n_new, e->d.ca_rows, e->d.ca_J);
+    else k_convert_all_P<double><<<g, 256, 0, s>>>((const double *)e->d.P, (double *)e->d.P2, e->ldP, n_new, e->d.ca_rows, e->d.ca_J);
+    void *t = e->d.P;
+    e->d.P = e->d.P2;
+    e->d.P2 = t;
 }
 
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out)

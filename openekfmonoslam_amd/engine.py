@@ -81,6 +81,7 @@ ABI = {
     "ekf_remove_features": (_i, [_vp, _vp, _i]),
     "ekf_remove_bad_features": (_i, [_vp, C.POINTER(_i)]),
     "ekf_convert_inverse_depth_to_depth": (_i, [_vp, C.POINTER(_i)]),
+    "ekf_convert_all_inverse_depth_to_depth": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ekf_get_feature_layout": (_i, [_vp, _vp, _vp]),
     "ekf_keep_step_predictions": (_i, [_vp, _i]),
     "ekf_get_step_predictions": (_i, [_vp, _vp, C.POINTER(_i)]),
@@ -535,6 +536,13 @@ class EkfEngine:
         k = _i(-1)
         self._chk(self.L.ekf_convert_inverse_depth_to_depth(self.h, C.byref(k)))
         return k.value
+
+    def convert_all_inverse_depth_to_depth(self):
+        """every inverse-depth feature below the linearity threshold, in one pass -> their indices, ascending (int32)"""
+        idx = np.zeros(max(self.N, 1), dtype=np.int32)
+        k = _i(0)
+        self._chk(self.L.ekf_convert_all_inverse_depth_to_depth(self.h, _p(idx), self.N, C.byref(k)))
+        return idx[: k.value].copy()
 
     def feature_layout(self):
         t = np.zeros(max(self.N, 1), dtype=np.int32)

@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -22,6 +22,8 @@
 // --fixed-map-from FRAME (likewise): map as always up to FRAME, then localise -- from the step that prints "step FRAME" on the map
 // is fixed (ImageEKF::setFixedMap): both updates move the camera alone, map management is skipped, "fixed map: on" is printed under
 // the step line; the covariance carries over from the mapping frames as it is.
+// --convert-all (likewise): every map-management tick converts EVERY inverse-depth feature below the linearity threshold to XYZ
+// instead of the reference's one (ImageEKF::setConvertAll); log.txt gains "Converted to depth: K" per tick.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -59,7 +61,7 @@ static void readPositionFixes(const std::string &path, std::vector<PositionFix> 
 
 int main(int argc, const char *argv[])
 {
-    bool warp = false, subpix = false, wide = false, normals = false, consistency = false; // the flags are taken out of the argument list; the positional arguments keep their places
+    bool warp = false, subpix = false, wide = false, normals = false, consistency = false, convertAll = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
     int budget = 0, fixedFrom = -1;
     std::string fixesFile;
@@ -74,16 +76,17 @@ int main(int argc, const char *argv[])
             argc -= 2;
             --i;
         } else if (std::string(argv[i]) == "--warp-templates" || std::string(argv[i]) == "--subpixel" || std::string(argv[i]) == "--wide-search" ||
-            std::string(argv[i]) == "--patch-normals" || std::string(argv[i]) == "--consistency") {
+            std::string(argv[i]) == "--patch-normals" || std::string(argv[i]) == "--consistency" || std::string(argv[i]) == "--convert-all") {
             if (std::string(argv[i]) == "--patch-normals") normals = true;
-            if (std::string(argv[i]) == "--consistency") consistency = true;
+            if (std::string(argv[i]) == "--convert-all") convertAll = true;
+            else if (std::string(argv[i]) == "--consistency") consistency = true;
             else (std::string(argv[i]) == "--subpixel" ? subpix : std::string(argv[i]) == "--wide-search" ? wide : warp) = true;
             for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
             --argc;
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -98,7 +101,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -116,7 +119,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes or a fixed map asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map or the batch conversion asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -125,6 +128,7 @@ int main(int argc, const char *argv[])
         extendedKalmanFilter.setNccDistinct(distinct);
         extendedKalmanFilter.setConsistency(consistency);
         extendedKalmanFilter.setMeasurementBudget(budget);
+        extendedKalmanFilter.setConvertAll(convertAll);
         std::vector<PositionFix> fixes;
         if (!fixesFile.empty()) readPositionFixes(fixesFile, fixes);
         std::FILE *csv = 0;

@@ -284,6 +284,34 @@ int ekf_get_fixed_map(const EkfEngine *e, int *on, int64_t *updates);
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);
 
+/* Frame intervals.  The reference predicts over dt = 1 (StateAndCovariancePrediction.cpp:246); here the interval
+ * is a number: r += v dt, q <- q (x) quat(w dt), Q = diag(SD^2 dt^2).  One unit is the period linearAccelSD and angularAccelSD
+ * were tuned for -- the nominal frame period -- so a frame that follows k dropped ones gets dt = k + 1.  One prediction over
+ * dt = 2 is not two over dt = 1: the velocity impulse is drawn once per prediction.
+ * ekf_set_frame_interval: the interval ekf_predict and every step function (ekf_step, ekf_step_frame, ekf_step_image,
+ * ekf_step_staged_image) use from now on.  Default 1.0, with which every result is bit for bit that of an engine that was never
+ * told an interval.  ekf_predict_dt: one prediction over dt; the set interval is left alone.
+ * ekf_set_staged_intervals: per-index intervals of a pre-staged sequence, kept on the host (the value reaches the kernel as an
+ * argument: no copy, no synchronisation per frame).  ekf_step_frame(i) and ekf_step_staged_image(i) use dt[i] for i < n and the
+ * set interval otherwise; n = 0 clears the table (dt may then be NULL).
+ * EKF_ERR_INVALID_ARG, with a message in ekf_last_error, nothing launched and nothing changed: a dt -- or any entry of a table --
+ * that is not finite or not greater than 0; n < 0; n > 0 with dt NULL.
+ * A sharded engine accepts all of these; EVERY rank must be given the same value (the prediction is replicated arithmetic on the
+ * camera rows: with equal intervals P[a][j] on one rank stays bitwise P[j][a] on the owner of row j, as with dt = 1).  The fixed
+ * map, the measurement budget, consistency and the NCC options are independent of the interval. */
+int ekf_set_frame_interval(EkfEngine *e, double dt);
+int ekf_get_frame_interval(const EkfEngine *e, double *dt);
+int ekf_predict_dt(EkfEngine *e, double dt);
+int ekf_set_staged_intervals(EkfEngine *e, int n, const double *dt);
+/* Look-ahead of the camera: the camera state (x13: r, q, v, w) and the 13 x 13 camera covariance F P_cc F' + G Q G' (row-major)
+ * a prediction over tau would leave, WITHOUT making it -- where will the camera be tau from now, and how sure is the filter
+ * (latency compensation for rendering or control).  One one-workgroup launch, fp64, from the current state and the camera corner
+ * of P, with the operations of ekf_predict_dt(tau) in its order: P13 is the value that prediction rounds to the storage type of P
+ * (in the fp64-stored configurations: the corner it leaves, bit for bit).  Read-only: the kernel writes its own 182-double
+ * buffer (allocated at creation) and nothing else -- not the state, not P, no per-frame table.  Either output may be NULL.
+ * Synchronises the stream.  tau is validated as dt above.  On a sharded engine the camera rows are replicated: any rank answers. */
+int ekf_predict_camera_ahead(const EkfEngine *e, double tau, double x13[13], double P13[169]);
+
 /* predictCameraMeasurements(state, P, features, featureIndexes, preds, jacobians, notPredicted)
  *                                                        EKF/MeasurementPrediction.h:59 (.cpp:705-719)
  * feat_idx == NULL / count == 0 predicts every map feature.  Outputs (all optional): predictions in input order,
@@ -322,7 +350,7 @@ int ekf_update_only_state(EkfEngine *e, const EkfMatch *matches, int M);
 int ekf_rescue(EkfEngine *e, const EkfMatch *outliers, int M, uint8_t *rescued_mask);
 
 /* EKF::step(image) with a fixed map                      EKF/EKF.h:57 (.cpp:242-572, including updateMapFeatures),
- * fed the frame's keypoints. */
+ * fed the frame's keypoints.  Its prediction runs over the interval of ekf_set_frame_interval (default 1). */
 int ekf_step(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_kp, EkfStepInfo *info);
 
 /* -- pre-staged sequences (inputs resident in HBM before a timed region) ---------------------------------- */

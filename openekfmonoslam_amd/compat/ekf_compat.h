@@ -592,6 +592,15 @@ inline void stateAndCovariancePrediction(State &state, Matd &covarianceMatrix)
     c.changed(state, &covarianceMatrix);
 }
 
+// ... over an interval of dt frame periods instead of the reference's 1 (ekf_predict_dt); residency as above
+inline void stateAndCovariancePrediction(State &state, Matd &covarianceMatrix, double dt)
+{
+    ekf_compat::Context &c = ekf_compat::Context::instance();
+    c.ensure(state, &covarianceMatrix);
+    c.check(ekf_predict_dt(c.engine(), dt), "ekf_predict_dt");
+    c.changed(state, &covarianceMatrix);
+}
+
 inline void predictCameraMeasurements(const State &state, const Matd &predictedStateCovariance, const VectorMapFeature &features,
                                       const std::vector<int> &featureIndexes, VectorImageFeaturePrediction &predictedDistortedFeatures,
                                       VectorMatd &predictedFeatureJacobians, VectorMapFeature &notPredictedFeatures)
@@ -790,6 +799,7 @@ public:
     EKF(const char *configurationFileName, const char *outputPath); // EKF.h:44   (ekf_io.h)
     void init(const cv::Mat &image);                                // EKF.h:47   (ekf_io.h)
     void step(const cv::Mat &image);                                // EKF.h:48   (ekf_io.h)
+    void step(const cv::Mat &image, double dt);                     // ... over dt frame periods (ekf_set_frame_interval; ekf_io.h)
 
     EKF(const EkfCamera &cam, const EkfParams &par, int maxFeatures, int precision = EKF_PRECISION_F64)
         : e_(0), steps_(0), drv_(0), drvDelete_(0)

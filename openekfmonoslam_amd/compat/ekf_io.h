@@ -292,11 +292,71 @@ public:
         return img;
     }
     int nextIndex() const { return index_; }
+    // how many images getNextImage() will still deliver: the files from the next index up to the end index or the first missing one
+    int remaining() const
+    {
+        int n = 0;
+        for (int i = index_; i <= end_; ++i, ++n) {
+            char name[32];
+            std::snprintf(name, sizeof(name), "%05d", i);
+            std::FILE *f = std::fopen((path_ + prefix_ + name + "." + ext_).c_str(), "rb");
+            if (!f) break;
+            std::fclose(f);
+        }
+        return n;
+    }
 
 private:
     std::string path_, prefix_, ext_;
     int index_, end_;
 };
+
+// Frame times for ImageEKF::setFrameInterval: one time per frame in seconds, in frame order, one per line (# starts a comment,
+// empty lines are skipped).  `frames` times, strictly increasing, or an exception -- before any frame is processed.
+// intervals[i], i >= 1, = (t[i] - t[i - 1]) / unit is the interval of the step on frame i; intervals[0] (the frame init() takes) = 0.
+// unit: the nominal frame period in seconds -- the period the configuration's linearAccelSD and angularAccelSD were tuned for, so
+// that they keep their meaning; a frame after k dropped ones then gets k + 1.
+inline void readFrameIntervals(const std::string &path, double unit, int frames, std::vector<double> &intervals)
+{
+    if (!(unit > 0.0) || unit > 1.7e308) throw std::runtime_error("the time unit must be a finite number of seconds greater than 0");
+    std::FILE *f = std::fopen(path.c_str(), "r");
+    if (!f) throw std::runtime_error("cannot read " + path);
+    std::vector<double> t;
+    char line[512];
+    for (int no = 1; std::fgets(line, sizeof(line), f); ++no) {
+        std::string text(line);
+        text = text.substr(0, text.find('#'));
+        if (text.find_first_not_of(" \t\r\n") == std::string::npos) continue;
+        char *end = 0;
+        const double v = std::strtod(text.c_str(), &end);
+        char where[32];
+        std::snprintf(where, sizeof(where), ":%d", no);
+        if (end == text.c_str() || std::string(end).find_first_not_of(" \t\r\n") != std::string::npos || !(v - v == 0.0)) {
+            std::fclose(f);
+            throw std::runtime_error(path + where + ": expected one finite time in seconds");
+        }
+        if (!t.empty() && !(v > t.back())) {
+            std::fclose(f);
+            throw std::runtime_error(path + where + ": the times must increase from frame to frame");
+        }
+        t.push_back(v);
+    }
+    std::fclose(f);
+    if ((int)t.size() != frames) {
+        std::ostringstream msg;
+        msg << path << ": " << t.size() << " times for " << frames << " frames";
+        throw std::runtime_error(msg.str());
+    }
+    intervals.assign(t.size(), 0.0);
+    for (size_t i = 1; i < t.size(); ++i) {
+        intervals[i] = (t[i] - t[i - 1]) / unit;
+        if (!(intervals[i] > 0.0) || intervals[i] > 1.7e308) { // (two times closer than the unit can resolve)
+            std::ostringstream msg;
+            msg << path << ": the interval before frame " << i << " is not a finite number greater than 0 in units of " << unit << " s";
+            throw std::runtime_error(msg.str());
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------------------- prediction image
 // drawPrediction (Gui/Draw.cpp:266-310): the frame with, per predicted feature, a 5-pixel cross (drawPoint :66-70), the
@@ -560,7 +620,8 @@ public:
     ImageEKF(const char *pathConfigFile, const char *outputPath, int precision = EKF_PRECISION_F64, double detectorThreshold = 1e9,
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
-          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false), convertAll_(false)
+          keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false), convertAll_(false),
+          interval_(1.0), intervalSet_(false)
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -604,6 +665,7 @@ public:
             log_ << std::endl << std::endl;
             log_ << "~~~~~~~~~~~~ STEP " << steps_ << " ~~~~~~~~~~~~" << std::endl;
             if (fixedMap_) log_ << "Fixed map: on" << std::endl;
+            if (intervalSet_) log_ << "Frame interval: dt = " << interval_ << std::endl;
         }
         EkfStepInfo info;
         if (out_.isOpened()) ekf_timing_reset(e_);
@@ -737,6 +799,17 @@ public:
         fixedMap_ = on;
     }
     bool fixedMap() const { return fixedMap_; }
+    // Frame intervals (ekf_set_frame_interval): the interval the prediction of every following step runs over, in
+    // units of the frame period linearAccelSD / angularAccelSD were tuned for (default 1; a frame after k dropped ones: k + 1); at
+    // any time, it takes effect with the next step.  Once it has been called log.txt gains one line per step, "Frame interval:
+    // dt = D"; with dt = 1 output.yml does not change.  Throws for a dt that is not finite or not greater than 0.
+    void setFrameInterval(double dt)
+    {
+        chk(ekf_set_frame_interval(e_, dt), "ekf_set_frame_interval");
+        interval_ = dt;
+        intervalSet_ = true;
+    }
+    double frameInterval() const { return interval_; }
     // External measurements between steps (ekf_update_external and its helpers): H by rows in CSR form over state
     // indices; a fix of the camera position; a measured distance between two map features.  They return the record (NIS, whitened
     // residual, applied) and throw on an error code.  output.yml and log.txt do not change.
@@ -866,6 +939,8 @@ private:
     int budget_;        // setMeasurementBudget(K)
     bool fixedMap_;     // setFixedMap(on)
     bool convertAll_;   // setConvertAll(on)
+    double interval_;   // setFrameInterval(dt)
+    bool intervalSet_;  // ... has been called: log.txt carries the interval of every step
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;
@@ -927,5 +1002,13 @@ inline void EKF::step(const cv::Mat &image)
     refreshLayout(); // the reference's public attributes are current after a step: `state` now, the covariance on first access
     ekf_compat::download(e_, state, 0);
     stateCovarianceMatrix.markStale(e_, ekf_state_dim(e_));
+}
+
+// step(image) for a frame that came dt frame periods after the previous one (ImageEKF::setFrameInterval; the interval stays set)
+inline void EKF::step(const cv::Mat &image, double dt)
+{
+    if (!drv_) throw ekf_compat::Error(EKF_ERR_INVALID_ARG, "EKF::step(image, dt) needs the EKF(configurationFileName, outputPath) constructor");
+    drv_->setFrameInterval(dt);
+    step(image);
 }
 #endif // EKF_IO_H

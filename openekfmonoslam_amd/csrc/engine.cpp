@@ -233,6 +233,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     if ((st = e->bufs.call) != hipSuccess) return fail(st, "hipMalloc " name)
 #define ALLOC(ptr, count) ALLOC_AS(#ptr, alloc(&(ptr), (count)))
     ALLOC(d.state, ST_COUNT);
+    ALLOC(d.cam_ahead, 13 + 169);
     ALLOC(d.feat_pos, 6 * cap);
     ALLOC(d.feat_type, cap);
     ALLOC(d.feat_covpos, cap);
@@ -1113,8 +1114,72 @@ int ekf_predict(EkfEngine *e)
 {
     if (!e) return EKF_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(e->device));
-    launch_predict(e);
+    launch_predict(e, e->frame_interval);
     return check_async(e);
+}
+
+// ---- frame intervals: an interval is finite and greater than 0, or the call does nothing
+static bool valid_interval(double dt) { return std::isfinite(dt) && dt > 0.0; }
+
+static int bad_interval(const EkfEngine *e, const char *who, const char *what, double dt)
+{
+    const_cast<EkfEngine *>(e)->err = std::string(who) + ": " + what + " = " + std::to_string(dt) + " is not a finite interval greater than 0";
+    return EKF_ERR_INVALID_ARG;
+}
+
+// the interval of staged frame i: its entry of ekf_set_staged_intervals' table, the set interval beyond the table
+static double staged_interval(const EkfEngine *e, int frame)
+{
+    return frame >= 0 && (size_t)frame < e->staged_dt.size() ? e->staged_dt[frame] : e->frame_interval;
+}
+
+int ekf_set_frame_interval(EkfEngine *e, double dt)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (!valid_interval(dt)) return bad_interval(e, "ekf_set_frame_interval", "dt", dt);
+    e->frame_interval = dt;
+    return EKF_OK;
+}
+
+int ekf_get_frame_interval(const EkfEngine *e, double *dt)
+{
+    if (!e || !dt) return EKF_ERR_INVALID_ARG;
+    *dt = e->frame_interval;
+    return EKF_OK;
+}
+
+int ekf_predict_dt(EkfEngine *e, double dt)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (!valid_interval(dt)) return bad_interval(e, "ekf_predict_dt", "dt", dt);
+    HIPCHK(hipSetDevice(e->device));
+    launch_predict(e, dt);
+    return check_async(e);
+}
+
+int ekf_set_staged_intervals(EkfEngine *e, int n, const double *dt)
+{
+    if (!e || n < 0 || (n > 0 && !dt)) return EKF_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i)
+        if (!valid_interval(dt[i])) return bad_interval(e, "ekf_set_staged_intervals", ("dt[" + std::to_string(i) + "]").c_str(), dt[i]);
+    e->staged_dt.assign(dt, dt + n);
+    return EKF_OK;
+}
+
+int ekf_predict_camera_ahead(const EkfEngine *ce, double tau, double x13[13], double P13[169])
+{
+    if (!ce) return EKF_ERR_INVALID_ARG;
+    EkfEngine *e = const_cast<EkfEngine *>(ce); // (the message of a failure is the only thing of the engine written here)
+    if (!valid_interval(tau)) return bad_interval(e, "ekf_predict_camera_ahead", "tau", tau);
+    HIPCHK(hipSetDevice(e->device));
+    launch_camera_ahead(e, tau, e->d.cam_ahead);
+    HIPCHK(hipGetLastError());
+    double h[13 + 169];
+    HIPCHK(hipMemcpyAsync(h, e->d.cam_ahead, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (x13) std::memcpy(x13, h, 13 * sizeof(double));
+    if (P13) std::memcpy(P13, h + 13, 169 * sizeof(double));
+    return EKF_OK;
 }
 
 // Sharded filter: the FULL exchange of the H.P table (2N x ldP: 192 MB at N = 2000, 1.2 GB at N = 5000 in fp32) and of its
@@ -1883,10 +1948,10 @@ restart:
     int np = 0;
     if (dev_counts) { // covariance strips and pixel predictions in one launch; with more than 256 features the compaction of
                       // the predicted list rides in the launch of the H P rows
-        const bool deferred = launch_predict_with_features(e, e->N);
+        const bool deferred = launch_predict_with_features(e, e->N, e->step_dt);
         launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred, true); // + the matcher's gates
     } else {
-        launch_predict(e);
+        launch_predict(e, e->step_dt);
         if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean, budget_active ? e->budget_K : 0))) return rc;
     }
     tm.mark();
@@ -2057,6 +2122,7 @@ int ekf_step(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_
     HIPCHK(hipSetDevice(e->device));
     int rc = upload_keypoints(e, kps, desc32, n_kp);
     if (rc) return rc;
+    e->step_dt = e->frame_interval;
     return step_dev(e, e->d.kps, e->d.kdesc, n_kp, info);
 }
 
@@ -2096,6 +2162,7 @@ int ekf_step_frame(EkfEngine *e, int frame, EkfStepInfo *info)
     if (!e || frame < 0 || frame >= e->frames.n) return EKF_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(e->device));
     const size_t off = (size_t)e->frames.offset[frame];
+    e->step_dt = staged_interval(e, frame);
     return step_dev(e, e->frames.kps + off, e->frames.desc + off * e->desc_bytes, e->frames.count[frame], info);
 }
 
@@ -2910,6 +2977,7 @@ int ekf_step_image(EkfEngine *e, const uint8_t *image, int width, int height, in
 {
     int rc = ekf_image_upload(e, image, width, height, stride, channels);
     if (rc) return rc;
+    e->step_dt = e->frame_interval;
     return step_image_dev(e, info);
 }
 
@@ -2976,6 +3044,7 @@ int ekf_step_staged_image(EkfEngine *e, int frame, EkfStepInfo *info)
     HIPCHK(hipSetDevice(e->device));
     int rc = staged_pyramid(e, frame);
     if (rc) return rc;
+    e->step_dt = staged_interval(e, frame);
     return step_image_dev(e, info);
 }
 

@@ -142,6 +142,7 @@ struct DeviceArrays {
     int *ca_rows = nullptr;       // per row u of the new matrix: first source row s(u), then row 3 k + a of ca_J or -1 for a kept row (2 x ncap ints)
     double *ca_J = nullptr;       // the 3 x 6 Jacobian of the k-th converted feature, in ascending feature order (18 x cap doubles)
     int *ca_sel = nullptr;        // the converted feature indices, ascending (cap ints)
+    double *cam_ahead = nullptr;  // ekf_predict_camera_ahead: 13 + 169 doubles, the only thing its kernel writes
     EkfMapPoint *map_points = nullptr; // ekf_get_map_points: cap records, allocated by its first call
     // prediction tables, keyed by feature index
     int *pred_vis = nullptr;      // visibility per feature, latest prediction (full or subset)
@@ -389,6 +390,9 @@ struct EkfEngine {
     int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
     int cons_stage = 0;            // stage the next covered update records: 0 ekf_update, 1 a step's first update, 2 its second
     int last_update_stage = 0;     // ... and that of the last update enqueued (its retry records the same stage)
+    double frame_interval = 1.0;   // ekf_set_frame_interval: the dt of ekf_predict and of every step function
+    double step_dt = 1.0;          // the interval of the step being run: frame_interval, or the staged table's entry of its frame
+    std::vector<double> staged_dt; // ekf_set_staged_intervals: per index of a pre-staged sequence, kept on the host (the value is a kernel argument)
     int budget_K = 0;              // ekf_set_measurement_budget: 0 = off, else a step measures at most this many features
     int bud_recs_n = 0;            // records in d.bud_recs: predicted features of the last step if the budget was active in it, else 0
     int bud_predicted = 0, bud_selected = 0; // the last step's full prediction: features predicted / handed on (equal when the budget did not bind)
@@ -534,10 +538,11 @@ __device__ __forceinline__ int block_exclusive_scan_1024(int c, int *wtot /* __s
 #endif
 
 // ---- launchers (kernels_*.hip) ; T selected by e->f32 ----------------------------------------------------
-void launch_predict(EkfEngine *e);
+void launch_predict(EkfEngine *e, double dt); // one prediction over the interval dt (> 0, finite: the ABI checks)
+void launch_camera_ahead(const EkfEngine *e, double tau, double *d_out); // read-only: x13 and the camera corner at horizon tau -> 13 + 169 doubles
 // full (idx == nullptr) or subset prediction; fills tables, compacted list and CNT_NPRED / CNT_NPRED_SUB
 bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool state_only, bool defer_compact = false);
-bool launch_predict_with_features(EkfEngine *e, int count); // step path: prepare, then covariance strips + all features in one launch
+bool launch_predict_with_features(EkfEngine *e, int count, double dt); // step path: prepare, then covariance strips + all features in one launch
 // d_count != nullptr: n_list is an upper bound, the list's length is read on the device
 void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false,
                     bool gates = false);

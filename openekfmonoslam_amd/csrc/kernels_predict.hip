@@ -9,37 +9,19 @@
 
 namespace ekf {
 
-__device__ void predict_prepare_serial(double *st, double *sG);
-
-// ------------------------------------------------------------------------------------------------ A1 + A2
-// F (13x13), G Q G' (13x13) from the PRE-prediction state, then the state prediction itself (covariance is predicted before
-// the state, :251-252; dt = 1, :246).  One workgroup: thread 0 forms F, G and the predicted state (a chain of a few hundred dependent
-// fp64 operations); the 169 entries of G Q G' -- a thousand multiply-adds, half of the 9 us the kernel took as one thread -- are dealt
-// to the workgroup behind one barrier.
-// counts != nullptr (EKF::step's launch): a step enqueued behind a failed update leaves the filter as it is (engine.h: filter_frozen)
-__global__ void __launch_bounds__(256) k_predict_prepare(double *st, ParD par, const int *counts)
+// The constant-velocity motion model over one interval dt (StateAndCovariancePrediction.cpp:43-65, :71-225 with its dt = 1, :246, a
+// parameter): r += v dt, q <- q (x) quat(w dt); F = d x_new / d x, G = d x_new / d (velocity impulse, angular velocity impulse).
+// x_in[13] -> F[169], G[78], the predicted camera state x_out[13] and R(q_new)[9].  x_out may alias x_in (x_in is read to the end
+// before x_out is written); F and R may be global memory.  One thread: a chain of a few hundred dependent fp64 operations.
+// The two small-angle tests act each on its own.  |w dt| < eps: the rotation quaternion is the identity.  Every |w_i| < eps: the
+// angular-velocity diagonal of F and the quaternion block of G are zero (:176-184).  At dt = 1 the first implies the second; at
+// another dt either holds without the other.
+// (forced inline: F and G are global memory and LDS in one caller, LDS in the other; as a called function the model takes generic
+// pointers and a stack, and the step's prediction was 2 us slower for it)
+__device__ __forceinline__ void motion_model(const double *x_in, const double dt, double *F, double *G, double *x_out, double *R)
 {
-    __shared__ double sG[13 * 6];
-    if (filter_frozen(counts)) return;
-    const double dt = 1.0;
-    const double ln = par.linearAccelSD * par.linearAccelSD * dt * dt;
-    const double an = par.angularAccelSD * par.angularAccelSD * dt * dt;
-    if (blockIdx.x != 0) return;
-    if (threadIdx.x == 0) predict_prepare_serial(st, sG);
-    __syncthreads();
-    if (threadIdx.x < 169) {
-        const int i = threadIdx.x / 13, j = threadIdx.x % 13;
-        double s = 0.0;
-        for (int k = 0; k < 6; ++k) s += (sG[i * 6 + k] * (k < 3 ? ln : an)) * sG[j * 6 + k];
-        st[ST_GQG + i * 13 + j] = s;
-    }
-}
-
-__device__ void predict_prepare_serial(double *st, double *sG)
-{
-    const double dt = 1.0;
-    double *x = st + ST_X;
-    double *F = st + ST_F, *GQG = st + ST_GQG;
+    double x[13];
+    for (int i = 0; i < 13; ++i) x[i] = x_in[i];
     for (int i = 0; i < 169; ++i) F[i] = 0.0;
     for (int i = 0; i < 13; ++i) F[i * 13 + i] = 1.0;
     for (int i = 0; i < 3; ++i) F[i * 13 + i + 7] = dt;
@@ -59,7 +41,6 @@ __device__ void predict_prepare_serial(double *st, double *sG)
         for (int i = 0; i < 4; ++i)
             for (int j = 0; j < 4; ++j) F[(3 + i) * 13 + 3 + j] = Fq[i * 4 + j];
     }
-    double G[13 * 6];
     for (int i = 0; i < 78; ++i) G[i] = 0.0;
     if (fabs(x[10]) < EKF_EPSILON && fabs(x[11]) < EKF_EPSILON && fabs(x[12]) < EKF_EPSILON) {
         for (int i = 0; i < 3; ++i) F[(i + 10) * 13 + i + 10] = 0.0; // :176-184, G quaternion block stays 0
@@ -96,8 +77,6 @@ __device__ void predict_prepare_serial(double *st, double *sG)
         G[(i + 10) * 6 + i + 3] = 1.0;
         G[i * 6 + i] = 1.0 * dt;
     }
-    for (int i = 0; i < 78; ++i) sG[i] = G[i];
-    (void)GQG;
     // predictState :43-65
     for (int i = 0; i < 3; ++i) x[i] += x[7 + i] * dt;
     {
@@ -108,7 +87,49 @@ __device__ void predict_prepare_serial(double *st, double *sG)
         x[5] = q1w * q2y - q1x * q2z + q1y * q2w + q1z * q2x;
         x[6] = q1w * q2z + q1x * q2y - q1y * q2x + q1z * q2w;
     }
-    quat_to_rot(x + 3, st + ST_R);
+    for (int i = 0; i < 13; ++i) x_out[i] = x[i];
+    quat_to_rot(x + 3, R);
+}
+
+// G Q G' [i][j], Q = diag(ln x 3, an x 3), ln = linearAccelSD^2 dt^2, an = angularAccelSD^2 dt^2: the velocity impulse is drawn ONCE
+// per prediction, so one prediction over 2 dt is not two over dt
+__device__ __forceinline__ double gqg_entry(const double *sG, const int i, const int j, const double ln, const double an)
+{
+    double s = 0.0;
+    for (int k = 0; k < 6; ++k) s += (sG[i * 6 + k] * (k < 3 ? ln : an)) * sG[j * 6 + k];
+    return s;
+}
+
+// ------------------------------------------------------------------------------------------------ A1 + A2
+// F (13x13), G Q G' (13x13) from the PRE-prediction state, then the state prediction itself (covariance is predicted before
+// the state, :251-252), over the interval dt (the reference's is 1, :246: ekf_set_frame_interval's default).  One workgroup: thread 0
+// forms F, G and the predicted state (motion_model); the 169 entries of G Q G' -- a thousand multiply-adds, half of the 9 us the
+// kernel took as one thread -- are dealt to the workgroup behind one barrier.
+// counts != nullptr (EKF::step's launch): a step enqueued behind a failed update leaves the filter as it is (engine.h: filter_frozen)
+__global__ void __launch_bounds__(256) k_predict_prepare(double *st, ParD par, const int *counts, const double dt)
+{
+    __shared__ double sG[13 * 6];
+    if (filter_frozen(counts)) return;
+    const double ln = par.linearAccelSD * par.linearAccelSD * dt * dt;
+    const double an = par.angularAccelSD * par.angularAccelSD * dt * dt;
+    if (blockIdx.x != 0) return;
+    if (threadIdx.x == 0) motion_model(st + ST_X, dt, st + ST_F, sG, st + ST_X, st + ST_R);
+    __syncthreads();
+    if (threadIdx.x < 169) st[ST_GQG + threadIdx.x] = gqg_entry(sG, threadIdx.x / 13, threadIdx.x % 13, ln, an);
+}
+
+// the corner's two products, shared with the look-ahead (k_camera_ahead): (F C)[i][j] and ((F C) F')[i][j], each summed over k upwards
+__device__ __forceinline__ double corner_fc(const double *sF, const double *sC, const int i, const int j)
+{
+    double s = 0.0;
+    for (int k = 0; k < 13; ++k) s += sF[i * 13 + k] * sC[k * 13 + j];
+    return s;
+}
+__device__ __forceinline__ double corner_fcf(const double *sFP, const double *sF, const int i, const int j)
+{
+    double s = 0.0;
+    for (int k = 0; k < 13; ++k) s += sFP[i * 13 + k] * sF[j * 13 + k];
+    return s;
 }
 
 // P[0:13,0:13] = F P F' + G Q G'; P[0:13,13:] = F P[0:13,13:]; P[13:,0:13] = P[13:,0:13] F'  (:226-239).
@@ -129,18 +150,12 @@ __device__ __forceinline__ void predict_cov_body(const int bx, T *P, int ld, int
     if (bx == 0) {
         for (int i = tid; i < 169; i += 256) sC[i] = (double)P[(size_t)(i / 13) * ld + (i % 13)];
         __syncthreads();
-        if (tid < 169) {
-            const int i = tid / 13, j = tid % 13;
-            double s = 0.0;
-            for (int k = 0; k < 13; ++k) s += sF[i * 13 + k] * sC[k * 13 + j];
-            sFP[tid] = s;
-        }
+        if (tid < 169) sFP[tid] = corner_fc(sF, sC, tid / 13, tid % 13);
         __syncthreads();
         if (tid < 169) { // upper triangle, mirrored: F C F' + G Q G' is symmetric; this keeps P bitwise symmetric
             const int i = tid / 13, j = tid % 13;
             if (i <= j) {
-                double s = 0.0;
-                for (int k = 0; k < 13; ++k) s += sFP[i * 13 + k] * sF[j * 13 + k];
+                const double s = corner_fcf(sFP, sF, i, j);
                 const T v = (T)(s + st[ST_GQG + tid]);
                 P[(size_t)i * ld + j] = v;
                 P[(size_t)j * ld + i] = v;
@@ -177,9 +192,46 @@ __global__ void __launch_bounds__(256) k_predict_cov(T *P, int ld, int n, const 
     predict_cov_body<T>((int)blockIdx.x, P, ld, n, st, rm);
 }
 
-void launch_predict(EkfEngine *e)
+// Look-ahead of the camera (ekf_predict_camera_ahead): the camera state and the camera corner of P a prediction
+// over tau WOULD leave, without making it.  One workgroup: k_predict_prepare's work into LDS instead of the state block, then block 0
+// of predict_cov_body on it -- the same functions in the same order, so out[13 + 13 i + j] is, bit for bit, the fp64 value ekf_predict
+// over tau rounds to the storage type of P.  Reads st[ST_X ..] and P[0:13, 0:13]; writes out[0 .. 182) and nothing else.
+template <typename T>
+__global__ void __launch_bounds__(256) k_camera_ahead(const double *st, const T *P, int ld, ParD par, const double tau, double *out)
 {
-    k_predict_prepare<<<1, 256, 0, e->stream>>>(e->d.state, e->par, nullptr);
+    __shared__ double sF[169];
+    __shared__ double sC[169];
+    __shared__ double sFP[169];
+    __shared__ double sG[13 * 6];
+    __shared__ double sR[9];
+    const int tid = threadIdx.x;
+    const double ln = par.linearAccelSD * par.linearAccelSD * tau * tau;
+    const double an = par.angularAccelSD * par.angularAccelSD * tau * tau;
+    if (tid == 0) motion_model(st + ST_X, tau, sF, sG, out, sR);
+    for (int i = tid; i < 169; i += 256) sC[i] = (double)P[(size_t)(i / 13) * ld + (i % 13)];
+    __syncthreads();
+    if (tid < 169) sFP[tid] = corner_fc(sF, sC, tid / 13, tid % 13);
+    __syncthreads();
+    if (tid < 169) {
+        const int i = tid / 13, j = tid % 13;
+        if (i <= j) {
+            const double s = corner_fcf(sFP, sF, i, j);
+            const double v = s + gqg_entry(sG, i, j, ln, an);
+            out[13 + i * 13 + j] = v;
+            out[13 + j * 13 + i] = v;
+        }
+    }
+}
+
+void launch_camera_ahead(const EkfEngine *e, double tau, double *d_out)
+{
+    if (e->f32) k_camera_ahead<float><<<1, 256, 0, e->stream>>>(e->d.state, (const float *)e->d.P, e->ldP, e->par, tau, d_out);
+    else k_camera_ahead<double><<<1, 256, 0, e->stream>>>(e->d.state, (const double *)e->d.P, e->ldP, e->par, tau, d_out);
+}
+
+void launch_predict(EkfEngine *e, double dt)
+{
+    k_predict_prepare<<<1, 256, 0, e->stream>>>(e->d.state, e->par, nullptr, dt);
     const int nb = 1 + (e->n > 13 ? (e->n - 13 + 255) / 256 : 0);
     if (e->f32)
         k_predict_cov<float><<<nb, 256, 0, e->stream>>>((float *)e->d.P, e->ldP, e->n, e->d.state, e->rm);
@@ -271,14 +323,14 @@ k_predict_cov_features(int nb_cov, T *P, int ld, int n, RowMap rm, const double 
 
 // launch_predict + launch_predict_features(e, nullptr, count, false, true) of the step path in two launches instead of three (or
 // four); returns whether the compaction of the predicted list is left to launch_hp_rows(..., from_flags = true)
-bool launch_predict_with_features(EkfEngine *e, int count)
+bool launch_predict_with_features(EkfEngine *e, int count, double dt)
 {
     e->match_gates_valid = false; // pred_uv is rewritten: the gates come with the H P rows of this prediction
     if (count <= 0) {
-        launch_predict(e);
+        launch_predict(e, dt);
         return launch_predict_features(e, nullptr, count, false, true);
     }
-    k_predict_prepare<<<1, 256, 0, e->stream>>>(e->d.state, e->par, e->d.counts);
+    k_predict_prepare<<<1, 256, 0, e->stream>>>(e->d.state, e->par, e->d.counts, dt);
     const int nb_cov = 1 + (e->n > 13 ? (e->n - 13 + 255) / 256 : 0);
     const int nb_f = (count + 255) / 256;
     const bool one = count <= 256; // one workgroup of features: it compacts its own list

@@ -100,6 +100,11 @@ ABI = {
     "ekf_descriptor_bytes": (_i, [_vp]),
     "ekf_num_features": (_i, [_vp]),
     "ekf_predict": (_i, [_vp]),
+    "ekf_set_frame_interval": (_i, [_vp, C.c_double]),
+    "ekf_get_frame_interval": (_i, [_vp, C.POINTER(C.c_double)]),
+    "ekf_predict_dt": (_i, [_vp, C.c_double]),
+    "ekf_set_staged_intervals": (_i, [_vp, _i, _vp]),
+    "ekf_predict_camera_ahead": (_i, [_vp, C.c_double, _vp, _vp]),
     "ekf_predict_measurements": (_i, [_vp, _vp, _i, _vp, C.POINTER(_i), _vp, _vp]),
     "ekf_predict_measurement_state": (_i, [_vp, _vp, C.POINTER(_i)]),
     "ekf_match": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(_i)]),
@@ -560,8 +565,36 @@ class EkfEngine:
         return d[: self.N].view(self.desc_dtype), tp[: self.N], tm[: self.N]
 
     # ---- stages
-    def predict(self):
-        self._chk(self.L.ekf_predict(self.h))
+    def predict(self, dt=None):
+        """One prediction over the set frame interval (ekf_predict), or -- dt given -- over dt, leaving the set interval alone
+        (ekf_predict_dt)."""
+        if dt is None:
+            self._chk(self.L.ekf_predict(self.h))
+        else:
+            self._chk(self.L.ekf_predict_dt(self.h, float(dt)))
+
+    def set_frame_interval(self, dt):
+        """The interval predict() and every step use from now on, in units of the frame period the noise parameters were tuned for
+        (default 1.0; a frame after k dropped ones: k + 1).  Not finite or not > 0: EkfError(EKF_ERR_INVALID_ARG), nothing changes."""
+        self._chk(self.L.ekf_set_frame_interval(self.h, float(dt)))
+
+    def frame_interval(self):
+        dt = C.c_double(0.0)
+        self._chk(self.L.ekf_get_frame_interval(self.h, C.byref(dt)))
+        return dt.value
+
+    def set_staged_intervals(self, dts):
+        """Per-index intervals of a pre-staged sequence: step_frame(i) / step_staged_image(i) use dts[i] for i < len(dts), the set
+        interval beyond; an empty list clears the table.  One bad entry refuses the whole table."""
+        d = np.ascontiguousarray(dts, dtype=np.float64).reshape(-1)
+        self._chk(self.L.ekf_set_staged_intervals(self.h, len(d), _p(d) if len(d) else None))
+
+    def camera_ahead(self, tau):
+        """Look-ahead (ekf_predict_camera_ahead): (x13, P13) -- the camera state and its 13 x 13 covariance F P_cc F' + G Q G' a
+        prediction over tau would leave, computed on the device in fp64 without touching the filter."""
+        x, P = np.zeros(13), np.zeros((13, 13))
+        self._chk(self.L.ekf_predict_camera_ahead(self.h, float(tau), _p(x), _p(P)))
+        return x, P
 
     def predict_measurements(self, feat_idx=None):
         idx = None if feat_idx is None else np.ascontiguousarray(feat_idx, dtype=np.int32)

@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -24,6 +24,12 @@
 // the step line; the covariance carries over from the mapping frames as it is.
 // --convert-all (likewise): every map-management tick converts EVERY inverse-depth feature below the linearity threshold to XYZ
 // instead of the reference's one (ImageEKF::setConvertAll); log.txt gains "Converted to depth: K" per tick.
+// --timestamps FILE (likewise): one time per frame in seconds, in frame order, one per line (# starts a comment); frame i is stepped
+// over dt = (t_i - t_(i-1)) / unit instead of 1 (ImageEKF::setFrameInterval); the interval is printed under the step line and log.txt
+// gains "Frame interval: dt = D" per step.  --time-unit SECONDS (default 1): set it to the nominal frame period -- the
+// configuration's LinearAccelSD and AngularAccelSD were tuned per frame and then keep their meaning; a frame after k dropped ones
+// gets dt = k + 1.  A time that does not increase, or a number of times that differs from the number of frames, is an error
+// before the first frame is touched.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -64,11 +70,15 @@ int main(int argc, const char *argv[])
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false, convertAll = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
     int budget = 0, fixedFrom = -1;
-    std::string fixesFile;
+    std::string fixesFile, timesFile;
+    double timeUnit = 1.0;
     for (int i = 1; i < argc; ++i)
         if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes" ||
-             std::string(argv[i]) == "--fixed-map-from") && i + 1 < argc) { // the flag and its value
+             std::string(argv[i]) == "--fixed-map-from" || std::string(argv[i]) == "--timestamps" || std::string(argv[i]) == "--time-unit") &&
+            i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
+            else if (std::string(argv[i]) == "--timestamps") timesFile = argv[i + 1];
+            else if (std::string(argv[i]) == "--time-unit") timeUnit = std::atof(argv[i + 1]);
             else if (std::string(argv[i]) == "--fixed-map-from") fixedFrom = std::max(std::atoi(argv[i + 1]), 0);
             else if (std::string(argv[i]) == "--position-fixes") fixesFile = argv[i + 1];
             else distinct = std::atof(argv[i + 1]);
@@ -86,7 +96,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -96,12 +106,14 @@ int main(int argc, const char *argv[])
     try {
         ekf_compat::FileSequenceImageGenerator generator(argv[2], "", "png", first, last);
         generator.init();
+        std::vector<double> intervals; // per frame, with --timestamps (checked against the frames on disk before any is read)
+        if (!timesFile.empty()) ekf_compat::readFrameIntervals(timesFile, timeUnit, generator.remaining(), intervals);
         ekf_compat::Image image = generator.getNextImage();
         if (image.empty()) {
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty()) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -119,7 +131,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map or the batch conversion asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map, the batch conversion or frame times asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -139,6 +151,7 @@ int main(int argc, const char *argv[])
         image = generator.getNextImage();
         while (!image.empty()) {
             if (fixedFrom >= 0 && extendedKalmanFilter.steps() + 1 >= fixedFrom && !extendedKalmanFilter.fixedMap()) extendedKalmanFilter.setFixedMap(true);
+            if (!intervals.empty()) extendedKalmanFilter.setFrameInterval(intervals[(size_t)extendedKalmanFilter.steps() + 1]);
             const EkfStepInfo info = extendedKalmanFilter.step(image);
             double x[13];
             ekf_get_state(extendedKalmanFilter.engine(), x, 0, 0);
@@ -146,6 +159,7 @@ int main(int argc, const char *argv[])
                         info.n_predicted, info.n_matches, info.n_inliers, info.n_rescued, ekf_num_features(extendedKalmanFilter.engine()),
                         x[0], x[1], x[2]);
             if (extendedKalmanFilter.fixedMap()) std::printf("        fixed map: on\n");
+            if (!intervals.empty()) std::printf("        frame interval: dt = %g\n", extendedKalmanFilter.frameInterval());
             for (size_t k = 0; k < fixes.size(); ++k)
                 if (fixes[k].frame == extendedKalmanFilter.steps()) {
                     const double s2 = fixes[k].sigma * fixes[k].sigma, R[9] = {s2, 0, 0, 0, s2, 0, 0, 0, s2};

@@ -1200,7 +1200,7 @@ static int complete_hp_table(EkfEngine *e)
 // device-side core of predictCameraMeasurements; leaves the count in h_counts.
 // lean (sharded EKF::step): only the 2x2 innovation blocks S_i travel after a prediction (32 bytes per feature; every rank
 // gates and matches all predictions).  The H.P rows stay with their owners until somebody consumes them: the rows of a
-// RANSAC batch's hypotheses (ransac_dev) and the rows of the matches an update selects (lean_gather_exchange) -- 2M of
+// RANSAC batch's hypotheses (ransac_dev) and the rows of the matches an update selects (the gather stage of a lean update) -- 2M of
 // the 2N rows, and for the outlier re-prediction nothing but the S_i (missing 2a / EKF.cpp:473).
 // budget > 0 (a step's full prediction with the measurement budget active): the predicted features are scored and
 // ranked before the H P pass and the `budget` most informative go on; what describes the whole prediction -- the kept step
@@ -1473,20 +1473,9 @@ int ekf_ransac(EkfEngine *e, const EkfMatch *matches, int M, uint8_t *inlier_mas
     return EKF_OK;
 }
 
-// Sharded EKF::step: k_gather has copied the H.P rows of the selected matches out of this rank's table, of which only the
-// rows of OWNED features are valid.  The list is in feature order, so rank r's rows are rows [shard_rb[r], shard_rb[r+1])
-// of the gathered matrix: the usual row-block exchange completes it (and the fp64 camera columns beside it).
-static int lean_gather_exchange(EkfEngine *e, int M)
-{
-    (void)M;
-    int rc;
-    if ((rc = exchange_rows(e, EKF_XCHG_HP, e->d.G, (size_t)e->ldP * hp_elem_bytes(e), e->shard_rb, "the gathered H.P rows"))) return rc;
-    if (e->f32 && !e->exact && (rc = exchange_rows(e, EKF_XCHG_HPC, e->d.Gc, 16 * sizeof(double), e->shard_rb, "their fp64 camera columns"))) return rc;
-    return EKF_OK;
-}
-
-// update with the matches in e->d.msel[0..M); lean: see lean_gather_exchange
-static int update_dev(EkfEngine *e, int M, int kind, bool lean = false)
+// update with the matches in e->d.msel[0..M), recorded as `stage` (UpdateCall); lean: a sharded step, whose H.P table holds the
+// owners' rows only -- the gather stage completes the gathered rows by an exchange (kernels_update.hip); early: launch_early_gather
+static int update_dev(EkfEngine *e, int M, int kind, int stage, bool lean = false, const EarlyGather &early = EarlyGather())
 {
     if (M <= 0) return EKF_OK; // Update.cpp:292
     lean = lean && e->shard_world > 1 && !e->hp_complete;
@@ -1501,14 +1490,11 @@ static int update_dev(EkfEngine *e, int M, int kind, bool lean = false)
             return EKF_ERR_INVALID_ARG;
         }
     }
-    EkfMatch *save = e->d.matches;
-    e->d.matches = e->d.msel;
-    e->after_gather = lean ? lean_gather_exchange : nullptr;
-    launch_update(e, M, kind);
-    e->after_gather = nullptr;
-    e->d.matches = save;
-    if (e->hook_rc) return e->hook_rc;
-    return check_async(e);
+    UpdateCall call;
+    call.matches = e->d.msel; call.M = M; call.kind = kind; call.stage = stage;
+    call.lean = lean; call.early = early;
+    const int rc = launch_update(e, call);
+    return rc ? rc : check_async(e);
 }
 
 // e->h_counts[CNT_ERR] != 0 was read back: the last update enqueued failed and, with everything enqueued behind it, left the filter
@@ -1526,15 +1512,14 @@ static int recover_failed_update(EkfEngine *e, int *status)
     if (!code) return EKF_OK;
     HIPCHK(hipMemsetAsync(e->d.counts + CNT_ERR, 0, sizeof(int), e->stream));
     e->h_counts[CNT_ERR] = 0;
-    e->p_exact_sym = e->last_update_sym; // (the frozen downdate did not symmetrise an uploaded P)
-    if (code == EKF_ERR_TIMEOUT && e->last_update_persist && e->last_update_M > 0) {
+    e->p_exact_sym = e->last_update.sym; // (the frozen downdate did not symmetrise an uploaded P)
+    if (code == EKF_ERR_TIMEOUT && e->last_update.persist && e->last_update.call.M > 0) {
         e->ps_backoff_len = std::min(std::max(64, 2 * e->ps_backoff_len), 4096); // see engine.h
         e->ps_backoff = e->ps_backoff_len;
         e->ps_ok_streak = 0;
-        ++e->force_launches;
-        e->cons_stage = e->last_update_stage; // (filter consistency: the retry records the stage of the update it repeats)
-        int rc = update_dev(e, e->last_update_M, e->last_update_kind, false);
-        --e->force_launches;
+        // (filter consistency: the retry records the stage of the update it repeats)
+        int rc = launch_update(e, retry_of(e->last_update.call));
+        if (!rc) rc = check_async(e);
         ++e->sweep_retries;
         if (rc) return rc;
         if ((rc = read_counts(e))) return rc;
@@ -1542,7 +1527,7 @@ static int recover_failed_update(EkfEngine *e, int *status)
         const int code2 = e->h_counts[CNT_ERR]; // the retry's own outcome (it cannot time out)
         HIPCHK(hipMemsetAsync(e->d.counts + CNT_ERR, 0, sizeof(int), e->stream));
         e->h_counts[CNT_ERR] = 0;
-        e->p_exact_sym = e->last_update_sym;
+        e->p_exact_sym = e->last_update.sym;
         *status = code2;
     } else {
         *status = code;
@@ -1572,8 +1557,7 @@ int ekf_update(EkfEngine *e, const EkfMatch *matches, int M)
     HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     if ((rc = complete_hp_table(e))) return rc;
     if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
-    e->cons_stage = 0;
-    rc = update_dev(e, M, UPDATE_COV);
+    rc = update_dev(e, M, UPDATE_COV, 0);
     if (rc) return rc;
     return finish_update(e);
 }
@@ -1587,7 +1571,7 @@ int ekf_update_only_state(EkfEngine *e, const EkfMatch *matches, int M)
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     if ((rc = complete_hp_table(e))) return rc;
-    rc = update_dev(e, M, UPDATE_STATE_ONLY);
+    rc = update_dev(e, M, UPDATE_STATE_ONLY, 0);
     if (rc) return rc;
     return finish_update(e);
 }
@@ -1629,8 +1613,7 @@ int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M)
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
-    e->cons_stage = 0;
-    rc = update_dev(e, M, UPDATE_FIXED_MAP);
+    rc = update_dev(e, M, UPDATE_FIXED_MAP, 0);
     if (rc) return rc;
     return finish_update(e);
 }
@@ -1829,38 +1812,34 @@ static void harvest_pu_events(EkfEngine *e)
         (void)hipEventDestroy(pr.first);
     }
     e->px_events.clear();
-    for (size_t i = 0; i < e->pu_events.size(); ++i) {
+    for (const PuBracket &b : e->pu_events) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e->pu_events[i].first, e->pu_events[i].second) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, b.first, b.second) == hipSuccess) {
             e->times.p_update_kernel_ms += ms;
             e->times.p_update_launches += 1;
-            e->times.p_update_flops += e->pu_work[i];
+            e->times.p_update_flops += b.work;
             e->times.p_update_bytes += 2.0 * (double)e->n * (double)e->n * (e->f32 ? 4.0 : 8.0);
-            e->pu_log.emplace_back(e->pu_m[i], ms);
+            e->pu_log.emplace_back(b.m, ms);
         }
-        (void)hipEventDestroy(e->pu_events[i].first);
-        (void)hipEventDestroy(e->pu_events[i].second);
+        (void)hipEventDestroy(b.first);
+        (void)hipEventDestroy(b.second);
     }
     e->pu_events.clear();
-    e->pu_work.clear();
-    e->pu_m.clear();
-    for (size_t i = 0; i < e->sw_events.size(); ++i) {
+    for (const SweepBracket &b : e->sw_events) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e->sw_events[i].first, e->sw_events[i].second) == hipSuccess) {
-            const double m = std::abs(e->sw_m[i]);
+        if (hipEventElapsedTime(&ms, b.first, b.second) == hipSuccess) {
+            const double m = std::abs(b.m);
             e->sweep_ms += ms;
             e->sweep_panels += ((long long)m + NB - 1) / NB;
-            e->sweep_launches += i < e->sw_launch.size() ? e->sw_launch[i] : 0;
+            e->sweep_launches += b.launches;
             e->sweep_updates += 1;
-            e->sweep_flops_f64 += m * m * m / 3.0;                        // Cholesky of S
-            if (e->sw_m[i] > 0) e->sweep_flops_b += m * m * (double)e->n;  // B = inv(L) (H P): forward substitution, m^2 n
+            e->sweep_flops_f64 += m * m * m / 3.0;                  // Cholesky of S
+            if (b.m > 0) e->sweep_flops_b += m * m * (double)e->n;  // B = inv(L) (H P): forward substitution, m^2 n
         }
-        (void)hipEventDestroy(e->sw_events[i].first);
-        (void)hipEventDestroy(e->sw_events[i].second);
+        (void)hipEventDestroy(b.first);
+        (void)hipEventDestroy(b.second);
     }
     e->sw_events.clear();
-    e->sw_launch.clear();
-    e->sw_m.clear();
 }
 
 struct StageTimer {
@@ -2020,13 +1999,12 @@ restart:
     li.n_outliers = no;
     tm.mark();
     // 7. low-innovation update (:430)
-    e->cons_stage = 1;
-    if ((rc = update_dev(e, ni, step_kind, lean))) return rc;
+    if ((rc = update_dev(e, ni, step_kind, 1, lean))) return rc;
     tm.mark();
     // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
     // (EKF.cpp:552-556).  An outlier that is not re-predicted has pred_vis = 0 and is not rescued.
     int nr = 0;
-    bool early_ga = false; // the second update's gather / assembly is already enqueued, for the count this stage left on the device
+    EarlyGather early; // the second update's gather / assembly, where it is already enqueued for the count this stage left on the device
     if (no > 0) {
         int nop = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
@@ -2041,13 +2019,13 @@ restart:
                 // and writes update scratch only -- nothing at all behind a failed first update, where this stage runs again below.
                 // (Only where the partition publishes the counters itself: a copy of the counter block made behind this launch could show
                 // the error flag of the SECOND update's first diagonal block as if the first update had failed.)
-                early_ga = seq_p > 0 && launch_early_gather(e, no, cnt + CNT_NRESC, step_kind);
+                early = seq_p > 0 ? launch_early_gather(e, no, cnt + CNT_NRESC, step_kind) : EarlyGather();
                 rc = wait_counts(e, seq_p);
             } else {
                 rc = predict_measurements_dev(e, e->d.work_idx, no, &nop, false, lean);
             }
             if (rc) return rc;
-            early_ga = early_ga && !e->h_counts[CNT_ERR];
+            if (e->h_counts[CNT_ERR]) early = EarlyGather();
             if (!e->h_counts[CNT_ERR]) break;
             // the first update failed (seen at this stage's read-back; everything behind it was frozen, a fused partition did
             // nothing and the inliers are still in d.msel): run it again or skip it (recover_failed_update), then this stage again
@@ -2067,11 +2045,8 @@ restart:
     if (normals && nr > 0)
         HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
     // 10. high-innovation update (:529-532)
-    e->cons_stage = 2;
-    e->early_ga.armed = early_ga; // (this update's route decides whether the early launch serves it: launch_update)
-    rc = update_dev(e, nr, step_kind, lean);
-    e->early_ga.armed = false;
-    if (rc) return rc;
+    // (this update's route decides whether the early launch serves it: launch_update)
+    if ((rc = update_dev(e, nr, step_kind, 2, lean, early))) return rc;
     tm.mark();
     if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
     if (dev_counts && e->async_errors) {
@@ -3112,7 +3087,7 @@ int ekf_debug_plane0_pieces(EkfEngine *e, int *nonzero, int *total)
     if (!e || !nonzero || !total || !e->d.Bz) return EKF_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    const int cbs = (e->n + 31) / 32, groups = (2 * e->last_update_M + 15) / 16;
+    const int cbs = (e->n + 31) / 32, groups = (2 * e->last_update.call.M + 15) / 16;
     std::vector<uint8_t> row((size_t)e->bz_stride);
     int nz = 0;
     for (int c = 0; c < cbs; ++c) {

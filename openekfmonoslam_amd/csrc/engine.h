@@ -299,11 +299,17 @@ struct Frames {
     uint8_t *desc = nullptr;
 };
 
-// the gather / assembly launch a step enqueued ahead of its second update (launch_early_gather): what it assumed of the route, and
-// whether the update about to be launched is the one it was made for (set by the step around that one call)
-struct EarlyGather {
-    bool armed = false;
-    bool planes_b = false, apriori = false, persist = false, b_in_sweep = false;
+// one bracket of the covariance downdate's kernel (launch_p_update, launch_p_update_exact, the external update), not yet harvested
+struct PuBracket {
+    hipEvent_t first, second;
+    double work; // n^2 m of the launch
+    int m;
+};
+// one bracket of the Cholesky sweep's launches of one update
+struct SweepBracket {
+    hipEvent_t first, second;
+    int m;        // rows of S; negative: the rows of B were not formed in these launches
+    int launches; // (pair launches cover two panels)
 };
 
 } // namespace ekf
@@ -328,12 +334,10 @@ struct EkfEngine {
     EkfExchangeFn xchg = nullptr;        // all-gather of per-feature row blocks between the ranks
     void *comm = nullptr;                // ncclComm_t of the in-engine transport (ekf_comm_init), or null
     bool hp_complete = true;             // sharded: the H.P table holds EVERY rank's rows since the last prediction
-    int (*after_gather)(EkfEngine *, int) = nullptr; // sharded step: completes the gathered rows right after k_gather
     // the row-block exchange of engine.cpp (RCCL send / recv or the host callback), callable from the update's launcher
     int (*exchange_hook)(EkfEngine *, int what, void *base, size_t row_bytes, const std::vector<int32_t> &rb, const char *name) = nullptr;
     std::vector<int32_t> shard_row_begin; // [world + 1] first state row of each rank's share (0 for rank 0: it also holds the camera's), n at the end
     long long xchg_bytes_planes = 0;      // bytes of digit planes this rank received (tests assert them against the model)
-    int hook_rc = 0;                     // its status (launch_update returns nothing)
     std::vector<int32_t> shard_rb;       // row boundaries of the gathered rows by owner (from CNT_SHARD0..)
     std::vector<int32_t> slot_rb;        // sharded step: prediction slots of the last full prediction by owner (from CNT_SHARD0..)
     std::vector<int32_t> last_col_rb;    // column shares of the planes of B used by the last sharded update (ekf_shard_counters)
@@ -346,20 +350,20 @@ struct EkfEngine {
     std::shared_ptr<ekf::SweepRegistry> ps_reg; // the device's registry of persistent sweeps (shared with the other engines on it)
     // automatic retry of an update whose persistent sweep timed out (EKF_ERR_TIMEOUT): the kernels behind a failed sweep leave the
     // filter untouched (filter_frozen), so the update is run again from the same P on the launch-per-panel sweep
-    int force_launches = 0;               // > 0: updates use the launch-per-panel sweep whatever sweep_mode says (the retry itself)
     int sweep_retries = 0;                // updates re-run this way since the engine was created (ekf_get_sweep_retries)
     // back-off (EKF_SWEEP_AUTO only): a device that another process shares makes persistent sweeps time out again and again, 5 ms each;
     // after a time-out the next ps_backoff updates take the launch-per-panel sweep, twice as many after every further time-out (64 ..
     // 4096), and 256 persistent sweeps in a row without one forget the history
     int ps_backoff = 0, ps_backoff_len = 0, ps_ok_streak = 0;
-    int last_update_M = 0;                // matches of the last update enqueued (its list is still in d.msel)
-    int last_update_kind = 1;             // ... its kind, ekf::UPDATE_* (a retry runs the same kind again)
-    bool last_update_sym = false;         // p_exact_sym as it was before that update
-    bool last_update_persist = false;     // that update's sweep was the persistent launch
+    // the last update enqueued: a retry issues ekf::retry_of(call), its list is still in d.msel
+    struct {
+        ekf::UpdateCall call;
+        bool sym = false;     // p_exact_sym as it was before that update
+        bool persist = false; // that update's sweep was the persistent launch
+    } last_update;
     // d.match_gates holds the gates of the predictions now in pred_S / pred_uv: set by the launch_hp_rows that wrote them, cleared by
     // everything else that rewrites those tables or the map under them
     bool match_gates_valid = false;
-    ekf::EarlyGather early_ga;            // step path: the second update's gather / assembly enqueued before the rescued count is read
     int ps_cap[2] = {0, 0};    // resident workgroups of k_chol_persist<false / true> on this device (0: not asked yet, -1: unusable)
     bool async_errors = false; // ekf_set_async_errors: no read-back at the end of a step
     bool err_unread = false;   // the last step returned without reading the error flag back (cleared by recover_failed_update)
@@ -388,8 +392,6 @@ struct EkfEngine {
     int fm_rows = 0;               // rows of each of the two tables in d.fm_gain
     bool consistency = false;      // ekf_set_consistency: every covariance update is followed by k_consistency
     int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
-    int cons_stage = 0;            // stage the next covered update records: 0 ekf_update, 1 a step's first update, 2 its second
-    int last_update_stage = 0;     // ... and that of the last update enqueued (its retry records the same stage)
     double frame_interval = 1.0;   // ekf_set_frame_interval: the dt of ekf_predict and of every step function
     double step_dt = 1.0;          // the interval of the step being run: frame_interval, or the staged table's entry of its frame
     std::vector<double> staged_dt; // ekf_set_staged_intervals: per index of a pre-staged sequence, kept on the host (the value is a kernel argument)
@@ -416,7 +418,7 @@ struct EkfEngine {
     int bstage_rows = 0;      // rows of B the exchange image of the planes holds (sharded exact configuration)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> px_events; // exact configuration: end of the sweep -> start of the downdate (inverse, GEMM, digit planes, dx, state)
     hipEvent_t px_mid = nullptr;                               // recorded after the sweep's last launch (timing only)
-    int pu_slots = 0;         // resident workgroups of the downdate kernel on this device (0: not asked yet, -1: unknown)
+    int pu_slots = 0;         // resident workgroups of the downdate kernel on this device (0: not asked yet, -1: unknown): launch_p_update's query
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;             // image-only work of the next frame, overlapped with the update
     hipEvent_t ev_main = nullptr, ev_prefetch = nullptr;
@@ -430,13 +432,9 @@ struct EkfEngine {
     bool timing = false;
     EkfStageTimes times{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pu_events; // P-update kernel brackets not yet harvested
-    std::vector<double> pu_work;                               // n^2 m of each bracket
-    std::vector<int> pu_m;                                     // m of each bracket
+    std::vector<ekf::PuBracket> pu_events;                     // P-update kernel brackets not yet harvested
     std::vector<std::pair<int, float>> pu_log;                 // harvested (m, ms) per launch
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> sw_events;  // brackets of the Cholesky sweep's launches of one update
-    std::vector<int> sw_m;                                     // m of each bracket
-    std::vector<int> sw_launch;                                // launches of each bracket (pair launches cover two panels)
+    std::vector<ekf::SweepBracket> sw_events;                  // brackets of the Cholesky sweeps not yet harvested
     double sweep_ms = 0.0, sweep_flops_f64 = 0.0, sweep_flops_b = 0.0; // harvested totals (ekf_timing_sweep)
     long long sweep_panels = 0, sweep_updates = 0, sweep_launches = 0;
     double slice_ms = 0.0;                                     // exact configuration: sweep end -> downdate start (harvested)
@@ -565,25 +563,23 @@ void launch_ransac_select(EkfEngine *e, int M, int h0, int batch, const int *d_M
 // publish_seq > 0: the batch's bookkeeping kernel also publishes the counter block (see publish_counts_block)
 void launch_ransac_batch(EkfEngine *e, int M, int h0, int batch, const int *d_M = nullptr, int publish_seq = 0);
 void launch_ransac_init(EkfEngine *e, int M);
-// kind of an update: the state alone (updateOnlyState), state and covariance, or the Schmidt-Kalman update of a fixed map (state
-// and covariance strip of the camera alone)
-enum { UPDATE_STATE_ONLY = 0, UPDATE_COV = 1, UPDATE_FIXED_MAP = 2 };
-void launch_update(EkfEngine *e, int M, int kind);
+// enqueues the update (update_route.h: UpdateCall, UPDATE_*); EKF_OK, or the code of the stage that ended it with e->err set
+int launch_update(EkfEngine *e, const UpdateCall &call);
 // the merged gather / assembly launch of an update of the matches in d.msel whose count (at most M_max) is still on the device at
-// d_M; false: the route does not allow it, nothing was launched (kernels_update.hip)
-bool launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind);
+// d_M; launched == false: the route does not allow it, nothing was enqueued (kernels_update.hip)
+EarlyGather launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind);
 // fixed-map update (kernels_fixedmap.hip), fp64 arithmetic, unsharded engines.  _gain: where the route forms no rows of B, behind the inverse of
 // L -- B_c = W' G[:, 0:13] and K_c' = W B_c into d.fm_gain.  _strip: the partial sums of the 13 x n strip Y' X (Y = B[:, 0:13] and
 // X = B, m rows in d.A; or from_gain: Y = K_c' and X = G) into d.cam_part, then the tail: strip downdate, camera state, normalisation
 void launch_fixed_map_gain(EkfEngine *e, int m, const double *G);
 void launch_fixed_map_strip(EkfEngine *e, int m, const double *X, bool from_gain);
-void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready = false, bool planes_ready = false); // kernels_pexact.hip
+int launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready = false, bool planes_ready = false); // kernels_pexact.hip; EKF_OK or the error
 void launch_round_P_f32(EkfEngine *e);                        // kernels_map.hip
 void launch_diag_extract(EkfEngine *e, float *diag);          // kernels_pexact.hip: sharded exact configuration
 void launch_planes_move(EkfEngine *e, bool pack, int m_k, int c_lo, int c_hi, int skip_lo, int skip_hi);
 void launch_dx_planes(EkfEngine *e, int m_k);
 void launch_slice_columns(EkfEngine *e, int m, int c_lo, int c_hi);
-void launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi);
+int launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi); // EKF_OK or the error
 void launch_rescue(EkfEngine *e, const EkfMatch *matches, int M);
 void launch_state_only_predict(EkfEngine *e, EkfPrediction *d_out); // predictMeasurementState on current state
 void launch_add_features(EkfEngine *e, const double *d_uv, int count, double *d_Jpo, double *d_Jhr);
@@ -601,8 +597,8 @@ void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, m
 // update, the downdate and the normalisation of the covariance, and leaves the record in d.ext_res
 void launch_external_update(EkfEngine *e, int m);
 // filter consistency (kernels_consistency.hip): NIS and the per-match innovations of the update whose sweep was just enqueued, from
-// d.zvec, the M matches in d.matches and the prediction tables -> d.cons_ctl / d.cons_recs; does nothing when the error flag is set
-void launch_consistency(EkfEngine *e, int M);
+// d.zvec, the M matches and the prediction tables -> d.cons_ctl / d.cons_recs, recorded under `stage`; does nothing when the error flag is set
+void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage);
 // measurement budget (kernels_budget.hip): S_i of the np features in d.plist -> d.pred_S, their keys, ranks, records and selected flags
 // (rank < K, or all when np <= K) -> d.bud_*; launch_compact (k_compact) then turns flags into a list
 void launch_budget_select(EkfEngine *e, int np, int K);

@@ -76,11 +76,11 @@ k_consistency(const double *zvec, const EkfMatch *matches, int M, const double *
     }
 }
 
-void launch_consistency(EkfEngine *e, int M)
+void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage)
 {
     if (M <= 0 || M > e->cap || !e->d.cons_ctl || !e->d.cons_recs) return;
-    k_consistency<<<1, 256, 0, e->stream>>>(e->d.zvec, e->d.matches, M, e->d.pred_uv, e->d.pred_S, e->cfg.cam.pixelErrorX, e->d.counts,
-                                           e->cons_stage, e->cons_epoch, e->cap, e->d.cons_ctl, e->d.cons_recs);
+    k_consistency<<<1, 256, 0, e->stream>>>(e->d.zvec, matches, M, e->d.pred_uv, e->d.pred_S, e->cfg.cam.pixelErrorX, e->d.counts,
+                                           stage, e->cons_epoch, e->cap, e->d.cons_ctl, e->d.cons_recs);
 }
 
 } // namespace ekf

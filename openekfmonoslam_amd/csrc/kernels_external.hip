@@ -296,9 +296,7 @@ static void external_update_t(EkfEngine *e, int m)
     k_ext_downdate<T><<<tiles * (tiles + 1) / 2, 256, 0, s>>>(P, ld, n, A, ld, e->d.ext_ctl, e->d.ext_res);
     if (e->timing) {
         (void)hipEventRecord(e1, s);
-        e->pu_events.emplace_back(e0, e1);
-        e->pu_work.push_back((double)n * (double)n * (double)m);
-        e->pu_m.push_back(m);
+        e->pu_events.push_back(PuBracket{e0, e1, (double)n * (double)n * (double)m, m});
     }
     k_ext_normalize<T><<<1 + (n > 7 ? (n - 7 + 255) / 256 : 0), 256, 0, s>>>(P, ld, n, e->d.state, e->d.ext_res);
 }

@@ -1126,7 +1126,7 @@ k_b_gemm_i8p(const int8_t *__restrict__ Wq, int ldw, size_t w_stride, const int 
 
 // B = inv(L) G on the int8 MFMA, straight into the digit planes of B (columns [c_lo, c_hi), multiples of 128 rounded outwards).
 // W = inv(L)' in e->d.W (k-major, ldW), G in e->d.G (k-major fp64); e->d.Bexp holds the a-priori column scales of B.
-void launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi)
+int launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi)
 {
     hipStream_t s = e->stream;
     const int m_k = round_up(m, 32), ld = e->ldP, ldw = e->ldW;
@@ -1150,14 +1150,15 @@ void launch_b_gemm_planes(EkfEngine *e, int m, int c_lo, int c_hi)
     k_b_gemm_i8p<<<std::min(e->n_cus, n_units), 512, 0, s>>>(e->d.Wq, ldw, w_stride, e->d.Wexp, e->d.Gq, ld, g_stride, e->d.Gexp, e->d.Bq,
                                                            (size_t)e->bq_rows * ld, e->d.Bexp, m, tiles_j, tj0, n_units, e->d.counts, c_lo, std::min(e->n, c_hi),
                                                            e->px_dense ? nullptr : e->d.Wz, e->d.Gz, e->bz_stride);
+    return EKF_OK;
 #else // (builds with another digit count are accuracy experiments on the rows-of-B-in-the-sweep path only)
     (void)n_units;
-    e->hook_rc = EKF_ERR_INVALID_ARG;
+    return EKF_ERR_INVALID_ARG;
 #endif
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
-void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order); // kernels_pupdate.hip
+int build_units(EkfEngine *e, int nt, int nrt, bool rect, int order, int slots); // kernels_pupdate.hip
 
 #ifdef PX_BENCH // scripts/micro/pu_i8_bench.hip only: 1 = one workgroup per unit (k_p_update_i8)
 int g_px_variant = 0;
@@ -1169,7 +1170,8 @@ constexpr int g_px_variant = 0;
 // exps_ready: e->d.Bexp already holds the column scales of columns 0 .. n - 1 (the engine collects them in the pass that forms
 // dx = B'z); otherwise k_col_exp computes them here (scripts/micro/pu_i8_bench.hip)
 // planes_ready: the digit planes of rows 0 .. m - 1 are in e->d.Bq already (the sweep formed B from them, chol_bplanes.h)
-void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bool planes_ready)
+// Returns EKF_OK, or the error that left P without its downdate (e->err set).
+int launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bool planes_ready)
 {
     hipStream_t s = e->stream;
     const int n = e->n, ld = e->ldP;
@@ -1199,17 +1201,14 @@ void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bo
     const bool rect = e->shard_world > 1;
     const int owned = e->rm.r1 - e->rm.r0;
     const int nrt = 1 + (owned + 127) / 128; // camera tile + owned row tiles
-    const int slots_saved = e->pu_slots;
-    e->pu_slots = e->n_cus; // one 512-thread workgroup per CU is resident (160 accumulator registers per lane)
-    build_units(e, nt, nrt, rect, 0);
-    e->pu_slots = slots_saved;
+    int rc = build_units(e, nt, nrt, rect, 0, e->n_cus); // one 512-thread workgroup per CU is resident (160 accumulator registers per lane)
     const int grid = e->pu_per_xcd * 8;
     const int4 *tm = (const int4 *)e->d.pu_tilemap;
-    if (grid == 0 || !tm) { // build_units failed (e->hook_rc is set): nothing was launched, the timing events go back
+    if (grid == 0 || !tm) { // build_units failed: nothing was launched, the timing events go back
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         if (e2) (void)hipEventDestroy(e2);
-        return;
+        return rc;
     }
     if (e->timing) (void)hipEventRecord(e0, s);
 #if PX_S_VALUE == 5
@@ -1221,8 +1220,7 @@ void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bo
     } else
 #else
     if (!e->f32) { // (other digit counts: fp32-stored P only)
-        e->hook_rc = EKF_ERR_INVALID_ARG;
-        return;
+        return EKF_ERR_INVALID_ARG;
     }
 #endif
     if (!e->p_exact_sym && !rect) k_p_update_i8<true><<<grid, 512, 0, s>>>((float *)e->d.P, ld, n, e->d.Bq, ld, plane_stride, m_k, e->d.Bexp, e->pu_per_xcd, tm, e->d.counts);
@@ -1238,17 +1236,16 @@ void launch_p_update_exact(EkfEngine *e, int m, bool use_bc, bool exps_ready, bo
             launched = false;
             e->err = std::string("exact downdate launch: ") + hipGetErrorString(le);
             std::fprintf(stderr, "ekf: %s\n", e->err.c_str());
-            e->hook_rc = EKF_ERR_HIP;
+            rc = EKF_ERR_HIP;
         }
     }
     if (e->timing) {
         (void)hipEventRecord(e1, s);
-        e->pu_events.emplace_back(e0, e1);
-        e->pu_work.push_back(rect ? (double)(owned + 13) * (double)n * (double)m * 2.0 : (double)n * (double)n * (double)m);
-        e->pu_m.push_back(m);
+        e->pu_events.push_back(PuBracket{e0, e1, rect ? (double)(owned + 13) * (double)n * (double)m * 2.0 : (double)n * (double)n * (double)m, m});
         e->px_events.emplace_back(e2, e0); // sweep end (or this call's start) -> downdate start
     }
     if (launched) e->p_exact_sym = true; // (a refused launch leaves P as uploaded: the next downdate still symmetrises it)
+    return rc;
 }
 
 } // namespace ekf

@@ -509,18 +509,20 @@ constexpr int g_pu_order_override = -1;
 #endif
 
 // order: 0 half units last, 1 half units first, 2 mixed first round (see below)
-void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order)
+// slots: workgroups of the kernel the device keeps resident, which the list is balanced against (<= 0: the CU-count rule)
+// Returns EKF_OK with the list in e->d.pu_tilemap / e->pu_per_xcd, or the error (e->err set, no list).
+int build_units(EkfEngine *e, int nt, int nrt, bool rect, int order, int slots)
 {
     if (g_pu_order_override >= 0) order = g_pu_order_override;
-    const long long key = ((long long)(rect ? -(nt * 4096 + nrt) : nt) * 4 + order) * 4096 + e->pu_slots;
-    if (e->pu_tilemap_nt == key && e->d.pu_tilemap) return;
+    const long long key = ((long long)(rect ? -(nt * 4096 + nrt) : nt) * 4 + order) * 4096 + slots;
+    if (e->pu_tilemap_nt == key && e->d.pu_tilemap) return EKF_OK;
     {   // the two orders of one geometry alternate every frame (LI / HI update): keep every list once built
         auto it = e->pu_tables.find(key);
         if (it != e->pu_tables.end()) {
             e->d.pu_tilemap = it->second.first;
             e->pu_per_xcd = it->second.second;
             e->pu_tilemap_nt = key;
-            return;
+            return EKF_OK;
         }
     }
     std::vector<int4> tiles;
@@ -545,8 +547,8 @@ void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order)
     // third round of whole tiles on a third of the CUs: the MFMA stream alone took 318 us where the balanced list takes 260
     // (scripts/micro/pu_bench.hip, profiles/r03_pu_bench.txt).
     int n_full;
-    if (e->pu_slots > 0) {
-        const int rounds = (2 * ntiles + e->pu_slots - 1) / e->pu_slots; // half-rounds of the whole launch
+    if (slots > 0) {
+        const int rounds = (2 * ntiles + slots - 1) / slots; // half-rounds of the whole launch
         const int used = (2 * ntiles + rounds - 1) / rounds;              // slots that get `rounds` half units
         n_full = rounds <= 1 ? 0 : std::min(ntiles, (rounds / 2) * used);
     } else {
@@ -572,7 +574,7 @@ void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order)
             // list (every slot: one of each) half of the slots run [half, tile] and the others [tile, half]: the epilogues of
             // the first units fall at T/3 and 2T/3 under the other slots' MFMA phases, and the launch ends with a mix of
             // tile and half-unit epilogues instead of every slot's tile epilogue at once
-            const int first = e->pu_slots > 0 ? e->pu_slots / NX : 0;
+            const int first = slots > 0 ? slots / NX : 0;
             for (int i = 0; i < first && (ih < hl.size() || jf < fl.size()); ++i) {
                 const bool want_h = (((i / 32) & 1) == 0) == (order == 2); // 32 CUs per XCD, handed one workgroup each in turn
                 if ((want_h && ih < hl.size()) || jf >= fl.size()) out.push_back(hl[ih++]);
@@ -598,12 +600,12 @@ void build_units(EkfEngine *e, int nt, int nrt, bool rect, int order)
         e->pu_per_xcd = 0;
         e->pu_tilemap_nt = -1;
         e->err = "work list of the covariance downdate: allocation or upload failed";
-        e->hook_rc = EKF_ERR_HIP;
-        return;
+        return EKF_ERR_HIP;
     }
     e->pu_tilemap_nt = key;
     e->pu_per_xcd = per;
     e->pu_tables[key] = std::make_pair(e->d.pu_tilemap, per);
+    return EKF_OK;
 }
 
 #ifdef PU_BENCH
@@ -635,7 +637,8 @@ static void launch_p_update_t(EkfEngine *e, int m_pad, int grid, const int4 *tm,
         k_p_update<T, false, false><<<grid, 256, 0, s>>>(P, e->ldP, e->n, B, e->ldP, m_pad, e->pu_per_xcd, tm, e->rm, stagger, frz);
 }
 
-void launch_p_update(EkfEngine *e, int m_pad, int m)
+// EKF_OK, or the error that left P without its downdate (no work list)
+int launch_p_update(EkfEngine *e, int m_pad, int m)
 {
     hipStream_t s = e->stream;
     const int n = e->n;
@@ -658,14 +661,11 @@ void launch_p_update(EkfEngine *e, int m_pad, int m)
     // Whole tiles first, half units last, in both regimes (scripts/micro/pu_bench.hip, 15 interleaved rounds, m = 1014: half
     // units first 332 us, mixed first round 323-347 us, whole tiles first 323 us).  Short k-loops keep the CU-count split of
     // rounds 1-2 (m = 298: 113 against 116.5 us with the balanced list): there the launch is mostly epilogue traffic.
-    const int slots_saved = e->pu_slots;
-    if (g_pu_force_slots) e->pu_slots = g_pu_force_slots;
-    else if (m_pad < 512 && !rect) e->pu_slots = -1;
-    build_units(e, nt, nrt, rect, 0);
-    e->pu_slots = slots_saved;
+    const int slots = g_pu_force_slots ? g_pu_force_slots : (m_pad < 512 && !rect) ? -1 : e->pu_slots;
+    const int rc = build_units(e, nt, nrt, rect, 0, slots);
     const int grid = e->pu_per_xcd * 8;
     const int4 *tm = (const int4 *)e->d.pu_tilemap;
-    if (grid == 0 || !tm) return; // build_units failed (e->hook_rc is set)
+    if (grid == 0 || !tm) return rc; // build_units failed
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing) {
         (void)hipEventCreate(&e0);
@@ -677,13 +677,12 @@ void launch_p_update(EkfEngine *e, int m_pad, int m)
     else launch_p_update_t<double>(e, m_pad, grid, tm, avg, rect);
     if (e->timing) {
         (void)hipEventRecord(e1, s);
-        e->pu_events.emplace_back(e0, e1);
         // flops of this launch / 1 (n^2 m counts the symmetric downdate; a rank computes owned x n x m x 2 / 2)
         // algorithmic work of the launch from the UN-padded m (the kernel runs m rounded up to 16 rows of B, the rest zero)
-        e->pu_work.push_back(rect ? (double)(owned + 13) * (double)n * (double)m * 2.0 : (double)n * (double)n * (double)m);
-        e->pu_m.push_back(m);
+        e->pu_events.push_back(PuBracket{e0, e1, rect ? (double)(owned + 13) * (double)n * (double)m * 2.0 : (double)n * (double)n * (double)m, m});
     }
     e->p_exact_sym = true;
+    return rc;
 }
 
 } // namespace ekf

@@ -1438,7 +1438,7 @@ k_fix_normalize(T *P, int ld, int n, RowMap rm, const double *dsave, const doubl
 }
 
 // P-update launcher lives in kernels_pupdate.hip
-void launch_p_update(EkfEngine *e, int m_pad, int m);
+int launch_p_update(EkfEngine *e, int m_pad, int m);
 
 // ---------------------------------------------------------------------------------------------- persistent sweep launcher
 // The registry of persistent sweeps of one device (engine.h: SweepRegistry).  The table below only FINDS the registry of a device;
@@ -1555,7 +1555,7 @@ static bool launch_persistent_sweep(EkfEngine *e, int m, const double *G, double
 
 // ---------------------------------------------------------------------------------------------- the update, stage by stage
 // update_impl (below) chooses the route of the update (update_route.h) and issues its launches in these stages, in this order; a
-// stage that returns false has set e->hook_rc and ends the update.
+// stage that returns an error code (with e->err set) ends the update.
 // T: storage type of P; TB: type of H P, of its gathered rows G, of B = inv(L) G and of the arithmetic that forms it
 // (EXACT: EKF_PRECISION_F32_EXACT, T = float, and EKF_PRECISION_F64_EXACT, T = double -- TB = double, the downdate by kernels_pexact.hip)
 
@@ -1583,16 +1583,15 @@ static BPlanes planes_of_B(EkfEngine *e, const UpdateRoute &r)
 }
 
 // 1. sharded exact: the diagonal of P behind the a-priori column scales -- every rank's own entries, then all of them
-static bool exchange_p_diag(EkfEngine *e, const UpdateRoute &r)
+static int exchange_p_diag(EkfEngine *e, const UpdateRoute &r)
 {
-    if (!(r.sharded && (r.planes_b || r.shard_cols))) return true;
+    if (!(r.sharded && (r.planes_b || r.shard_cols))) return EKF_OK;
     launch_diag_extract(e, e->d.Pdiag);
     std::vector<int32_t> drb(e->shard_row_begin.begin(), e->shard_row_begin.end());
-    e->hook_rc = e->exchange_hook(e, EKF_XCHG_PDIAG, e->d.Pdiag, sizeof(float), drb, "the diagonal of P");
-    return e->hook_rc == 0;
+    return e->exchange_hook(e, EKF_XCHG_PDIAG, e->d.Pdiag, sizeof(float), drb, "the diagonal of P");
 }
 
-#define GATHER_ARGS e->d.matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
+#define GATHER_ARGS matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
                     e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->d.HPc, e->d.Gc, EXACT ? e->d.Bexp : nullptr
 
 // grid.x of the gather: 16 bytes of a row per thread -- or one workgroup per row where nothing is copied (bookkeeping, row map, its
@@ -1603,10 +1602,10 @@ static int gather_grid_x(const UpdateRoute &r)
     return (r.planes_b && !r.sharded) || r.sym_g ? 1 : (r.n_pad / (int)(16 / sizeof(TB)) + 255) / 256;
 }
 
-// gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output), for the matches in
-// e->d.matches.  d_M: r.M is an upper bound and the kernel reads the count (k_gather_assemble)
+// gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output).
+// d_M: r.M is an upper bound and the kernel reads the count (k_gather_assemble)
 template <typename T, typename TB, bool EXACT>
-static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const int *d_M)
+static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const EkfMatch *matches, const int *d_M)
 {
     const int M = r.M, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
     double *V = e->d.Dinv, *W = inv_W(e, r);
@@ -1620,11 +1619,13 @@ static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const int
 }
 
 // 2. the gathered rows G of H P and S = H P H' + R
-// early_done: the step enqueued this update's merged launch behind its rescue stage, with the count on the device
-// (launch_early_gather), under the same route: nothing is launched here
+// call.early serves the route: the step enqueued this update's merged launch behind its rescue stage, with the count on the device
+// (launch_early_gather), under the same route -- nothing is launched here
 template <typename T, typename TB, bool EXACT>
-static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r, bool early_done)
+static int gather_and_assemble(EkfEngine *e, const UpdateRoute &r, const UpdateCall &call)
 {
+    const EkfMatch *matches = call.matches;
+    int rc;
     hipStream_t s = e->stream;
     const int M = r.M, m = r.m, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
     const bool planes_b = r.planes_b, sharded = r.sharded, sym_g = r.sym_g, apriori = r.apriori;
@@ -1632,16 +1633,20 @@ static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r, bool early_d
     float *Wf = inv_Wf<TB>(e, r);
     dim3 grid(gather_grid_x<TB>(r), m_pad);
     if (r.merged_ga) {
-        if (!early_done) launch_gather_assemble<T, TB, EXACT>(e, r, nullptr);
+        if (!early_gather_serves(call.early, r)) launch_gather_assemble<T, TB, EXACT>(e, r, matches, nullptr);
     } else if (apriori && !sharded) // a-priori column scales from the diagonal of the covariance itself
         k_gather<TB, T><<<grid, 256, 0, s>>>(GATHER_ARGS, (const T *)e->d.P, ld, n, planes_b || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
     else
         k_gather<TB, float><<<grid, 256, 0, s>>>(GATHER_ARGS, apriori ? e->d.Pdiag : nullptr, 0, n,
                                                 (planes_b && !sharded) || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
 #undef GATHER_ARGS
-    // sharded step: every rank gathered the rows of the matches it owns; the others arrive here (engine.cpp)
-    e->hook_rc = (e->after_gather && !sym_g) ? e->after_gather(e, M) : 0;
-    if (e->hook_rc) return false;
+    // sharded step: k_gather has copied the H.P rows of the selected matches out of this rank's table, of which only the rows of
+    // OWNED features are valid.  The list is in feature order, so rank r's rows are rows [shard_rb[r], shard_rb[r+1]) of the
+    // gathered matrix: the usual row-block exchange completes it (and the fp64 camera columns beside it)
+    if (call.lean && !sym_g) {
+        if ((rc = e->exchange_hook(e, EKF_XCHG_HP, e->d.G, (size_t)ld * sizeof(TB), e->shard_rb, "the gathered H.P rows"))) return rc;
+        if (sizeof(TB) == 4 && (rc = e->exchange_hook(e, EKF_XCHG_HPC, e->d.Gc, 16 * sizeof(double), e->shard_rb, "their fp64 camera columns"))) return rc;
+    }
     TB *G = rows_of_G<TB>(e, r); // (sym_g: G is formed by k_g_cols below)
     grid = dim3((M + 15) / 16, (M + 15) / 16);
     if (sym_g) {
@@ -1661,8 +1666,7 @@ static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r, bool early_d
         k_assemble_S<TB><<<grid, 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
                                              nullptr, nullptr, ldw, e->d.counts, e->d.Lexp, nullptr, b_lo, b_hi, St, m_pad, 0);
         // (rows of the image are m_pad doubles: only the live columns of S travel, not the capacity-strided ldW)
-        e->hook_rc = e->exchange_hook(e, EKF_XCHG_SCOLS, St, (size_t)m_pad * sizeof(double), e->shard_rb, "the columns of S");
-        if (e->hook_rc) return false;
+        if ((rc = e->exchange_hook(e, EKF_XCHG_SCOLS, St, (size_t)m_pad * sizeof(double), e->shard_rb, "the columns of S"))) return rc;
         k_s_unpack<<<dim3((m + 255) / 256, m), 256, 0, s>>>(St, m_pad, e->d.S, ldS, m, 2 * b_lo, 2 * b_hi, e->d.Lexp);
         k_assemble_S<TB><<<dim3(1, 1), 256, 0, s>>>(G, ld, M, e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->cfg.cam.pixelErrorX, e->d.S, ldS, V,
                                                    W, nullptr, ldw, e->d.counts, nullptr, nullptr, 0, 0, nullptr, 0, 1);
@@ -1671,12 +1675,12 @@ static bool gather_and_assemble(EkfEngine *e, const UpdateRoute &r, bool early_d
                                              e->cfg.cam.pixelErrorX, e->d.S, ldS, V, W, Wf, ldw, e->d.counts,
                                              planes_b ? e->d.Lexp : nullptr, planes_b && !sharded ? e->d.Grow : nullptr, 0, M, nullptr, 0,
                                              r.persist ? 0 : 1); // (the persistent sweep's chain workgroup factorises the first block itself)
-    return true;
+    return EKF_OK;
 }
 
 // 3. the Cholesky sweep of S (with the rows of B where the route forms them in it): one persistent launch, or a launch per panel / pair
 template <typename TB, bool EXACT>
-static bool cholesky_sweep(EkfEngine *e, const UpdateRoute &r)
+static int cholesky_sweep(EkfEngine *e, const UpdateRoute &r)
 {
     hipStream_t s = e->stream;
     const int m = r.m, m_pad = r.m_pad, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
@@ -1700,8 +1704,7 @@ static bool cholesky_sweep(EkfEngine *e, const UpdateRoute &r)
         }
         if (!launched) { // (only a failed memset of the flag block is left: the layout was checked before the gather)
             e->err = "persistent sweep could not be launched";
-            e->hook_rc = EKF_ERR_HIP;
-            return false;
+            return EKF_ERR_HIP;
         }
         n_sweep_launches = 1;
     }
@@ -1754,23 +1757,22 @@ static bool cholesky_sweep(EkfEngine *e, const UpdateRoute &r)
     }
     if (e->timing) {
         (void)hipEventRecord(sw1, s);
-        e->sw_events.emplace_back(sw0, sw1);
+        // (negative: the rows of B were not formed in these launches)
+        e->sw_events.push_back(SweepBracket{sw0, sw1, r.b_in_sweep ? m : -m, n_sweep_launches});
         if (EXACT && r.update_cov) { // -> launch_p_update_exact: the bracket "sweep end .. downdate start"
             if (e->px_mid) (void)hipEventDestroy(e->px_mid); // (an update that failed between the two left it behind)
             e->px_mid = nullptr;
             if (hipEventCreate(&e->px_mid) == hipSuccess) (void)hipEventRecord(e->px_mid, s);
         }
-        e->sw_m.push_back(r.b_in_sweep ? m : -m); // negative: the rows of B were not formed in these launches
-        e->sw_launch.push_back(n_sweep_launches);
     }
-    return true;
+    return EKF_OK;
 }
 
 // 4. B not formed in the sweep: inv(L), then B = inv(L) G by one GEMM
 template <typename TB>
-static void inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
+static int inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
 {
-    if (!r.need_inverse) return;
+    if (!r.need_inverse) return EKF_OK;
     hipStream_t s = e->stream;
     const int m = r.m, m_pad = r.m_pad, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
     double *V = e->d.Dinv, *W = inv_W(e, r);
@@ -1789,12 +1791,11 @@ static void inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
     if (r.fixed_map) {
         // no m x m x n product: the camera's 13 columns of B = W' G and of the gain K' = W B are all the strip needs
         launch_fixed_map_gain(e, m, (const double *)rows_of_G<TB>(e, r));
-        return;
+        return EKF_OK;
     }
     if (r.gemm_planes) {
         const int c_lo = r.shard_cols ? r.col_rb[e->shard_rank] : 0, c_hi = r.shard_cols ? r.col_rb[e->shard_rank + 1] : n_pad;
-        launch_b_gemm_planes(e, m, c_lo, c_hi);
-        return;
+        return launch_b_gemm_planes(e, m, c_lo, c_hi);
     }
     // B = inv(L) G = W' G : one GEMM, k <= row (W upper triangular)
     const int TM = sizeof(TB) == 4 ? 128 : 64;
@@ -1811,15 +1812,16 @@ static void inverse_and_gemm(EkfEngine *e, const UpdateRoute &r)
     }
     g.n_split = g.tiles_i / 2; // k-depth of row tile i is ~(i+1) TM: halve the units of the longer half
     launch_xty(e, g, 1, sizeof(TB) == 4, s);
+    return EKF_OK;
 }
 
 // 5. dx = B'z and the state (which waits for the covariance tail where the route merges the two)
 template <typename T, typename TB, bool EXACT>
-static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
+static int dx_and_state(EkfEngine *e, const UpdateRoute &r)
 {
     hipStream_t s = e->stream;
     const int m = r.m, n = r.n, ld = e->ldP;
-    if (r.fixed_map) return true; // dx of the camera alone: formed by the strip's tail (k_fm_tail); k_state_apply must not run
+    if (r.fixed_map) return EKF_OK; // dx of the camera alone: formed by the strip's tail (k_fm_tail); k_state_apply must not run
     if (r.shard_cols) {
         // every rank's column blocks of the digit planes to every rank: pack [column][plane][k group], row-block exchange, unpack;
         // dx = B'z then comes from the planes (the fp64 rows of B exist only for the own columns)
@@ -1827,8 +1829,8 @@ static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
         const int c0 = r.col_rb[e->shard_rank], c1 = r.col_rb[e->shard_rank + 1];
         if (!r.planes_b && !r.gemm_planes) launch_slice_columns(e, m, c0, c1); // B came out of the GEMM in fp64
         launch_planes_move(e, true, m_k, c0, c1, 0, 0);
-        e->hook_rc = e->exchange_hook(e, EKF_XCHG_BPLANES, e->d.Bstage, (size_t)PX_S * m16 * 16, r.col_rb, "the digit planes of B");
-        if (e->hook_rc) return false;
+        const int rc = e->exchange_hook(e, EKF_XCHG_BPLANES, e->d.Bstage, (size_t)PX_S * m16 * 16, r.col_rb, "the digit planes of B");
+        if (rc) return rc;
         launch_planes_move(e, false, m_k, 0, r.n_pad, c0, c1);
         launch_dx_planes(e, m_k);
     } else if (r.gemm_planes || r.planes_b) { // B exists as digit planes only
@@ -1859,57 +1861,59 @@ static bool dx_and_state(EkfEngine *e, const UpdateRoute &r)
         k_state_apply<<<(nt + 255) / 256, 256, 0, s>>>(e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos, e->N, e->d.dx_part, ld,
                                                        r.update_cov ? 1 : 0, r.fix_diag ? nullptr : e->d.counts);
     }
-    return true;
+    return EKF_OK;
 }
 
 // 6. the consistency record, the downdate of P and the covariance tail
 template <typename T, typename TB, bool EXACT>
-static void downdate_and_tail(EkfEngine *e, const UpdateRoute &r)
+static int downdate_and_tail(EkfEngine *e, const UpdateRoute &r, const UpdateCall &call)
 {
     hipStream_t s = e->stream;
     const int n = r.n, ld = e->ldP;
     // filter consistency: z is final in d.zvec and the error flag tells whether this sweep failed
-    if (e->consistency && (r.update_cov || r.fixed_map)) launch_consistency(e, r.M);
+    if (e->consistency && (r.update_cov || r.fixed_map)) launch_consistency(e, call.matches, r.M, call.stage);
     if (r.fixed_map) {
         // the camera's strip of P and the camera state (kernels_fixedmap.hip): Y' X with Y = B[:, 0:13], X = B where the sweep formed
         // the rows of B, Y = K_c', X = G (the gathered rows of H P) where it did not
         if constexpr (sizeof(TB) == 8) launch_fixed_map_strip(e, r.m, r.b_in_sweep ? (const double *)e->d.A : (const double *)rows_of_G<TB>(e, r), !r.b_in_sweep);
-        return;
+        return EKF_OK;
     }
-    if (!r.update_cov) return;
+    if (!r.update_cov) return EKF_OK;
     // (column scales: k_gather + k_dx_partial, or a-priori; planes: the sweep's / the GEMM's / the ranks')
-    if (EXACT) launch_p_update_exact(e, r.m, false, true, r.planes_b || r.shard_cols || r.gemm_planes);
-    else launch_p_update(e, r.m_pad, r.m);
+    // (a downdate that failed on the host still gets its tail enqueued: the code travels to the end)
+    const int rc = EXACT ? launch_p_update_exact(e, r.m, false, true, r.planes_b || r.shard_cols || r.gemm_planes) : launch_p_update(e, r.m_pad, r.m);
     // the kernels behind the sweep that write x or P leave them alone when the sweep failed (filter_frozen, engine.h); the fast fp32
     // configuration keeps its own tail (its sweep is never the persistent launch: nothing to retry)
     if (r.fix_diag) {
         k_fix_normalize<T><<<(n + 255) / 256, 256, 0, s>>>((T *)e->d.P, ld, n, e->rm, e->d.diag_save, e->d.sq_part, e->d.cam_save,
                                                            e->d.cam_part, ld, e->d.state);
-        return;
+        return rc;
     }
     const int nb = 1 + (n > 7 ? (n - 7 + 255) / 256 : 0);
     if (r.merged_tail) {
         const int nt = max(e->N * 6, 1);
         k_apply_normalize<T><<<max(nb, (nt + 255) / 256), 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, e->d.feat_pos, e->d.feat_type,
                                                                        e->d.feat_covpos, e->N, e->d.dx_part, ld, e->d.counts);
-        return;
+        return rc;
     }
     k_normalize_cov<T><<<nb, 256, 0, s>>>((T *)e->d.P, ld, n, e->d.state, e->rm, e->d.counts);
+    return rc;
 }
 
-// what choose_update_route reads of the engine, for an update of M matches
+// what choose_update_route reads of the call and of the engine
 template <typename T, typename TB, bool EXACT>
-static UpdateRouteIn route_input(EkfEngine *e, int M, int kind)
+static UpdateRouteIn route_input(EkfEngine *e, const UpdateCall &call)
 {
     UpdateRouteIn in;
-    in.M = M; in.n = e->n; in.update_cov = kind == UPDATE_COV; in.fixed_map = kind == UPDATE_FIXED_MAP;
+    route_input_of_call(in, call);
+    in.n = e->n;
     in.b_fp32 = sizeof(TB) == 4; in.p_fp32 = sizeof(T) == 4; in.exact = EXACT;
-    in.b_path = e->b_path; in.sweep_mode = e->sweep_mode; in.force_launches = e->force_launches > 0; in.ps_backoff = e->ps_backoff > 0;
+    in.b_path = e->b_path; in.sweep_mode = e->sweep_mode; in.ps_backoff = e->ps_backoff > 0;
     in.shard_world = e->shard_world; in.shard_rank = e->shard_rank;
     in.shard_row_begin = e->shard_row_begin.data(); in.n_shard_row_begin = e->shard_row_begin.size();
     in.Lq = e->d.Lq != nullptr; in.Wq = e->d.Wq != nullptr; in.Bstage = e->d.Bstage != nullptr; in.bstage_rows = e->bstage_rows;
     in.W = e->d.W != nullptr; in.Tbuf = e->d.Tbuf != nullptr; in.sweep_ctl = e->d.sweep_ctl != nullptr;
-    in.exchange_hook = e->exchange_hook != nullptr; in.after_gather = e->after_gather != nullptr;
+    in.exchange_hook = e->exchange_hook != nullptr;
     in.shard_rb_ok = (int)e->shard_rb.size() == e->shard_world + 1;
     in.n_cus = e->n_cus;
     if (sizeof(TB) == 8) { // (the persistent sweep needs the fp64 arithmetic of B)
@@ -1923,28 +1927,28 @@ static UpdateRouteIn route_input(EkfEngine *e, int M, int kind)
 // were rescued (engine.cpp step_dev): M_max bounds the grid, d_M is the count on the device, the matches are in d.msel.  The
 // launch depends on the route only through same_gather_launch's fields (update_route.h), so it goes ahead when the route of the
 // largest and of the smallest possible update agree in them; the route is computed without its side effects (the back-off
-// bookkeeping stays in update_impl).  Returns whether it launched and records what it assumed: update_impl skips its own launch
-// when the real route agrees (e->early_ga, armed by the step).
+// bookkeeping stays in update_impl).  Returns whether it launched and what it assumed: the step passes that in the update's call,
+// and update_impl skips its own launch when the real route agrees (early_gather_serves).
 template <typename T, typename TB, bool EXACT>
-static bool early_gather_impl(EkfEngine *e, int M_max, const int *d_M, int kind)
+static EarlyGather early_gather_impl(EkfEngine *e, int M_max, const int *d_M, int kind)
 {
-    e->early_ga = EarlyGather();
-    UpdateRouteIn in = route_input<T, TB, EXACT>(e, M_max, kind);
+    UpdateCall call;
+    call.matches = e->d.msel; call.M = M_max; call.kind = kind;
+    UpdateRouteIn in = route_input<T, TB, EXACT>(e, call);
     const UpdateRoute hi = choose_update_route(in);
     in.M = 1;
     const UpdateRoute lo = choose_update_route(in);
-    if (hi.refusal || lo.refusal || !hi.merged_ga || !same_gather_launch(hi, lo)) return false;
-    EkfMatch *save = e->d.matches;
-    e->d.matches = e->d.msel;
-    launch_gather_assemble<T, TB, EXACT>(e, hi, d_M);
-    e->d.matches = save;
-    e->early_ga.planes_b = hi.planes_b; e->early_ga.apriori = hi.apriori; e->early_ga.persist = hi.persist; e->early_ga.b_in_sweep = hi.b_in_sweep;
-    return true;
+    if (hi.refusal || lo.refusal || !hi.merged_ga || !same_gather_launch(hi, lo)) return EarlyGather();
+    launch_gather_assemble<T, TB, EXACT>(e, hi, call.matches, d_M);
+    EarlyGather g;
+    g.launched = true;
+    g.planes_b = hi.planes_b; g.apriori = hi.apriori; g.persist = hi.persist; g.b_in_sweep = hi.b_in_sweep;
+    return g;
 }
 
-bool launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind)
+EarlyGather launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind)
 {
-    if (M_max <= 0) return false;
+    if (M_max <= 0) return EarlyGather();
     if (e->exact && e->f32) return early_gather_impl<float, double, true>(e, M_max, d_M, kind);
     if (e->exact) return early_gather_impl<double, double, true>(e, M_max, d_M, kind);
     if (e->f32) return early_gather_impl<float, float, false>(e, M_max, d_M, kind);
@@ -1953,16 +1957,12 @@ bool launch_early_gather(EkfEngine *e, int M_max, const int *d_M, int kind)
 
 // the route, the two effects it reports (back-off bookkeeping) with what a retry needs, then the launches
 template <typename T, typename TB, bool EXACT = false>
-static void update_impl(EkfEngine *e, int M, int kind)
+static int update_impl(EkfEngine *e, const UpdateCall &call)
 {
-    // (armed by the step for the one update behind its rescue stage; every other update launches its own gather)
-    const bool early_armed = e->early_ga.armed;
-    e->early_ga.armed = false;
-    UpdateRoute r = choose_update_route(route_input<T, TB, EXACT>(e, M, kind));
+    UpdateRoute r = choose_update_route(route_input<T, TB, EXACT>(e, call));
     if (r.refusal) {
         e->err = r.refusal;
-        e->hook_rc = EKF_ERR_INVALID_ARG;
-        return;
+        return EKF_ERR_INVALID_ARG;
     }
 #ifdef EKF_SWEEP_TRACE // tuning runs and accuracy experiments of the debug build only
     if (const char *ev = std::getenv("EKF_PS_NT"); ev && r.persist) ps_set_tile_workers(r.ps, std::max(1, std::min(r.ps.n_t, atoi(ev))), e->n_cus);
@@ -1972,29 +1972,26 @@ static void update_impl(EkfEngine *e, int M, int kind)
     if (r.consumed_backoff) --e->ps_backoff;
     if (r.persist && ++e->ps_ok_streak >= 256) e->ps_backoff_len = 0;
     if (!r.col_rb.empty()) e->last_col_rb = r.col_rb; // (ekf_shard_counters)
-    e->last_update_M = M; // what a retry needs (engine.cpp: recover_failed_update)
-    e->last_update_kind = kind;
-    e->last_update_sym = e->p_exact_sym;
-    e->last_update_persist = r.persist;
-    e->last_update_stage = e->cons_stage;
+    e->last_update.call = call; // what a retry needs (engine.cpp: recover_failed_update)
+    e->last_update.sym = e->p_exact_sym;
+    e->last_update.persist = r.persist;
 
-    if (!exchange_p_diag(e, r)) return;
-    const bool early_done = early_armed && r.merged_ga && r.planes_b == e->early_ga.planes_b && r.apriori == e->early_ga.apriori &&
-                            r.persist == e->early_ga.persist && r.b_in_sweep == e->early_ga.b_in_sweep;
-    if (!gather_and_assemble<T, TB, EXACT>(e, r, early_done)) return;
-    if (!cholesky_sweep<TB, EXACT>(e, r)) return;
-    inverse_and_gemm<TB>(e, r);
-    if (!dx_and_state<T, TB, EXACT>(e, r)) return;
-    downdate_and_tail<T, TB, EXACT>(e, r);
+    int rc;
+    if ((rc = exchange_p_diag(e, r))) return rc;
+    if ((rc = gather_and_assemble<T, TB, EXACT>(e, r, call))) return rc;
+    if ((rc = cholesky_sweep<TB, EXACT>(e, r))) return rc;
+    if ((rc = inverse_and_gemm<TB>(e, r))) return rc;
+    if ((rc = dx_and_state<T, TB, EXACT>(e, r))) return rc;
+    return downdate_and_tail<T, TB, EXACT>(e, r, call);
 }
 
-void launch_update(EkfEngine *e, int M, int kind)
+int launch_update(EkfEngine *e, const UpdateCall &call)
 {
-    if (M <= 0) return;
-    if (e->exact && e->f32) update_impl<float, double, true>(e, M, kind);
-    else if (e->exact) update_impl<double, double, true>(e, M, kind);
-    else if (e->f32) update_impl<float, float>(e, M, kind);
-    else update_impl<double, double>(e, M, kind);
+    if (call.M <= 0) return EKF_OK;
+    if (e->exact && e->f32) return update_impl<float, double, true>(e, call);
+    if (e->exact) return update_impl<double, double, true>(e, call);
+    if (e->f32) return update_impl<float, float>(e, call);
+    return update_impl<double, double>(e, call);
 }
 
 } // namespace ekf

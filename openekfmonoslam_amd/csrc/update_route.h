@@ -22,6 +22,28 @@ struct PsLayout {
     int nbk, n_b, n_t, grid, layout_cus;
 };
 
+// kind of an update: the state alone (updateOnlyState), state and covariance, or the Schmidt-Kalman update of a fixed map (state
+// and covariance strip of the camera alone)
+enum { UPDATE_STATE_ONLY = 0, UPDATE_COV = 1, UPDATE_FIXED_MAP = 2 };
+
+// the gather / assembly launch a step enqueued ahead of its second update (launch_early_gather): whether anything was enqueued
+// and what it assumed of the route.  The step hands it to that one update in its UpdateCall.
+struct EarlyGather {
+    bool launched = false;
+    bool planes_b = false, apriori = false, persist = false, b_in_sweep = false;
+};
+
+// One update, as its caller asks for it (launch_update): everything the launcher is told, nothing it has to find in the engine.
+struct UpdateCall {
+    const EkfMatch *matches = nullptr; // the match list, on the device
+    int M = 0;
+    int kind = UPDATE_COV;       // UPDATE_*
+    int stage = 0;               // what the consistency record says: 0 ekf_update, 1 a step's first update, 2 its second
+    bool lean = false;           // sharded step: each rank gathered the rows of the matches it owns, an exchange completes them
+    bool force_launches = false; // the launch-per-panel sweep whatever sweep_mode says (the retry of a timed-out persistent sweep)
+    EarlyGather early;           // this update's merged gather / assembly launch may be enqueued already
+};
+
 struct UpdateRouteIn {
     int M = 0, n = 0; // matches (two rows each), state columns
     bool update_cov = true;
@@ -30,14 +52,15 @@ struct UpdateRouteIn {
     bool p_fp32 = false; // sizeof(T) == 4: P stored in fp32
     bool exact = false;  // EKF_PRECISION_F32_EXACT / _F64_EXACT
     int b_path = EKF_UPDATE_PATH_AUTO, sweep_mode = EKF_SWEEP_AUTO;
-    bool force_launches = false; // force_launches > 0: the retry of a timed-out persistent sweep
+    bool force_launches = false; // UpdateCall::force_launches: the retry of a timed-out persistent sweep
     bool ps_backoff = false;     // ps_backoff > 0: recent time-outs (a shared device), engine.h
     int shard_world = 1, shard_rank = 0;
     const int32_t *shard_row_begin = nullptr;
     size_t n_shard_row_begin = 0;
     bool Lq = false, Wq = false, Bstage = false, W = false, Tbuf = false, sweep_ctl = false; // which optional tables exist
     int bstage_rows = 0;
-    bool exchange_hook = false, after_gather = false;
+    bool exchange_hook = false;
+    bool after_gather = false; // UpdateCall::lean: the gathered rows are completed by an exchange behind the gather
     bool shard_rb_ok = false; // shard_rb has world + 1 entries
     int n_cus = 256;
     int ps_cap[2] = {0, 0}; // resident workgroups of k_chol_persist<false / true> (-1: unusable)
@@ -201,6 +224,30 @@ inline bool same_gather_launch(const UpdateRoute &a, const UpdateRoute &b)
     return !a.refusal && !b.refusal && a.merged_ga == b.merged_ga && a.planes_b == b.planes_b && a.apriori == b.apriori &&
            a.persist == b.persist && a.b_in_sweep == b.b_in_sweep && a.sharded == b.sharded && a.sym_g == b.sym_g &&
            a.b_fp32 == b.b_fp32 && a.n == b.n && a.n_pad == b.n_pad;
+}
+
+// what a call decides of the route's input (the rest is read of the engine: kernels_update.hip route_input)
+inline void route_input_of_call(UpdateRouteIn &in, const UpdateCall &c)
+{
+    in.M = c.M; in.update_cov = c.kind == UPDATE_COV; in.fixed_map = c.kind == UPDATE_FIXED_MAP;
+    in.after_gather = c.lean; in.force_launches = c.force_launches;
+}
+
+// whether the launch recorded in g is the merged gather / assembly launch of an update on route r: that update skips its own
+inline bool early_gather_serves(const EarlyGather &g, const UpdateRoute &r)
+{
+    return g.launched && r.merged_ga && r.planes_b == g.planes_b && r.apriori == g.apriori &&
+           r.persist == g.persist && r.b_in_sweep == g.b_in_sweep;
+}
+
+// the retry of an update whose persistent sweep timed out: the same update on the launch-per-panel sweep, every launch its own
+// (no lean exchange -- a sharded update's sweep is never persistent -- and no early gather)
+inline UpdateCall retry_of(const UpdateCall &c)
+{
+    UpdateCall r;
+    r.matches = c.matches; r.M = c.M; r.kind = c.kind; r.stage = c.stage;
+    r.force_launches = true;
+    return r;
 }
 
 // One launch of the launch-per-panel sweep, panels from row k0 on; have_pair: an earlier launch of this sweep was a pair launch

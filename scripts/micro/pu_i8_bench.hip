@@ -191,7 +191,7 @@ int main(int argc, char **argv)
         if (n_bad || asym) rc = 1;
         for (auto &pr : e.pu_events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
         for (auto &pr : e.px_events) { hipEventDestroy(pr.first); }
-        e.pu_events.clear(); e.px_events.clear(); e.pu_work.clear(); e.pu_m.clear();
+        e.pu_events.clear(); e.px_events.clear();
 
         // ---- timing, interleaved
         std::vector<float> t_px, t_slice, t_f32;
@@ -211,7 +211,7 @@ int main(int argc, char **argv)
             }
             for (auto &pr : e.pu_events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
             for (auto &pr : e.px_events) { hipEventDestroy(pr.first); }
-            e.pu_events.clear(); e.px_events.clear(); e.pu_work.clear(); e.pu_m.clear();
+            e.pu_events.clear(); e.px_events.clear();
         }
         auto med = [](std::vector<float> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
         auto mn = [](std::vector<float> v) { return *std::min_element(v.begin(), v.end()); };

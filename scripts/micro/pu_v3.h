@@ -169,7 +169,7 @@ static void launch_pu3(EkfEngine *e, int m_pad, int m)
 {
     const int n = e->n, nt = (n + 127) / 128;
     const int m_k = round_up(m, BK);
-    build_units(e, nt, 0, false, m_pad >= 512 ? 1 : 0);
+    build_units(e, nt, 0, false, m_pad >= 512 ? 1 : 0, e->pu_slots);
     k_pu3<BK, NST, MINW, ABL><<<e->pu_per_xcd * 8, 256, 0, e->stream>>>((float *)e->d.P, e->ldP, n, (const float *)e->d.A, e->ldP, m_k,
                                                                         e->pu_per_xcd, (const int4 *)e->d.pu_tilemap);
 }
@@ -385,7 +385,7 @@ template <int ABL>
 static void launch_pu_abl(EkfEngine *e, int m_pad, int m)
 {
     const int n = e->n, nt = (n + 127) / 128;
-    build_units(e, nt, 0, false, m_pad >= 512 ? 1 : 0);
+    build_units(e, nt, 0, false, m_pad >= 512 ? 1 : 0, e->pu_slots);
     k_pu_abl<ABL><<<e->pu_per_xcd * 8, 256, 0, e->stream>>>((float *)e->d.P, e->ldP, n, (const float *)e->d.A, e->ldP, round_up(m, 16),
                                                             e->pu_per_xcd, (const int4 *)e->d.pu_tilemap);
 }

@@ -288,6 +288,110 @@ static void pair_steps()
     }
 }
 
+// a route with the four fields the merged gather / assembly launch depends on (same_gather_launch), merged_ga as given
+static UpdateRoute route_with(bool planes_b, bool apriori, bool persist, bool b_in_sweep, bool merged_ga)
+{
+    UpdateRoute r;
+    r.planes_b = planes_b; r.apriori = apriori; r.persist = persist; r.b_in_sweep = b_in_sweep; r.merged_ga = merged_ga;
+    return r;
+}
+
+static void early_gather()
+{
+    CHECK(!EarlyGather().launched);
+    CHECK(!early_gather_serves(EarlyGather(), route_with(false, false, false, false, true))); // nothing was enqueued
+    for (int bits = 0; bits < 16; ++bits) { // every value of the four fields
+        const bool pb = bits & 1, ap = bits & 2, ps = bits & 4, bs = bits & 8;
+        EarlyGather g;
+        g.launched = true;
+        g.planes_b = pb; g.apriori = ap; g.persist = ps; g.b_in_sweep = bs;
+        CHECK(early_gather_serves(g, route_with(pb, ap, ps, bs, true)));
+        CHECK(!early_gather_serves(g, route_with(!pb, ap, ps, bs, true))); // any one of the four differs
+        CHECK(!early_gather_serves(g, route_with(pb, !ap, ps, bs, true)));
+        CHECK(!early_gather_serves(g, route_with(pb, ap, !ps, bs, true)));
+        CHECK(!early_gather_serves(g, route_with(pb, ap, ps, !bs, true)));
+        CHECK(!early_gather_serves(g, route_with(pb, ap, ps, bs, false))); // gather and assembly apart: the early launch is not this update's
+        g.launched = false;
+        CHECK(!early_gather_serves(g, route_with(pb, ap, ps, bs, true)));
+    }
+    // on real routes: what launch_early_gather records of one serves the same route, and not its launch-per-panel retry
+    for (Cfg c : ALL) {
+        const UpdateRoute r = choose_update_route(make(c, 16, 613));
+        EarlyGather g;
+        g.launched = true;
+        g.planes_b = r.planes_b; g.apriori = r.apriori; g.persist = r.persist; g.b_in_sweep = r.b_in_sweep;
+        CHECK(early_gather_serves(g, r));
+        UpdateRouteIn in = make(c, 16, 613);
+        in.force_launches = true;
+        CHECK(early_gather_serves(g, choose_update_route(in)) == !r.persist);
+    }
+}
+
+static void retries()
+{
+    static const EkfMatch list[2] = {};
+    for (int kind : {UPDATE_STATE_ONLY, UPDATE_COV, UPDATE_FIXED_MAP})
+        for (int stage : {0, 1, 2})
+            for (int flags = 0; flags < 8; ++flags) {
+                UpdateCall c;
+                c.matches = list + (stage & 1); c.M = 17 + stage; c.kind = kind; c.stage = stage;
+                c.lean = flags & 1; c.force_launches = flags & 2;
+                if (flags & 4) {
+                    c.early.launched = true;
+                    c.early.planes_b = c.early.apriori = c.early.persist = c.early.b_in_sweep = true;
+                }
+                const UpdateCall t = retry_of(c);
+                CHECK(t.matches == c.matches && t.M == c.M && t.kind == kind && t.stage == stage);
+                CHECK(t.force_launches && !t.lean);
+                CHECK(!t.early.launched && !t.early.planes_b && !t.early.apriori && !t.early.persist && !t.early.b_in_sweep);
+                CHECK(!early_gather_serves(t.early, route_with(false, false, false, false, true)));
+            }
+}
+
+// the route's input as a call fills it: force_launches and lean, both sides of each
+static void calls()
+{
+    for (int mode : {EKF_SWEEP_PAIRS, EKF_SWEEP_SINGLE, EKF_SWEEP_AUTO, EKF_SWEEP_PERSISTENT, EKF_SWEEP_LAUNCHES})
+        for (Cfg c : {F64, F32X})
+            for (int force = 0; force < 2; ++force) {
+                UpdateCall call;
+                call.M = 16; call.force_launches = force != 0;
+                UpdateRouteIn in = make(c, 1, 613);
+                in.sweep_mode = mode;
+                route_input_of_call(in, call);
+                const UpdateRoute r = choose_update_route(in);
+                const bool pm = mode == EKF_SWEEP_AUTO || mode == EKF_SWEEP_PERSISTENT;
+                CHECK(r.M == 16 && r.update_cov && !r.fixed_map);
+                CHECK(r.persist == (pm && !force));
+                // (the retry: the launch-per-panel sweep by the size rule whatever the mode)
+                CHECK(r.lmode == (!force && (mode == EKF_SWEEP_PAIRS || mode == EKF_SWEEP_SINGLE) ? mode : EKF_SWEEP_AUTO));
+            }
+    for (Cfg c : ALL)
+        for (int lean = 0; lean < 2; ++lean) {
+            UpdateCall call;
+            call.M = 16; call.lean = lean != 0;
+            UpdateRouteIn in = make(c, 1, 613);
+            route_input_of_call(in, call);
+            CHECK(choose_update_route(in).merged_ga == !lean); // one GPU: gather and assembly in one launch unless rows are exchanged between them
+            CHECK(!choose_update_route(in).sym_g);
+        }
+    for (int kind : {UPDATE_STATE_ONLY, UPDATE_COV, UPDATE_FIXED_MAP}) {
+        UpdateCall call;
+        call.M = 16; call.kind = kind;
+        UpdateRouteIn in = make(F64, 1, 613);
+        route_input_of_call(in, call);
+        CHECK(in.update_cov == (kind == UPDATE_COV) && in.fixed_map == (kind == UPDATE_FIXED_MAP));
+        const UpdateRoute r = choose_update_route(in);
+        CHECK(r.update_cov == (kind == UPDATE_COV) && r.fixed_map == (kind == UPDATE_FIXED_MAP));
+    }
+    // the retry of a call, end to end: never persistent, never lean
+    UpdateCall call;
+    call.M = 16; call.lean = true;
+    UpdateRouteIn in = make(F64, 1, 613);
+    route_input_of_call(in, retry_of(call));
+    CHECK(!choose_update_route(in).persist && choose_update_route(in).merged_ga);
+}
+
 int main()
 {
     auto_path_boundary();
@@ -296,6 +400,9 @@ int main()
     persistent_layout();
     sharded_exact();
     pair_steps();
+    early_gather();
+    retries();
+    calls();
     if (n_failed) {
         std::printf("update_route_check: %d checks failed\n", n_failed);
         return 1;

@@ -126,6 +126,38 @@ int ekf_descriptor_bytes(const EkfEngine *e); /* bytes per descriptor row (32, o
 int ekf_get_precision(const EkfEngine *e);    /* the EKF_PRECISION_* in use (what EKF_PRECISION_AUTO resolved to) */
 int ekf_num_features(const EkfEngine *e);
 
+/* -- the whole map in one buffer ------------------------------------------------------------- */
+/* A map blob is the complete filter and map, bit for bit: x13, the feature parameters, types, descriptors, timesPredicted /
+ * timesMatched and P always; with the bits of `sections` also the NCC templates, the template warp's source patches with their
+ * capture poses, and the patch normals (a table the engine never allocated is simply absent: no error).  It is little-endian,
+ * versioned, self-describing and checksummed; its format is a contract, written down in DESIGN.md 9.3.  P is stored in the
+ * engine's storage type, as the packed upper triangle (n (n + 1) / 2 elements) when it is bitwise symmetric (known after a
+ * covariance update, else found out by a read-only pass on the device: a predicted covariance is) and as the full square
+ * otherwise: both triangles are always recoverable bit for bit, and it is packed and checksummed on the device (kernels_mapblob.hip), so one copy moves n (n + 1) / 2 * w bytes.  The blob carries no
+ * modes or settings.  No counterpart in the reference. */
+enum { EKF_MAP_TEMPLATES = 1, EKF_MAP_WARP_SOURCES = 2, EKF_MAP_PATCH_NORMALS = 4, EKF_MAP_ALL = 7 };
+/* The size ekf_save_map would write now. */
+int ekf_map_blob_bytes(EkfEngine *e, int sections, size_t *bytes);
+/* Writes the blob; *bytes receives its size.  EKF_ERR_CAPACITY when `capacity` is too small (*bytes: the size needed, nothing
+ * written).  Read-only: no state, no P and no per-feature table is written (the second covariance buffer of the out-of-place map
+ * passes is the staging buffer, allocated on first use).  Synchronises the stream and first reports a pending asynchronous error
+ * as ekf_update_external does, and then does nothing else.  A sharded engine: EKF_ERR_INVALID_ARG. */
+int ekf_save_map(EkfEngine *e, int sections, void *blob, size_t capacity, size_t *bytes);
+/* Replaces the engine's filter and map by the blob's.  The blob is untrusted: everything is validated on the host first (never
+ * reading outside [blob, blob + bytes)), then P is uploaded and checked on the device (checksum, every entry finite, diagonal
+ * > 0), and only then is anything written: a load that is refused leaves the engine bit for bit as it was (a table the blob needs
+ * and the engine lacks is allocated, zero-filled, before; the modes stay as they are).  EKF_ERR_INVALID_ARG: malformed, truncated
+ * or corrupt blob, another descriptor format than the engine's, a sharded engine (ekf_last_error names the field);
+ * EKF_ERR_CAPACITY: more features than max_features; EKF_ERR_NON_FINITE: the device check found a bad entry of P.  P may have
+ * another element size than the engine's: fp32 widens exactly, fp64 is rounded once to nearest.  Afterwards the engine is where
+ * ekf_set_state would leave it, except that the counters, templates, source patches, capture poses and normals hold the blob's
+ * values (zero for features 0..N-1 where the section is absent), P counts as bitwise symmetric exactly for a triangle blob, and no
+ * retry of an earlier update is pending.  Settings and modes are untouched; the blob's camera is reported in *info (may be NULL)
+ * and not compared.  Pending asynchronous errors: as ekf_save_map. */
+int ekf_load_map(EkfEngine *e, const void *blob, size_t bytes, EkfMapBlobInfo *info);
+/* Host only (no engine, no device): validates the blob, all checksums included, and reports its header. */
+int ekf_map_blob_info(const void *blob, size_t bytes, EkfMapBlobInfo *info);
+
 /* -- map management: the state dimension changes, P is edited in place on the device ------ */
 /* initState + initCovariance                              EKF/CommonFunctions.cpp:39-80 (empties the map) */
 int ekf_reset(EkfEngine *e);

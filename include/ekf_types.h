@@ -150,6 +150,20 @@ typedef struct EkfExternalUpdate {
     int32_t applied;            /* 1: x and P were updated; 0: the gate rejected it, nothing changed */
 } EkfExternalUpdate;            /* 144 bytes, no padding */
 
+/* What the header of a map blob says (ekf_save_map / ekf_load_map / ekf_map_blob_info; the format: DESIGN.md 9.3).  No
+ * counterpart in the reference, which cannot save its map. */
+typedef struct EkfMapBlobInfo {
+    uint32_t version;      /* 1                                                                                      */
+    int32_t N, n;          /* features, state dimension                                                              */
+    int32_t p_elem_bytes;  /* 4 or 8: P is stored as the saving engine stored it                                     */
+    int32_t p_layout;      /* 0 = packed upper triangle (P was bitwise symmetric), 1 = full square                   */
+    int32_t desc_bytes;    /* bytes per descriptor row                                                               */
+    int32_t desc_flags;    /* EkfEngineConfig::flags of the saving engine                                            */
+    uint32_t section_mask; /* EKF_MAP_* of the optional sections present                                             */
+    uint64_t total_bytes;
+    EkfCamera cam;         /* the camera the blob was saved under: reported, never compared                          */
+} EkfMapBlobInfo;          /* 40 + 104 = 144 bytes, no padding                                                       */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

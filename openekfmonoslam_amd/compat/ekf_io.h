@@ -609,6 +609,36 @@ inline void writeMapPly(EkfEngine *e, const std::string &path, bool normals = fa
     if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + path);
 }
 
+// ------------------------------------------------------------------------------------------- the whole map in one file
+// (ekf_save_map / ekf_load_map, DESIGN.md 9.3: the file is the blob, byte for byte).  Short writes and reads are reported.
+inline void saveMapFile(EkfEngine *e, const std::string &path, int sections = EKF_MAP_ALL)
+{
+    size_t bytes = 0;
+    if (ekf_map_blob_bytes(e, sections, &bytes) != EKF_OK) throw std::runtime_error(std::string("ekf_map_blob_bytes: ") + ekf_last_error(e));
+    std::vector<uint8_t> blob(bytes);
+    if (ekf_save_map(e, sections, blob.data(), blob.size(), &bytes) != EKF_OK) throw std::runtime_error(std::string("ekf_save_map: ") + ekf_last_error(e));
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot write " + path);
+    const size_t put = std::fwrite(blob.data(), 1, bytes, f);
+    if (std::fclose(f) != 0 || put != bytes)
+        throw std::runtime_error("short write to " + path + ": " + std::to_string(put) + " of " + std::to_string(bytes) + " bytes");
+}
+
+inline EkfMapBlobInfo loadMapFile(EkfEngine *e, const std::string &path)
+{
+    std::FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("cannot read " + path);
+    std::vector<uint8_t> blob;
+    uint8_t chunk[1 << 16];
+    for (size_t got; (got = std::fread(chunk, 1, sizeof(chunk), f)) > 0;) blob.insert(blob.end(), chunk, chunk + got);
+    const bool failed = std::ferror(f) != 0;
+    std::fclose(f);
+    if (failed) throw std::runtime_error("short read from " + path + ": stopped after " + std::to_string(blob.size()) + " bytes");
+    EkfMapBlobInfo info;
+    if (ekf_load_map(e, blob.data(), blob.size(), &info) != EKF_OK) throw std::runtime_error("ekf_load_map(" + path + "): " + ekf_last_error(e));
+    return info;
+}
+
 // ------------------------------------------------------------------------------------------------ ImageEKF
 // class EKF of the reference (1PointRansacEKF/EKF.h:41-63) with its own constructor arguments, image in.
 class ImageEKF {
@@ -835,6 +865,20 @@ public:
     // the map as 3-D points with covariances (device export), and the same as an ASCII PLY file
     void mapPoints(std::vector<EkfMapPoint> &points) { ekf_compat::mapPoints(e_, points); }
     void writeMapPly(const std::string &path) { ekf_compat::writeMapPly(e_, path, patchNormals_); }
+    // The whole filter and map in one file (ekf_save_map: state, covariance, descriptors, counters, NCC templates, the warp's
+    // source patches and the patch normals), and the way to start from such a file INSTEAD of init(image): the first step() then
+    // runs on the loaded map.  The modes and settings are not in the file: set them as for init().
+    void saveMap(const std::string &path) { ekf_compat::saveMapFile(e_, path); }
+    EkfMapBlobInfo loadMap(const std::string &path)
+    {
+        if (log_.is_open()) {
+            log_ << "Map loaded from: " << path << std::endl << std::endl;
+            log_ << "~~~~~~~~~~~~ STEP " << steps_ << " ~~~~~~~~~~~~" << std::endl;
+        }
+        const EkfMapBlobInfo info = ekf_compat::loadMapFile(e_, path);
+        logState();
+        return info;
+    }
     EkfEngine *engine() { return e_; }
     int steps() const { return steps_; }
     const EkfCamera &camera() const { return cam_; }

@@ -1,6 +1,7 @@
 // engine.cpp -- C ABI of the MI355X EKF engine (see include/ekf_engine.h).  Host orchestration only: every
 // number is produced by the HIP kernels in kernels_*.hip; there is no CPU compute path.
 #include "engine.h"
+#include "map_blob.h"
 #include "../../include/ekf_test_hooks.h"
 
 #include <cmath>
@@ -643,6 +644,10 @@ int ekf_set_state(EkfEngine *e, const double x13[13], int n_features, const doub
     if (e->d.wpose) HIPCHK(hipMemset(e->d.wpose, 0, (size_t)e->cap * WPOSE_DOUBLES * sizeof(double))); // template warp: no feature has a source patch
     if (e->d.wnorm) HIPCHK(hipMemset(e->d.wnorm, 0, (size_t)e->cap * sizeof(PatchNormalRec))); // patch normals: no feature has an estimate
     e->last_match_warped = false; // d.wtmpl belongs to the map the last match saw
+    // an update still unread (ekf_set_async_errors) belongs to the map that was: if it is found timed out it is reported, not run
+    // again on this one
+    e->last_update.persist = false;
+    e->last_update.sym = e->p_exact_sym;
     return EKF_OK;
 }
 
@@ -676,6 +681,245 @@ int ekf_get_state(EkfEngine *e, double x13[13], double *feature_pos, double *P)
         }
     }
     return pending;
+}
+
+// ------------------------------------------------------------------------------------------------ map blob
+// (the format and the host-side validation: map_blob.h, the P section: kernels_mapblob.hip)
+static int second_P(EkfEngine *e);
+
+static int map_blob_refusal(EkfEngine *e, const char *who)
+{
+    if (e->shard_world > 1) {
+        e->err = std::string(who) + ": not available on a sharded engine";
+        return EKF_ERR_INVALID_ARG;
+    }
+    return EKF_OK;
+}
+
+static int map_blob_ctl(EkfEngine *e)
+{
+    if (e->d.mb_ctl) return EKF_OK;
+    const hipError_t st = e->bufs.alloc(&e->d.mb_ctl, 1);
+    if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc map blob control record");
+    return EKF_OK;
+}
+
+// The shape of the blob the engine would write now.  The packed triangle needs a bitwise symmetric P: where the engine does not
+// know it symmetric already (p_exact_sym: every covariance update leaves it so), a read-only pass on the device finds out -- a
+// predicted covariance is, an uploaded one or the map block a fixed-map update leaves alone need not be.
+static int map_blob_shape(EkfEngine *e, int sections, mapblob::Shape *out)
+{
+    mapblob::Shape s;
+    s.N = e->N;
+    s.n = e->n;
+    s.p_elem_bytes = e->f32 ? 4 : 8;
+    bool sym = e->p_exact_sym;
+    if (!sym) {
+        if (const int rc = map_blob_ctl(e)) return rc;
+        launch_map_asym(e, e->d.mb_ctl);
+        HIPCHK(hipGetLastError());
+        MapBlobCtl ctl;
+        HIPCHK(hipMemcpyAsync(&ctl, e->d.mb_ctl, sizeof(ctl), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        sym = ctl.asym == 0;
+    }
+    s.p_layout = sym ? mapblob::P_TRIANGLE : mapblob::P_FULL;
+    s.desc_bytes = e->desc_bytes;
+    s.desc_flags = e->cfg.flags;
+    s.mask = (uint32_t)sections & mapblob::MASK_TEMPLATES;
+    if ((sections & EKF_MAP_WARP_SOURCES) && e->d.wsrc && e->d.wpose) s.mask |= mapblob::MASK_WARP_SOURCES;
+    if ((sections & EKF_MAP_PATCH_NORMALS) && e->d.wnorm) s.mask |= mapblob::MASK_PATCH_NORMALS;
+    *out = s;
+    return EKF_OK;
+}
+
+int ekf_map_blob_bytes(EkfEngine *e, int sections, size_t *bytes)
+{
+    if (!e || !bytes || (sections & ~EKF_MAP_ALL)) return EKF_ERR_INVALID_ARG;
+    if (const int rc = map_blob_refusal(e, "ekf_map_blob_bytes")) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    mapblob::Shape s;
+    if (const int rc = map_blob_shape(e, sections, &s)) return rc;
+    *bytes = (size_t)mapblob::layout_of(s).total;
+    return EKF_OK;
+}
+
+int ekf_save_map(EkfEngine *e, int sections, void *blob_, size_t capacity, size_t *bytes)
+{
+    if (!e || !bytes || (sections & ~EKF_MAP_ALL)) return EKF_ERR_INVALID_ARG;
+    if (const int rc = map_blob_refusal(e, "ekf_save_map")) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc = take_pending_error(e); // as ekf_update_external: the failed update it reports is not this call's
+    if (rc) return rc;
+    mapblob::Shape s;
+    if ((rc = map_blob_shape(e, sections, &s))) return rc;
+    const mapblob::Layout L = mapblob::layout_of(s);
+    *bytes = (size_t)L.total;
+    if (!blob_ || capacity < L.total) {
+        e->err = "ekf_save_map: the buffer holds " + std::to_string(capacity) + " bytes, the blob needs " + std::to_string(L.total);
+        return blob_ ? EKF_ERR_CAPACITY : EKF_ERR_INVALID_ARG;
+    }
+    if ((rc = second_P(e))) return rc; // the staging buffer of the P section
+    if ((rc = map_blob_ctl(e))) return rc;
+    uint8_t *blob = (uint8_t *)blob_;
+    mapblob::zero_gaps(blob, L);
+    launch_map_pack(e, s.p_layout, e->d.P2, e->d.mb_ctl);
+    HIPCHK(hipGetLastError());
+    MapBlobCtl ctl;
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(&ctl, e->d.mb_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(blob + L.offset[mapblob::SEC_P], e->d.P2, (size_t)L.bytes[mapblob::SEC_P], hipMemcpyDeviceToHost, st));
+    // the per-feature tables are contiguous in map order: plain copies
+    const void *table[mapblob::N_SECTIONS] = {e->d.state, e->d.feat_pos, e->d.feat_type, e->d.feat_desc, e->d.feat_times_predicted,
+                                              e->d.feat_times_matched, nullptr, e->d.tmpl, e->d.wsrc, e->d.wpose, e->d.wnorm, nullptr};
+    for (int id = 0; id < mapblob::N_SECTIONS; ++id)
+        if (table[id] && L.present[id] && L.bytes[id] > 0)
+            HIPCHK(hipMemcpyAsync(blob + L.offset[id], table[id], (size_t)L.bytes[id], hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(blob + L.offset[mapblob::SEC_CAMERA], &e->cfg.cam, sizeof(EkfCamera));
+    uint64_t sums[mapblob::N_SECTIONS];
+    for (int id = 0; id < mapblob::N_SECTIONS; ++id)
+        sums[id] = !L.present[id] ? 0 : (id == mapblob::SEC_P ? (uint64_t)ctl.sum : mapblob::checksum(blob + L.offset[id], L.bytes[id]));
+    mapblob::write_header(blob, s, L, sums);
+    return EKF_OK;
+}
+
+int ekf_map_blob_info(const void *blob, size_t bytes, EkfMapBlobInfo *info)
+{
+    mapblob::Parsed p;
+    if (!mapblob::parse(blob, bytes, true, &p, nullptr)) return EKF_ERR_INVALID_ARG;
+    if (info) *info = mapblob::info_of(p);
+    return EKF_OK;
+}
+
+int ekf_load_map(EkfEngine *e, const void *blob_, size_t bytes, EkfMapBlobInfo *info)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (const int rc = map_blob_refusal(e, "ekf_load_map")) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc = take_pending_error(e); // as ekf_save_map
+    if (rc) return rc;
+    // 1. everything the host can check
+    mapblob::Parsed p;
+    if (!mapblob::parse(blob_, bytes, false, &p, &e->err)) return EKF_ERR_INVALID_ARG;
+    const uint8_t *blob = (const uint8_t *)blob_;
+    const mapblob::Shape &s = p.shape;
+    const mapblob::Layout &L = p.layout;
+    if (s.desc_bytes != e->desc_bytes || s.desc_flags != e->cfg.flags) {
+        e->err = "map blob: desc_bytes / desc_flags " + std::to_string(s.desc_bytes) + " / " + std::to_string(s.desc_flags) +
+                 " are not the engine's descriptor format " + std::to_string(e->desc_bytes) + " / " + std::to_string(e->cfg.flags);
+        return EKF_ERR_INVALID_ARG;
+    }
+    if (s.N > e->cap) {
+        e->err = "map blob: N = " + std::to_string(s.N) + " exceeds the engine's max_features = " + std::to_string(e->cap);
+        return EKF_ERR_CAPACITY;
+    }
+    const int N = s.N, n = s.n;
+    // 2. tables the blob needs and the engine lacks (zeroed; the modes stay as they are).  The normals are read beside the capture poses
+    const bool has_warp = L.present[mapblob::SEC_WARP_SOURCES], has_norm = L.present[mapblob::SEC_PATCH_NORMALS];
+    if ((has_warp || has_norm) && !e->d.wpose) {
+        const size_t cap = (size_t)e->cap;
+        auto g = e->bufs.group(); // as ekf_set_template_warp
+        g.alloc(&e->d.wsrc, cap * 3 * WARP_SS);
+        g.alloc(&e->d.wtmpl, cap * 3 * NCC_TT);
+        g.alloc(&e->d.wpose, cap * WPOSE_DOUBLES);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "template warp tables");
+    }
+    if (has_norm && !e->d.wnorm) {
+        auto g = e->bufs.group(); // as ekf_set_patch_normals
+        g.alloc(&e->d.wnorm, (size_t)e->cap);
+        g.alloc(&e->d.pn_list, (size_t)e->cap);
+        if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "patch normal tables");
+    }
+    if ((rc = map_blob_ctl(e))) return rc;
+    // 3. P goes up into a staging buffer and is checked there: d.P2 where the section fits (always when the element sizes agree),
+    // else a buffer of this call's
+    const size_t p_bytes = (size_t)L.bytes[mapblob::SEC_P];
+    const size_t p2_bytes = (size_t)round_up(e->ncap, LD_ALIGN) * e->ldP * (e->f32 ? 4 : 8);
+    void *staging = nullptr, *own = nullptr;
+    if (p_bytes <= p2_bytes) {
+        if ((rc = second_P(e))) return rc;
+        staging = e->d.P2;
+    } else {
+        const hipError_t st = hipMalloc(&own, p_bytes);
+        if (st != hipSuccess) return alloc_failed(e, st, "hipMalloc map blob staging");
+        staging = own;
+    }
+    hipStream_t st = e->stream;
+    MapBlobCtl ctl;
+    auto staged = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(staging, blob + L.offset[mapblob::SEC_P], p_bytes, hipMemcpyHostToDevice, st));
+        launch_map_check(e, staging, n, s.p_elem_bytes, s.p_layout, e->d.mb_ctl);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&ctl, e->d.mb_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((uint64_t)ctl.sum != p.sums[mapblob::SEC_P]) {
+            e->err = "map blob: section P: checksum does not match its bytes";
+            return EKF_ERR_INVALID_ARG;
+        }
+        if (ctl.non_finite || ctl.bad_diag) {
+            e->err = "map blob: section P: " + std::to_string(ctl.non_finite) + " entries are not finite, " + std::to_string(ctl.bad_diag) +
+                     " diagonal entries are not > 0";
+            return EKF_ERR_NON_FINITE;
+        }
+        // 4. only now is anything written
+        double stt[ST_R + 9];
+        std::memcpy(stt, blob + L.offset[mapblob::SEC_X13], 13 * sizeof(double));
+        quat_to_rot(stt + 3, stt + ST_R);
+        HIPCHK(hipMemcpyAsync(e->d.state, stt, sizeof(stt), hipMemcpyHostToDevice, st));
+        std::vector<int> type(N), covpos(N);
+        if (N > 0) std::memcpy(type.data(), blob + L.offset[mapblob::SEC_FEAT_TYPE], (size_t)N * 4);
+        for (int i = 0, pos = 13; i < N; ++i) {
+            covpos[i] = pos;
+            pos += type[i] == EKF_FEATURE_INVERSE_DEPTH ? 6 : 3;
+        }
+        const size_t cap = (size_t)e->cap;
+        // whole tables as ekf_set_state leaves them, then the blob's values for the features 0 .. N - 1
+        HIPCHK(hipMemsetAsync(e->d.feat_times_predicted, 0, cap * sizeof(unsigned), st));
+        HIPCHK(hipMemsetAsync(e->d.feat_times_matched, 0, cap * sizeof(unsigned), st));
+        if (e->d.wpose) HIPCHK(hipMemsetAsync(e->d.wpose, 0, cap * WPOSE_DOUBLES * sizeof(double), st));
+        if (e->d.wnorm) HIPCHK(hipMemsetAsync(e->d.wnorm, 0, cap * sizeof(PatchNormalRec), st));
+        if (N > 0) {
+            HIPCHK(hipMemcpyAsync(e->d.feat_covpos, covpos.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, st));
+            void *table[mapblob::N_SECTIONS] = {nullptr, e->d.feat_pos, e->d.feat_type, e->d.feat_desc, e->d.feat_times_predicted,
+                                                e->d.feat_times_matched, nullptr, e->d.tmpl, e->d.wsrc, e->d.wpose, e->d.wnorm, nullptr};
+            const size_t absent_bytes[mapblob::N_SECTIONS] = {0, 0, 0, 0, 0, 0, 0, (size_t)N * 3 * NCC_TT, (size_t)N * 3 * WARP_SS, 0, 0, 0};
+            for (int id = 0; id < mapblob::N_SECTIONS; ++id) {
+                if (!table[id]) continue;
+                if (L.present[id]) HIPCHK(hipMemcpyAsync(table[id], blob + L.offset[id], (size_t)L.bytes[id], hipMemcpyHostToDevice, st));
+                else if (absent_bytes[id]) HIPCHK(hipMemsetAsync(table[id], 0, absent_bytes[id], st));
+            }
+        }
+        HIPCHK(hipMemsetAsync(e->d.P, 0, (size_t)e->p_rows_cap * e->ldP * (e->f32 ? 4 : 8), st));
+        launch_map_unpack(e, staging, n, s.p_elem_bytes, s.p_layout);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(e->d.pred_vis, 0, cap * sizeof(int), st));
+        HIPCHK(hipMemsetAsync(e->d.pred_vis_full, 0, cap * sizeof(int), st));
+        HIPCHK(hipStreamSynchronize(st)); // (the copies above read this call's vectors and the caller's blob)
+        e->N = N;
+        e->n = n;
+        e->n_pred = 0;
+        e->n_gates = 0;
+        e->h_type = type;
+        e->h_covpos = covpos;
+        refresh_row_map(e);
+        e->n_step_preds = 0;
+        e->bud_recs_n = e->bud_predicted = e->bud_selected = 0;
+        e->last_match_warped = false;
+        e->p_exact_sym = s.p_layout == mapblob::P_TRIANGLE;
+        e->last_update = decltype(e->last_update)(); // no update of the map that was is run again on this one
+        e->last_update.sym = e->p_exact_sym;
+        return EKF_OK;
+    };
+    rc = staged();
+    if (rc != EKF_OK && rc != EKF_ERR_HIP && !own) (void)hipMemsetAsync(staging, 0, p_bytes, st); // a refused section does not stay in d.P2
+    (void)hipStreamSynchronize(st);
+    if (own) (void)hipFree(own);
+    if (rc == EKF_OK && info) *info = mapblob::info_of(p);
+    return rc;
 }
 
 

@@ -114,6 +114,14 @@ struct FmCtl {
     long long updates;
 };
 
+// map blob (ekf_save_map / ekf_load_map): what the kernels of kernels_mapblob.hip accumulate over a P section
+struct MapBlobCtl {
+    unsigned long long sum; // the section's checksum (map_blob.h)
+    unsigned non_finite;    // entries that are not finite (k_map_check)
+    unsigned bad_diag;      // diagonal entries that are not > 0 (k_map_check)
+    unsigned asym, pad;     // entries above the diagonal whose bits differ from their mirror's (k_map_asym)
+};
+
 // 1-point RANSAC: what a hypothesis needs of one match, gathered once per frame by the launch that writes the feature -> match index
 // (k_match_compact on the step path, k_match_index behind an arbitrary list) so that the hypotheses' workgroups read ONE contiguous
 // record per match instead of chasing match -> feature -> type / position / parameters through four tables each
@@ -255,6 +263,7 @@ struct DeviceArrays {
     int *bud_all = nullptr;                // the list before the selection (the compaction writes d.plist from it)
     int *bud_flag = nullptr;               // selected?
     EkfMeasurementRank *bud_recs = nullptr; // ekf_get_measurement_ranks
+    MapBlobCtl *mb_ctl = nullptr; // map blob (ekf_save_map / ekf_load_map; allocated by the first of them)
     float *Pdiag = nullptr;     // sharded exact configuration: diagonal of P, n floats, completed by an exchange
     int8_t *Bstage = nullptr;   // ... and the digit planes of B in the exchange layout [column][plane][k / 16][16]
 };
@@ -593,6 +602,14 @@ constexpr int CA_TILE = 64, CA_CW = 132;
 // d.ca_rows (n_new rows), and the swap of the two buffers
 void launch_convert_all(EkfEngine *e, int count, int n_new);
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
+// map blob (kernels_mapblob.hip; layout: mapblob::P_TRIANGLE / P_FULL of map_blob.h).  _pack: the engine's P -> the flat section in
+// `staging`, its checksum -> *d_ctl (zeroed first).  _check: read-only pass over an uploaded section of n rows and elem_bytes per
+// element -> *d_ctl (zeroed first).  _unpack: such a section -> the engine's P (rows and columns below n; both triangles)
+// _asym: read-only pass over the engine's P, counts the pairs (i, j > i) that are not bitwise equal -> d_ctl->asym (zeroed first)
+void launch_map_asym(EkfEngine *e, MapBlobCtl *d_ctl);
+void launch_map_pack(EkfEngine *e, int layout, void *staging, MapBlobCtl *d_ctl);
+void launch_map_check(EkfEngine *e, const void *staging, int n, int elem_bytes, int layout, MapBlobCtl *d_ctl);
+void launch_map_unpack(EkfEngine *e, const void *staging, int n, int elem_bytes, int layout);
 // external measurement update (kernels_external.hip): the call's ExtCtl is in d.ext_ctl; enqueues A = H P, the solve, the state
 // update, the downdate and the normalisation of the covariance, and leaves the record in d.ext_res
 void launch_external_update(EkfEngine *e, int m);

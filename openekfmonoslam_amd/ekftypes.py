@@ -142,6 +142,18 @@ class EkfExternalUpdate(C.Structure):
 
 assert C.sizeof(EkfExternalUpdate) == 144
 
+
+
+class EkfMapBlobInfo(C.Structure):
+    """What the header of a map blob says (ekf_load_map / ekf_map_blob_info); 144 bytes, no padding."""
+
+    _fields_ = [("version", C.c_uint32), ("N", C.c_int32), ("n", C.c_int32), ("p_elem_bytes", C.c_int32), ("p_layout", C.c_int32),
+                ("desc_bytes", C.c_int32), ("desc_flags", C.c_int32), ("section_mask", C.c_uint32), ("total_bytes", C.c_uint64),
+                ("cam", EkfCamera)]
+
+
+assert C.sizeof(EkfMapBlobInfo) == 144
+
 DESC_BYTES = 32
 FEATURE_DEPTH = 1
 FEATURE_INVERSE_DEPTH = 2

@@ -13,12 +13,13 @@ import numpy as np
 
 from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
                        MEASUREMENT_RANK_DTYPE, NCC_RIVAL_DTYPE,
-                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapPoint, EkfParams, EkfStepInfo)
+                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapBlobInfo, EkfMapPoint, EkfParams, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
 PRECISION_F64, PRECISION_F32, PRECISION_F32_EXACT, PRECISION_F64_EXACT, PRECISION_AUTO = 0, 1, 2, 3, 4
 IMAGE_MATCHER_NCC, IMAGE_MATCHER_KEYPOINTS = 0, 1
+MAP_TEMPLATES, MAP_WARP_SOURCES, MAP_PATCH_NORMALS, MAP_ALL = 1, 2, 4, 7  # EKF_MAP_*: optional sections of a map blob
 
 
 class EkfEngineConfig(C.Structure):
@@ -76,6 +77,10 @@ ABI = {
     "ekf_set_state": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "ekf_get_state": (_i, [_vp, _vp, _vp, _vp]),
     "ekf_get_map_features": (_i, [_vp, _vp, _vp, _vp]),
+    "ekf_map_blob_bytes": (_i, [_vp, _i, C.POINTER(C.c_size_t)]),
+    "ekf_save_map": (_i, [_vp, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ekf_load_map": (_i, [_vp, _vp, C.c_size_t, C.POINTER(EkfMapBlobInfo)]),
+    "ekf_map_blob_info": (_i, [_vp, C.c_size_t, C.POINTER(EkfMapBlobInfo)]),
     "ekf_reset": (_i, [_vp]),
     "ekf_add_features": (_i, [_vp, _vp, _vp, _i]),
     "ekf_remove_features": (_i, [_vp, _vp, _i]),
@@ -242,6 +247,22 @@ def comm_unique_id():
     return buf
 
 
+def _blob_info_dict(info):
+    d = {name: int(getattr(info, name)) for name, _ in EkfMapBlobInfo._fields_ if name != "cam"}
+    d["cam"] = {name: getattr(info.cam, name) for name, _ in EkfCamera._fields_}
+    return d
+
+
+def map_blob_info(blob):
+    """Validates a map blob on the host (no engine, no device; every checksum included) and returns its header as a dict."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8)
+    info = EkfMapBlobInfo()
+    rc = load_library().ekf_map_blob_info(_p(b), b.size, C.byref(info))
+    if rc:
+        raise EkfError(rc, "not a valid map blob")
+    return _blob_info_dict(info)
+
+
 class EkfEngine:
     """One device-resident filter (state, covariance, map, per-frame tables) on one MI355X."""
 
@@ -351,6 +372,28 @@ class EkfEngine:
         P = P_out if P_out is not None else (np.zeros((self.n, self.n)) if want_P else None)
         self._chk(self.L.ekf_get_state(self.h, _p(x), _p(fp), _p(P)))
         return x, fp[: self.N], P
+
+    def map_blob_bytes(self, sections=MAP_ALL):
+        """size of the blob save_map would return now"""
+        nb = C.c_size_t(0)
+        self._chk(self.L.ekf_map_blob_bytes(self.h, int(sections), C.byref(nb)))
+        return nb.value
+
+    def save_map(self, sections=MAP_ALL):
+        """The whole filter and map as one blob (np.uint8): state, map, counters, P packed on the device, and with `sections` the
+        NCC templates, the warp's source patches and capture poses, the patch normals.  Read-only."""
+        blob = np.zeros(self.map_blob_bytes(sections), dtype=np.uint8)
+        nb = C.c_size_t(0)
+        self._chk(self.L.ekf_save_map(self.h, int(sections), _p(blob), blob.size, C.byref(nb)))
+        assert nb.value == blob.size
+        return blob
+
+    def load_map(self, blob):
+        """Replaces the filter and map by the blob's; a refused blob leaves the engine as it was.  Returns the blob's header."""
+        b = np.ascontiguousarray(blob, dtype=np.uint8)
+        info = EkfMapBlobInfo()
+        self._chk(self.L.ekf_load_map(self.h, _p(b), b.size, C.byref(info)))
+        return _blob_info_dict(info)
 
     def camera_covariance(self):
         P = np.zeros((13, 13))

@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -30,6 +30,10 @@
 // configuration's LinearAccelSD and AngularAccelSD were tuned per frame and then keep their meaning; a frame after k dropped ones
 // gets dt = k + 1.  A time that does not increase, or a number of times that differs from the number of frames, is an error
 // before the first frame is touched.
+// --save-map FILE (likewise): after the last frame the whole filter and map go to FILE (ImageEKF::saveMap: one blob).
+// --load-map FILE (likewise): the filter starts from such a file instead of initialising on the first frame, which is then stepped
+// on like the others (ImageEKF::loadMap); with --fixed-map-from 0 the run localises on the loaded map from its first step, with
+// the templates of the run that saved it.  The modes (--warp-templates, --patch-normals, ...) are not in the file: give them again.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -70,14 +74,17 @@ int main(int argc, const char *argv[])
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false, convertAll = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
     int budget = 0, fixedFrom = -1;
-    std::string fixesFile, timesFile;
+    std::string fixesFile, timesFile, saveMapFile, loadMapFile;
     double timeUnit = 1.0;
     for (int i = 1; i < argc; ++i)
         if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes" ||
-             std::string(argv[i]) == "--fixed-map-from" || std::string(argv[i]) == "--timestamps" || std::string(argv[i]) == "--time-unit") &&
+             std::string(argv[i]) == "--fixed-map-from" || std::string(argv[i]) == "--timestamps" || std::string(argv[i]) == "--time-unit" ||
+             std::string(argv[i]) == "--save-map" || std::string(argv[i]) == "--load-map") &&
             i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
             else if (std::string(argv[i]) == "--timestamps") timesFile = argv[i + 1];
+            else if (std::string(argv[i]) == "--save-map") saveMapFile = argv[i + 1];
+            else if (std::string(argv[i]) == "--load-map") loadMapFile = argv[i + 1];
             else if (std::string(argv[i]) == "--time-unit") timeUnit = std::atof(argv[i + 1]);
             else if (std::string(argv[i]) == "--fixed-map-from") fixedFrom = std::max(std::atoi(argv[i + 1]), 0);
             else if (std::string(argv[i]) == "--position-fixes") fixesFile = argv[i + 1];
@@ -96,7 +103,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -113,7 +120,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty()) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty() && saveMapFile.empty() && loadMapFile.empty()) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -131,7 +138,7 @@ int main(int argc, const char *argv[])
             if (!outputPath.empty()) ekf_compat::writeMapPly(extendedKalmanFilter.engine(), outputPath + "map.ply");
             return 0;
         }
-        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map, the batch conversion or frame times asked for: the driver class with its extra arguments)
+        // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map, the batch conversion, frame times or a map file asked for: the driver class with its extra arguments)
         ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
@@ -146,9 +153,14 @@ int main(int argc, const char *argv[])
         std::FILE *csv = 0;
         if (consistency && !outputPath.empty() && !(csv = std::fopen((outputPath + "consistency.csv").c_str(), "w")))
             throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
-        extendedKalmanFilter.init(image);
-        std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
-        image = generator.getNextImage();
+        if (loadMapFile.empty()) {
+            extendedKalmanFilter.init(image);
+            std::printf("init: %d features\n", ekf_num_features(extendedKalmanFilter.engine()));
+            image = generator.getNextImage();
+        } else { // the first frame is a step like the others
+            const EkfMapBlobInfo info = extendedKalmanFilter.loadMap(loadMapFile);
+            std::printf("loaded map: %d features, %llu bytes\n", info.N, (unsigned long long)info.total_bytes);
+        }
         while (!image.empty()) {
             if (fixedFrom >= 0 && extendedKalmanFilter.steps() + 1 >= fixedFrom && !extendedKalmanFilter.fixedMap()) extendedKalmanFilter.setFixedMap(true);
             if (!intervals.empty()) extendedKalmanFilter.setFrameInterval(intervals[(size_t)extendedKalmanFilter.steps() + 1]);
@@ -215,6 +227,10 @@ int main(int argc, const char *argv[])
             if (csv && std::fclose(csv) != 0) throw std::runtime_error("cannot write " + outputPath + "consistency.csv");
         }
         if (!outputPath.empty()) extendedKalmanFilter.writeMapPly(outputPath + "map.ply");
+        if (!saveMapFile.empty()) {
+            extendedKalmanFilter.saveMap(saveMapFile);
+            std::printf("saved map: %d features to %s\n", ekf_num_features(extendedKalmanFilter.engine()), saveMapFile.c_str());
+        }
     } catch (const std::exception &ex) {
         std::fprintf(stderr, "ekf_sequence: %s\n", ex.what());
         return 1;

@@ -1,6 +1,6 @@
 // engine.cpp -- C ABI of the MI355X EKF engine (see include/ekf_engine.h).  Host orchestration only: every
 // number is produced by the HIP kernels in kernels_*.hip; there is no CPU compute path.
-#include "engine.h"
+#include "engine_host.h"
 #include "map_blob.h"
 #include "../../include/ekf_test_hooks.h"
 
@@ -8,9 +8,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -19,22 +17,6 @@
 #include <rccl/rccl.h> // types only: the library is loaded at run time (rccl_api)
 
 using namespace ekf;
-
-namespace ekf {
-void launch_partition(EkfEngine *e, const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, EkfMatch *dst0,
-                      int *cnt1, bool map_update = false, const uint8_t *d_kdesc = nullptr, int *d_idx0 = nullptr,
-                      int publish_seq = 0, bool rescue = false, const int *d_M = nullptr, bool behind_ransac = false);
-void launch_outlier_idx(EkfEngine *e, const EkfMatch *src, int M, int *idx);
-} // namespace ekf
-
-#define HIPCHK(call)                                                                                          \
-    do {                                                                                                      \
-        hipError_t _st = (call);                                                                              \
-        if (_st != hipSuccess) {                                                                              \
-            e->err = std::string(#call) + ": " + hipGetErrorString(_st);                                      \
-            return EKF_ERR_HIP;                                                                               \
-        }                                                                                                     \
-    } while (0)
 
 // RCCL entry points used by the sharded engine, resolved from librccl.so.1 on first use (the same library
 // torch.distributed's "nccl" backend has loaded, when the host is PyTorch)
@@ -92,13 +74,6 @@ static int alloc_failed(EkfEngine *e, hipError_t st, const char *what)
     e->err = std::string(what) + ": " + hipGetErrorString(st);
     return EKF_ERR_HIP;
 }
-
-static int exchange_rows(EkfEngine *e, int what, void *base, size_t row_bytes, const std::vector<int32_t> &rb, const char *name);
-
-// element size of H P and of its gathered rows (fp64 beside the exact downdate, else the covariance's)
-static inline size_t hp_elem_bytes(const EkfEngine *e) { return e->exact ? 8 : (e->f32 ? 4 : 8); }
-
-extern "C" {
 
 int ekf_abi_version(void) { return 1; }
 
@@ -352,7 +327,7 @@ static int create_impl(const EkfEngineConfig *cfg, int rank, int world, EkfEngin
     for (auto &ev : e->ev)
         if ((st = hipEventCreate(&ev)) != hipSuccess) return fail(st, "hipEventCreate");
     e->h_counts.assign(CNT_COUNT, 0);
-    {   // host mirror of the counter block (optional: without it read_counts falls back to memcpy + synchronise)
+    {   // host mirror of the counter block (optional: without it read_counts (step.cpp) falls back to memcpy + synchronise)
         void *hp = nullptr;
         if (hipHostMalloc(&hp, 64 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
             std::memset(hp, 0, 64 * sizeof(int));
@@ -428,7 +403,7 @@ int ekf_comm_init(EkfEngine *e, const uint8_t id[EKF_COMM_ID_BYTES])
 // Completes a replicated per-feature table: rank r owns rows [rb[r], rb[r+1]) of row_bytes each and has just written
 // them (on the engine's stream).  In-engine transport: every pair of ranks exchanges its blocks directly, enqueued on the
 // same stream; otherwise the host's callback (which needs the stream idle).
-static int exchange_rows(EkfEngine *e, int what, void *base, size_t row_bytes, const std::vector<int32_t> &rb, const char *name)
+int ekf::exchange_rows(EkfEngine *e, int what, void *base, size_t row_bytes, const std::vector<int32_t> &rb, const char *name)
 {
     const int world = e->shard_world, me = e->shard_rank;
     if (what == EKF_XCHG_BPLANES) e->xchg_bytes_planes += (long long)((size_t)(rb[world] - rb[0] - (rb[me + 1] - rb[me])) * row_bytes);
@@ -543,8 +518,6 @@ int ekf_state_dim(const EkfEngine *e) { return e ? e->n : 0; }
 int ekf_descriptor_bytes(const EkfEngine *e) { return e ? e->desc_bytes : 0; }
 int ekf_get_precision(const EkfEngine *e) { return e ? e->cfg.precision : -1; }
 int ekf_num_features(const EkfEngine *e) { return e ? e->N : 0; }
-
-static int finish_update(EkfEngine *e);
 
 // With ekf_set_async_errors a step does not read the error flag of its last update back; the flag is sticky on the
 // device and is reported (and cleared) by the next step, by ekf_synchronize or by ekf_get_state, whichever comes first.
@@ -924,7 +897,6 @@ int ekf_load_map(EkfEngine *e, const void *blob_, size_t bytes, EkfMapBlobInfo *
 
 
 // ------------------------------------------------------------------------------------------ map management
-static int check_async(EkfEngine *e);
 static int dims_of(int type) { return type == EKF_FEATURE_INVERSE_DEPTH ? 6 : 3; }
 
 int ekf_reset(EkfEngine *e)
@@ -1292,62 +1264,7 @@ int ekf_convert_all_inverse_depth_to_depth(EkfEngine *e, int32_t *converted_idx,
     return check_async(e);
 }
 
-// ----------------------------------------------------------------------------------------------- utilities
-// The device counter block is mirrored into a page of host memory the GPU can write (hipHostMallocMapped, coherent):
-// a one-wavefront kernel copies the 16 ints and then a sequence number, the host polls the sequence number.  The
-// per-frame control flow needs ~6 of these round trips (how many predictions / matches / inliers / rescued decide the
-// next launches); a memcpy + stream synchronise costs ~20 us each, the poll a few.
-constexpr int POLL_SECONDS = 20; // bound of a host poll in wall time (not in iterations: their rate depends on the host); then the plain path
-
-static int read_counts(EkfEngine *e)
-{
-    if (e->h_mirror) {
-        const int seq = ++e->mirror_seq;
-        launch_publish_counts(e, e->d_mirror, seq);
-        volatile int *m = e->h_mirror;
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(POLL_SECONDS);
-        for (long spin = 0;; ++spin) {
-            if (m[CNT_COUNT] == seq) {
-                std::atomic_thread_fence(std::memory_order_acquire);
-                for (int i = 0; i < CNT_COUNT; ++i) e->h_counts[i] = m[i];
-                return EKF_OK;
-            }
-            if ((spin & 0xfffff) == 0xfffff) { // every ~1e6 polls: the stream drained without the write, or the time bound: fall back
-                if (hipStreamQuery(e->stream) == hipSuccess && m[CNT_COUNT] != seq) break;
-                if (std::chrono::steady_clock::now() > t_end) break;
-            }
-        }
-    }
-    HIPCHK(hipMemcpyAsync(e->h_counts.data(), e->d.counts, CNT_COUNT * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return EKF_OK;
-}
-
-// read_counts for a stage whose last kernel published the counter block itself (publish_counts_block, sequence number
-// taken with next_publish_seq before that launch): poll only
-static int next_publish_seq(EkfEngine *e) { return e->h_mirror ? ++e->mirror_seq : 0; }
-
-static int wait_counts(EkfEngine *e, int seq)
-{
-    if (seq <= 0) return read_counts(e);
-    volatile int *m = e->h_mirror;
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(POLL_SECONDS);
-    for (long spin = 0;; ++spin) {
-        if (m[CNT_COUNT] == seq) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            for (int i = 0; i < CNT_COUNT; ++i) e->h_counts[i] = m[i];
-            return EKF_OK;
-        }
-        if ((spin & 0xfffff) == 0xfffff &&
-            ((hipStreamQuery(e->stream) == hipSuccess && m[CNT_COUNT] != seq) || std::chrono::steady_clock::now() > t_end)) break;
-#if defined(__x86_64__)
-        __builtin_ia32_pause(); // the caller's thread polls one cache line; leave the core's other thread its issue slots
-#endif
-    }
-    return read_counts(e); // the stream drained without the write (or the poll gave up): the plain path
-}
-
-static int check_async(EkfEngine *e)
+int ekf::check_async(EkfEngine *e)
 {
     HIPCHK(hipGetLastError());
     return EKF_OK;
@@ -1426,132 +1343,6 @@ int ekf_predict_camera_ahead(const EkfEngine *ce, double tau, double x13[13], do
     return EKF_OK;
 }
 
-// Sharded filter: the FULL exchange of the H.P table (2N x ldP: 192 MB at N = 2000, 1.2 GB at N = 5000 in fp32) and of its
-// fp64 camera columns -- what rounds 1-2 did after every prediction.  EKF::step no longer needs it (see `lean` below); the
-// stateless stage calls of the ABI (ekf_ransac / ekf_update / ... on a caller-ordered match list) still do.
-static int complete_hp_table(EkfEngine *e)
-{
-    if (e->shard_world <= 1 || e->hp_complete) return EKF_OK;
-    int rc;
-    std::vector<int32_t> rb(e->shard_world + 1);
-    for (int r = 0; r <= e->shard_world; ++r) rb[r] = 2 * e->shard_feat_begin[r];
-    if ((rc = exchange_rows(e, EKF_XCHG_HP, e->d.HP, (size_t)e->ldP * hp_elem_bytes(e), rb, "the H.P row blocks"))) return rc;
-    if (e->f32 && !e->exact && (rc = exchange_rows(e, EKF_XCHG_HPC, e->d.HPc, 16 * sizeof(double), rb, "the fp64 camera columns of H.P"))) return rc;
-    e->hp_complete = true;
-    return EKF_OK;
-}
-
-// device-side core of predictCameraMeasurements; leaves the count in h_counts.
-// lean (sharded EKF::step): only the 2x2 innovation blocks S_i travel after a prediction (32 bytes per feature; every rank
-// gates and matches all predictions).  The H.P rows stay with their owners until somebody consumes them: the rows of a
-// RANSAC batch's hypotheses (ransac_dev) and the rows of the matches an update selects (the gather stage of a lean update) -- 2M of
-// the 2N rows, and for the outlier re-prediction nothing but the S_i (missing 2a / EKF.cpp:473).
-// budget > 0 (a step's full prediction with the measurement budget active): the predicted features are scored and
-// ranked before the H P pass and the `budget` most informative go on; what describes the whole prediction -- the kept step
-// predictions and the gate snapshot -- is taken from all of them first, with the S_i the selector formed.
-static int predict_measurements_dev(EkfEngine *e, const int *d_idx, int count, int *n_out, bool count_predicted = false,
-                                    bool lean = false, int budget = 0)
-{
-    launch_predict_features(e, d_idx, d_idx ? count : e->N, false);
-    const bool slots = lean && !d_idx && e->shard_world > 1; // sharded step: where each rank's run of the predicted list starts (matching by owner)
-    if (slots) launch_shard_bounds_idx(e, e->d.plist, e->d.counts + CNT_NPRED);
-    int rc = read_counts(e);
-    if (rc) return rc;
-    int np = e->h_counts[d_idx ? CNT_NPRED_SUB : CNT_NPRED];
-    const bool budgeted = budget > 0 && !d_idx;
-    if (budgeted) {
-        const int np_all = np;
-        launch_budget_select(e, np_all, budget);
-        if (e->keep_step_preds) {
-            launch_pack_predictions(e, e->d.plist, np_all, e->d.step_preds);
-            e->n_step_preds = np_all;
-        }
-        if (e->img.valid) {
-            launch_gate_snapshot(e, np_all);
-            e->n_gates = np_all;
-        }
-        if (np_all > 0) launch_compact(e, e->d.bud_flag, e->d.bud_all, np_all, e->d.plist, e->d.counts + CNT_NPRED);
-        np = std::min(np_all, budget);
-        e->bud_recs_n = e->bud_predicted = np_all;
-        e->bud_selected = np;
-    }
-    if (slots) {
-        e->slot_rb.assign(e->shard_world + 1, 0);
-        for (int r = 0; r <= e->shard_world; ++r) e->slot_rb[r] = e->h_counts[CNT_SHARD0 + r];
-    } else if (!d_idx) e->slot_rb.clear();
-    // (the whole map, all of its predictions: the matcher's gates ride along)
-    launch_hp_rows(e, d_idx ? e->d.plist_sub : e->d.plist, np, count_predicted, nullptr, false, !d_idx && !budgeted);
-    if (!d_idx) e->n_pred = np;
-    *n_out = np;
-    if (e->shard_world > 1 && np > 0) {
-        // every rank wrote the H.P rows and S_i of the features it owns
-        e->hp_complete = false;
-        if (!lean && (rc = complete_hp_table(e))) return rc;
-        std::vector<int32_t> rb(e->shard_world + 1);
-        for (int r = 0; r <= e->shard_world; ++r) rb[r] = e->shard_feat_begin[r];
-        if ((rc = exchange_rows(e, EKF_XCHG_PRED_S, e->d.pred_S, 4 * sizeof(double), rb, "the innovation covariance blocks"))) return rc;
-    }
-    if (!d_idx && !budgeted && e->keep_step_preds) { // EKF.cpp:294-305 draws the step's predictions as they were BEFORE the updates
-        launch_pack_predictions(e, e->d.plist, np, e->d.step_preds);
-        e->n_step_preds = np;
-    }
-    if (!d_idx && !budgeted && e->img.valid) { // image mode: keep the gates of this prediction for detectNewImageFeatures' mask
-        launch_gate_snapshot(e, np);
-        e->n_gates = np;
-    }
-    return check_async(e);
-}
-
-static int download_predictions(EkfEngine *e, const int *d_list, int np, EkfPrediction *preds, double *Hs, double *Hf)
-{
-    if (np <= 0) return EKF_OK;
-    const int N = e->N;
-    std::vector<int> list(np);
-    std::vector<double> uv(2 * (size_t)N), S(4 * (size_t)N), hs(14 * (size_t)N), hf(12 * (size_t)N);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(list.data(), d_list, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(uv.data(), e->d.pred_uv, uv.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(S.data(), e->d.pred_S, S.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hs.data(), e->d.Hs, hs.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hf.data(), e->d.Hf, hf.size() * 8, hipMemcpyDeviceToHost));
-    for (int k = 0; k < np; ++k) {
-        const int fi = list[k];
-        if (preds) {
-            preds[k].featureIndex = fi;
-            preds[k]._pad = 0;
-            preds[k].imagePos[0] = uv[2 * fi];
-            preds[k].imagePos[1] = uv[2 * fi + 1];
-            for (int i = 0; i < 4; ++i) preds[k].covarianceMatrix[i] = S[4 * fi + i];
-        }
-        if (Hs)
-            for (int r = 0; r < 2; ++r)
-                for (int c = 0; c < 13; ++c) Hs[(size_t)26 * k + r * 13 + c] = c < 7 ? hs[14 * fi + r * 7 + c] : 0.0;
-        if (Hf)
-            for (int i = 0; i < 12; ++i) Hf[(size_t)12 * k + i] = hf[12 * fi + i];
-    }
-    return EKF_OK;
-}
-
-int ekf_predict_measurements(EkfEngine *e, const int32_t *feat_idx, int count, EkfPrediction *preds, int *n_preds,
-                             double *Hs, double *Hf)
-{
-    if (!e) return EKF_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    const bool sub = feat_idx && count > 0;
-    if (sub) {
-        if (count > e->cap) return EKF_ERR_CAPACITY;
-        for (int i = 0; i < count; ++i)
-            if (feat_idx[i] < 0 || feat_idx[i] >= e->N) return EKF_ERR_INVALID_ARG;
-        HIPCHK(hipMemcpyAsync(e->d.work_idx, feat_idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    }
-    int np = 0;
-    int rc = predict_measurements_dev(e, sub ? e->d.work_idx : nullptr, count, &np);
-    if (rc) return rc;
-    if (n_preds) *n_preds = np;
-    if (preds || Hs || Hf) return download_predictions(e, sub ? e->d.plist_sub : e->d.plist, np, preds, Hs, Hf);
-    return EKF_OK;
-}
-
 int ekf_predict_measurement_state(EkfEngine *e, EkfPrediction *preds, int *n_preds)
 {
     if (!e || !preds || !n_preds) return EKF_ERR_INVALID_ARG;
@@ -1565,261 +1356,6 @@ int ekf_predict_measurement_state(EkfEngine *e, EkfPrediction *preds, int *n_pre
     return EKF_OK;
 }
 
-static int upload_keypoints(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_kp)
-{
-    if (n_kp > e->kcap) return EKF_ERR_CAPACITY;
-    if (n_kp > 0) {
-        HIPCHK(hipMemcpyAsync(e->d.kps, kps, (size_t)n_kp * sizeof(EkfKeypoint), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(e->d.kdesc, desc32, (size_t)n_kp * e->desc_bytes, hipMemcpyHostToDevice, e->stream));
-    }
-    e->n_kp = n_kp;
-    return EKF_OK;
-}
-
-// d_nkp != nullptr: keypoints detected on the device, n_kp is their capacity and the count is read by the kernel
-static int match_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, int *n_matches,
-                     const int *d_nkp = nullptr)
-{
-    launch_match(e, d_kps, d_desc, e->n_pred, n_kp, nullptr, false, d_nkp);
-    int rc = read_counts(e);
-    if (rc) return rc;
-    *n_matches = e->h_counts[CNT_NMATCH];
-    return check_async(e);
-}
-
-// Sharded EKF::step ("Matching: features/ellipses independent => shard by feature; image replicated; all-gather match
-// lists"): every rank gates and matches the predictions of the features it OWNS -- one run of slots of the feature-ordered
-// predicted list (slot_rb, predict_measurements_dev) -- with either matcher, the per-slot tables (valid flag, keypoint index or
-// matched pixel, distance) are all-gathered, and every rank compacts the same tables into the same match list
-// (Matching.cpp:217-262 divided by the ranks; the list is identical to the unsharded one, which the tests assert).
-static int match_sharded_dev(EkfEngine *e, bool use_ncc, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, int *n_matches)
-{
-    const int W = e->shard_world, me = e->shard_rank, np = e->n_pred;
-    if ((int)e->slot_rb.size() != W + 1 || e->slot_rb[0] != 0 || e->slot_rb[W] != np) {
-        e->err = "sharded matching: the predicted list is not in feature order";
-        return EKF_ERR_INVALID_ARG;
-    }
-    if (use_ncc && !e->img.valid) {
-        e->err = "NCC matcher: no image uploaded";
-        return EKF_ERR_INVALID_ARG;
-    }
-    int rc = EKF_OK;
-    if (np > 0) {
-        if (use_ncc) launch_match_ncc_slots(e, e->slot_rb[me], e->slot_rb[me + 1], e->subpix_on);
-        else launch_match_slots(e, d_kps, d_desc, n_kp, e->slot_rb[me], e->slot_rb[me + 1]);
-        rc = exchange_rows(e, EKF_XCHG_MATCH_VALID, e->d.mt_valid, sizeof(int), e->slot_rb, "the match flags");
-        if (!rc) rc = use_ncc ? exchange_rows(e, EKF_XCHG_MATCH_XY, e->d.mt_xy, sizeof(EkfKeypoint), e->slot_rb, "the matched pixels")
-                              : exchange_rows(e, EKF_XCHG_MATCH_KP, e->d.mt_kp, sizeof(int), e->slot_rb, "the matched keypoint indices");
-        if (!rc) rc = exchange_rows(e, EKF_XCHG_MATCH_DIST, e->d.mt_dist, sizeof(float), e->slot_rb, "the match distances");
-    }
-    if (!rc) {
-        if (use_ncc) {
-            if (np > 0) launch_match_compact_slots(e, np, e->d.mt_xy);
-            else HIPCHK(hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream));
-        } else launch_match_compact(e, d_kps, np);
-    }
-    if (rc) return rc;
-    if ((rc = read_counts(e))) return rc;
-    *n_matches = e->h_counts[CNT_NMATCH];
-    return check_async(e);
-}
-
-int ekf_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_kp, EkfMatch *matches,
-              int *n_matches)
-{
-    if (!e || n_kp < 0 || (n_kp > 0 && (!kps || !desc32))) return EKF_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    int rc = upload_keypoints(e, kps, desc32, n_kp);
-    if (rc) return rc;
-    int M = 0;
-    rc = match_dev(e, e->d.kps, e->d.kdesc, n_kp, &M);
-    if (rc) return rc;
-    if (n_matches) *n_matches = M;
-    if (matches && M > 0) HIPCHK(hipMemcpy(matches, e->d.matches, (size_t)M * sizeof(EkfMatch), hipMemcpyDeviceToHost));
-    return EKF_OK;
-}
-
-// RANSAC over e->d.matches[0..M); on return best_flags holds the inlier mask, h_counts the loop state.
-// lean (sharded EKF::step, feature-ordered match list): the hypotheses are divided by feature ownership, see below.
-static int ransac_dev(EkfEngine *e, int M, bool lean = false)
-{
-    launch_ransac_init(e, M);
-    launch_match_index(e, M);
-    const int batch = e->cfg.ransac_batch;
-    const int W = e->shard_world, me = e->shard_rank;
-    // Sharded EKF::step ("RANSAC: hypotheses are independent => shard hypotheses across GPUs, all-gather the support
-    // counts"): hypothesis h uses the H.P rows of ITS feature as gain columns, and those rows are with the feature's owner -- so every
-    // rank evaluates the hypotheses of the features it owns (one run [mb[me], mb[me + 1]) of the feature-ordered match list: no row of
-    // H.P travels) and the ranks all-gather a batch's support counts (4 bytes per hypothesis) and inlier masks (M bytes per
-    // hypothesis) before the sequential bookkeeping, which every rank then replays identically (1PointRansac.cpp:125-180).
-    const bool by_owner = lean && W > 1 && !e->hp_complete;
-    std::vector<int32_t> mb, rb;
-    if (by_owner) {
-        launch_shard_bounds(e, e->d.matches, M);
-        int rc = read_counts(e);
-        if (rc) return rc;
-        mb.assign(W + 1, 0);
-        for (int r = 0; r <= W; ++r) mb[r] = e->h_counts[CNT_SHARD0 + r];
-        if (mb[0] != 0 || mb[W] != M) {
-            e->err = "sharded RANSAC: the match list is not in feature order";
-            return EKF_ERR_INVALID_ARG;
-        }
-        rb.assign(W + 1, 0);
-    }
-    for (int h0 = 0, nb = batch; h0 < M; h0 += nb, nb = batch * RANSAC_WIDE_FACTOR) {
-        const int batch = nb; // (this batch's width: the first one narrow -- a converged filter ends inside it --, the others wide)
-        if (by_owner) {
-            const int h1 = std::min(M, h0 + batch);
-            launch_ransac_hyp(e, M, h0, batch, nullptr, mb[me], mb[me + 1]);
-            for (int r = 0; r <= W; ++r) rb[r] = std::min(std::max(mb[r], h0), h1) - h0; // rows of the batch's tables by owner
-            int rc;
-            if ((rc = exchange_rows(e, EKF_XCHG_HYP_COUNT, e->d.hyp_count, sizeof(int), rb, "the support counts of a RANSAC batch"))) return rc;
-            if ((rc = exchange_rows(e, EKF_XCHG_HYP_FLAGS, e->d.hyp_flags, (size_t)e->mcap, rb, "the inlier masks of a RANSAC batch"))) return rc;
-            launch_ransac_select(e, M, h0, batch, nullptr, 0);
-        } else {
-            launch_ransac_batch(e, M, h0, batch);
-        }
-        int rc = read_counts(e);
-        if (rc) return rc;
-        if (e->h_counts[CNT_RS_DONE]) break;
-    }
-    return check_async(e);
-}
-
-// The device code keys predictions, Jacobians and H.P rows by featureIndex: one match per feature (what the matcher
-// produces, Matching.cpp:217-262).  A list with a repeated featureIndex is rejected instead of being half-processed.
-static int validate_matches(const EkfEngine *e, const EkfMatch *m, int M)
-{
-    if (M < 0 || M > e->cap || (M > 0 && !m)) return EKF_ERR_INVALID_ARG;
-    std::vector<uint8_t> seen((size_t)e->N, 0);
-    for (int i = 0; i < M; ++i) {
-        const int f = m[i].featureIndex;
-        if (f < 0 || f >= e->N || seen[f]) return EKF_ERR_INVALID_ARG;
-        seen[f] = 1;
-    }
-    return EKF_OK;
-}
-
-int ekf_ransac(EkfEngine *e, const EkfMatch *matches, int M, uint8_t *inlier_mask, int *n_hypotheses)
-{
-    if (!e || !inlier_mask) return EKF_ERR_INVALID_ARG;
-    int rc = validate_matches(e, matches, M);
-    if (rc) return rc;
-    if (n_hypotheses) *n_hypotheses = 0;
-    if (M == 0) return EKF_OK;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->d.matches, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
-    if ((rc = complete_hp_table(e))) return rc; // a sharded step leaves the H.P table with the owners' rows only
-    rc = ransac_dev(e, M);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(inlier_mask, e->d.best_flags, (size_t)M, hipMemcpyDeviceToHost));
-    if (n_hypotheses) *n_hypotheses = e->h_counts[CNT_RS_NEXT];
-    return EKF_OK;
-}
-
-// update with the matches in e->d.msel[0..M), recorded as `stage` (UpdateCall); lean: a sharded step, whose H.P table holds the
-// owners' rows only -- the gather stage completes the gathered rows by an exchange (kernels_update.hip); early: launch_early_gather
-static int update_dev(EkfEngine *e, int M, int kind, int stage, bool lean = false, const EarlyGather &early = EarlyGather())
-{
-    if (M <= 0) return EKF_OK; // Update.cpp:292
-    lean = lean && e->shard_world > 1 && !e->hp_complete;
-    if (lean) { // where each rank's run of the (feature-ordered) selected matches starts
-        launch_shard_bounds(e, e->d.msel, M);
-        int rc = read_counts(e);
-        if (rc) return rc;
-        e->shard_rb.assign(e->shard_world + 1, 0);
-        for (int r = 0; r <= e->shard_world; ++r) e->shard_rb[r] = 2 * e->h_counts[CNT_SHARD0 + r];
-        if (e->shard_rb[0] != 0 || e->shard_rb[e->shard_world] != 2 * M) {
-            e->err = "sharded update: the match list is not in feature order";
-            return EKF_ERR_INVALID_ARG;
-        }
-    }
-    UpdateCall call;
-    call.matches = e->d.msel; call.M = M; call.kind = kind; call.stage = stage;
-    call.lean = lean; call.early = early;
-    const int rc = launch_update(e, call);
-    return rc ? rc : check_async(e);
-}
-
-// e->h_counts[CNT_ERR] != 0 was read back: the last update enqueued failed and, with everything enqueued behind it, left the filter
-// as it was (filter_frozen, engine.h).  Clears the flag.  A persistent sweep that timed out (another process's kernels on the
-// device, a partition that could not hold the grid: chol_persist.h) is not the caller's problem: the SAME update -- its match list
-// is still in d.msel -- runs again on the launch-per-panel sweep, which has no cross-workgroup waits, from the untouched P
-// (S, nu and the gathered rows are formed again); *status stays EKF_OK when that succeeds and the engine counts the retry.
-// Anything else (S not positive definite) goes to *status: that update is skipped, as the reference skips it (cv::invert
-// returns zeros, K = 0: EKF/Update.cpp:101-108).  Returns a hard error (HIP, exchange) or EKF_OK.  Called right after a read-back,
-// so a step's unread flag (err_unread) has been read and is handled here.
-static int recover_failed_update(EkfEngine *e, int *status)
-{
-    e->err_unread = false;
-    const int code = e->h_counts[CNT_ERR];
-    if (!code) return EKF_OK;
-    HIPCHK(hipMemsetAsync(e->d.counts + CNT_ERR, 0, sizeof(int), e->stream));
-    e->h_counts[CNT_ERR] = 0;
-    e->p_exact_sym = e->last_update.sym; // (the frozen downdate did not symmetrise an uploaded P)
-    if (code == EKF_ERR_TIMEOUT && e->last_update.persist && e->last_update.call.M > 0) {
-        e->ps_backoff_len = std::min(std::max(64, 2 * e->ps_backoff_len), 4096); // see engine.h
-        e->ps_backoff = e->ps_backoff_len;
-        e->ps_ok_streak = 0;
-        // (filter consistency: the retry records the stage of the update it repeats)
-        int rc = launch_update(e, retry_of(e->last_update.call));
-        if (!rc) rc = check_async(e);
-        ++e->sweep_retries;
-        if (rc) return rc;
-        if ((rc = read_counts(e))) return rc;
-        if (!e->h_counts[CNT_ERR]) return EKF_OK;
-        const int code2 = e->h_counts[CNT_ERR]; // the retry's own outcome (it cannot time out)
-        HIPCHK(hipMemsetAsync(e->d.counts + CNT_ERR, 0, sizeof(int), e->stream));
-        e->h_counts[CNT_ERR] = 0;
-        e->p_exact_sym = e->last_update.sym;
-        *status = code2;
-    } else {
-        *status = code;
-    }
-    e->err = *status == EKF_ERR_TIMEOUT ? "the persistent Cholesky sweep timed out"
-             : (*status == EKF_ERR_NON_FINITE ? "a row of B = inv(L) H P does not fit its a-priori column scale (covariance not positive semi-definite, or not finite)"
-                                              : "S = H P H' + R is not positive definite");
-    return EKF_OK;
-}
-
-static int finish_update(EkfEngine *e)
-{
-    int rc = read_counts(e);
-    if (rc) return rc;
-    int status = EKF_OK;
-    if ((rc = recover_failed_update(e, &status))) return rc;
-    return status;
-}
-
-int ekf_update(EkfEngine *e, const EkfMatch *matches, int M)
-{
-    if (!e) return EKF_ERR_INVALID_ARG;
-    int rc = validate_matches(e, matches, M);
-    if (rc) return rc;
-    if (M == 0) return EKF_OK;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
-    if ((rc = complete_hp_table(e))) return rc;
-    if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
-    rc = update_dev(e, M, UPDATE_COV, 0);
-    if (rc) return rc;
-    return finish_update(e);
-}
-
-int ekf_update_only_state(EkfEngine *e, const EkfMatch *matches, int M)
-{
-    if (!e) return EKF_ERR_INVALID_ARG;
-    int rc = validate_matches(e, matches, M);
-    if (rc) return rc;
-    if (M == 0) return EKF_OK;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
-    if ((rc = complete_hp_table(e))) return rc;
-    rc = update_dev(e, M, UPDATE_STATE_ONLY, 0);
-    if (rc) return rc;
-    return finish_update(e);
-}
-
 // ------------------------------------------------------------------------------ fixed map
 // why the fixed-map update is not available on this engine, or null
 static const char *fixed_map_refusal(const EkfEngine *e)
@@ -1831,7 +1367,7 @@ static const char *fixed_map_refusal(const EkfEngine *e)
 
 // the mode's scratch, on its first use: the control block and the two m x 13 gain tables of updates above B_SWEEP_MAX rows (the
 // partial sums of the strip share d.cam_part with the fast fp32 configuration's repair, which the mode refuses)
-static int fixed_map_scratch(EkfEngine *e)
+int ekf::fixed_map_scratch(EkfEngine *e)
 {
     if (e->d.fm_ctl) return EKF_OK;
     HIPCHK(hipSetDevice(e->device));
@@ -1850,16 +1386,7 @@ int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M)
         e->err = std::string("ekf_update_fixed_map: ") + why;
         return EKF_ERR_INVALID_ARG;
     }
-    int rc = validate_matches(e, matches, M);
-    if (rc) return rc;
-    if (M == 0) return EKF_OK;
-    if ((rc = fixed_map_scratch(e))) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
-    if (e->consistency) ++e->cons_epoch; // the records of this call: DESIGN.md 4.11
-    rc = update_dev(e, M, UPDATE_FIXED_MAP, 0);
-    if (rc) return rc;
-    return finish_update(e);
+    return update_stage(e, matches, M, UPDATE_FIXED_MAP);
 }
 
 int ekf_set_fixed_map(EkfEngine *e, int on)
@@ -2047,273 +1574,6 @@ int ekf_rescue(EkfEngine *e, const EkfMatch *outliers, int M, uint8_t *rescued_m
     return check_async(e);
 }
 
-// ------------------------------------------------------------------------------------------------------ step
-static void harvest_pu_events(EkfEngine *e)
-{
-    for (auto &pr : e->px_events) { // exact downdate: the column-scale + digit-plane kernels (their end event is the downdate's start event, destroyed below)
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) e->slice_ms += ms;
-        (void)hipEventDestroy(pr.first);
-    }
-    e->px_events.clear();
-    for (const PuBracket &b : e->pu_events) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, b.first, b.second) == hipSuccess) {
-            e->times.p_update_kernel_ms += ms;
-            e->times.p_update_launches += 1;
-            e->times.p_update_flops += b.work;
-            e->times.p_update_bytes += 2.0 * (double)e->n * (double)e->n * (e->f32 ? 4.0 : 8.0);
-            e->pu_log.emplace_back(b.m, ms);
-        }
-        (void)hipEventDestroy(b.first);
-        (void)hipEventDestroy(b.second);
-    }
-    e->pu_events.clear();
-    for (const SweepBracket &b : e->sw_events) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, b.first, b.second) == hipSuccess) {
-            const double m = std::abs(b.m);
-            e->sweep_ms += ms;
-            e->sweep_panels += ((long long)m + NB - 1) / NB;
-            e->sweep_launches += b.launches;
-            e->sweep_updates += 1;
-            e->sweep_flops_f64 += m * m * m / 3.0;                  // Cholesky of S
-            if (b.m > 0) e->sweep_flops_b += m * m * (double)e->n;  // B = inv(L) (H P): forward substitution, m^2 n
-        }
-        (void)hipEventDestroy(b.first);
-        (void)hipEventDestroy(b.second);
-    }
-    e->sw_events.clear();
-}
-
-struct StageTimer {
-    EkfEngine *e;
-    std::vector<hipEvent_t> evs;
-    explicit StageTimer(EkfEngine *eng) : e(eng) {}
-    ~StageTimer() // early returns of step_dev skip finish(): the events recorded so far are released here
-    {
-        for (auto ev : evs) (void)hipEventDestroy(ev);
-    }
-    void mark()
-    {
-        if (!e->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, e->stream);
-        evs.push_back(ev);
-    }
-    void finish()
-    {
-        if (!e->timing || evs.size() < 7) return;
-        (void)hipStreamSynchronize(e->stream);
-        double *dst[6] = {&e->times.prediction_ms, &e->times.matching_ms, &e->times.ransac_ms,
-                          &e->times.update_li_ms,  &e->times.rescue_ms,   &e->times.update_hi_ms};
-        for (int i = 0; i < 6; ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, evs[i], evs[i + 1]) == hipSuccess) *dst[i] += ms;
-        }
-        for (auto ev : evs) (void)hipEventDestroy(ev);
-        evs.clear();
-        e->times.steps += 1;
-        harvest_pu_events(e);
-    }
-};
-
-static int match_ncc_dev(EkfEngine *e, int *n_matches);
-
-static int detect_step_keypoints(EkfEngine *e);
-
-// EKF::step (EKF.cpp:242-556) with keypoints already on the device.  detect: the keypoints of this frame are detected and
-// described on the device, into d_kps / d_desc (= d.kps / d.kdesc, n_kp = their capacity), between the prediction and the
-// matching (ekf_set_image_matcher(EKF_IMAGE_MATCHER_KEYPOINTS)).
-//
-// Device counts (descriptor matcher on host-detected keypoints, no image loaded, no kept predictions, one GPU): how many
-// features were predicted, how many matches there are and how many outliers were re-predicted only decide launch sizes, so the
-// launches use upper bounds (N, N, the outlier count) and the kernels read the counts on the device.  What the host still needs
-// to know -- the RANSAC result (loop state and inlier count: the size of the first update), the rescued count (the size of the
-// second), the error flag -- comes from three read-backs instead of six (two with ekf_set_async_errors).  A read-back idles the GPU
-// for as long as the host needs to see the counters and enqueue the next launch, a few us; behind the first two the next stage's
-// first launch is therefore enqueued BEFORE the poll, sized by an upper bound and reading its count on the device: the
-// low-innovation partition behind the first RANSAC batch (28.2 against 36.0 us per frame in ransac_ms) and the second update's
-// gather / assembly behind the rescue partition (2-3 us per frame).  What follows them -- the sweeps, whose grid
-// layout the host decides from the size -- still waits.
-// Every other step reads the counts back after each stage, because the host sizes or records launches by them:
-// with an image loaded the prediction's gates are snapshotted for the detectors (n_gates), kept predictions are packed for
-// ekf_get_step_predictions, the NCC matcher is launched per prediction, and a sharded engine divides predictions, matches and
-// updates between the ranks by owner.
-static int step_dev(EkfEngine *e, const EkfKeypoint *d_kps, const uint8_t *d_desc, int n_kp, EkfStepInfo *info,
-                    bool use_ncc = false, bool detect = false)
-{
-    const bool budget_active = e->budget_K > 0 && e->budget_K < e->N; // measurement budget: with K >= N it cannot bind
-    const bool dev_counts = !use_ncc && !detect && !e->img.valid && !e->keep_step_preds && e->shard_world == 1 && !budget_active;
-    const bool lean = e->shard_world > 1; // sharded: rows of H.P travel when consumed, not after every prediction
-    const int step_kind = e->fixed_map ? UPDATE_FIXED_MAP : UPDATE_COV; // ekf_set_fixed_map: both updates move the camera alone
-    int *cnt = e->d.counts;
-    EkfStepInfo li;
-    std::memset(&li, 0, sizeof(li));
-    int status = EKF_OK, rc;
-    const int retries0 = e->sweep_retries;
-    // A failed update is seen at the next read-back; until then everything enqueued behind it has left the filter alone
-    // (filter_frozen, engine.h).  The previous step's last update can still be unread (err_unread, ekf_set_async_errors): a
-    // device-count step sees it at its first read-back, after its own prediction ran frozen, and starts again (below); a
-    // host-count step reads it before it launches anything.  Either way that update runs again or is skipped and reported here.
-    if (!dev_counts && e->err_unread) {
-        if ((rc = read_counts(e))) return rc;
-        if ((rc = recover_failed_update(e, &status))) return rc;
-    }
-    bool restarted = false;
-    bool partitioned = false; // the low-innovation partition has run (see the RANSAC stage)
-restart:
-    if (e->consistency) ++e->cons_epoch; // filter consistency: the records of this step
-    StageTimer tm(e);
-    tm.mark();
-    // 1-2. prediction (:273-284), timesPredicted++ (EKF.cpp:572)
-    int np = 0;
-    if (dev_counts) { // covariance strips and pixel predictions in one launch; with more than 256 features the compaction of
-                      // the predicted list rides in the launch of the H P rows
-        const bool deferred = launch_predict_with_features(e, e->N, e->step_dt);
-        launch_hp_rows(e, e->d.plist, e->N, true, cnt + CNT_NPRED, deferred, true); // + the matcher's gates
-    } else {
-        launch_predict(e, e->step_dt);
-        if ((rc = predict_measurements_dev(e, nullptr, e->N, &np, true, lean, budget_active ? e->budget_K : 0))) return rc;
-    }
-    tm.mark();
-    // 4. matching (:337); keypoints from images: detector + descriptor inside the gates of this prediction (Matching.cpp:188-210)
-    int M = 0;
-    if (dev_counts) {
-        launch_match(e, d_kps, d_desc, e->N, n_kp, cnt + CNT_NPRED, true); // + the RANSAC loop state and the feature -> match index
-    } else {
-        if (detect && (rc = detect_step_keypoints(e))) return rc;
-        if (lean) rc = match_sharded_dev(e, use_ncc, d_kps, d_desc, n_kp, &M); // every rank matches the predictions of its own features
-        else rc = use_ncc ? match_ncc_dev(e, &M) : match_dev(e, d_kps, d_desc, n_kp, &M, detect ? cnt + CNT_KP_FOUND : nullptr);
-        if (rc) return rc;
-    }
-    tm.mark();
-    // 6. 1-point RANSAC (:402); predictions/Jacobians are looked up by featureIndex (:368-392)
-    if (dev_counts) { // the first batch is launched before anything is known on the host
-        const int batch = e->cfg.ransac_batch;
-        const int seq_r = next_publish_seq(e);
-        launch_ransac_batch(e, e->N, 0, batch, cnt + CNT_NMATCH, seq_r);
-        // The partition behind the loop is enqueued before the host polls for the batch's outcome, so the GPU does not wait for the
-        // host between the two: sized by N, it reads the match count on the device and does nothing unless this batch ended the loop
-        // and the filter is not frozen (k_partition: behind_ransac) -- the restart below sees no side effect.
-        const bool early = e->N > 0;
-        if (early)
-            launch_partition(e, e->d.matches, e->N, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx, 0, false,
-                             cnt + CNT_NMATCH, true);
-        if ((rc = wait_counts(e, seq_r))) return rc;
-        if (e->h_counts[CNT_ERR] && !restarted) {
-            // the previous step's last update failed and its final read-back was skipped: this step's prediction did not touch
-            // the filter -- recover (that update again, or skipped and reported here), then this step from its start
-            if ((rc = recover_failed_update(e, &status))) return rc;
-            restarted = true;
-            goto restart;
-        }
-        np = e->n_pred = e->h_counts[CNT_NPRED];
-        M = e->h_counts[CNT_NMATCH];
-        partitioned = early && e->h_counts[CNT_RS_DONE] && !e->h_counts[CNT_ERR]; // what the early launch saw (same counter block)
-        for (int h0 = batch, nb = batch * RANSAC_WIDE_FACTOR; !e->h_counts[CNT_RS_DONE] && h0 < M; h0 += nb) {
-            launch_ransac_batch(e, M, h0, nb); // (wide batches behind the first: see ransac_dev)
-            if ((rc = read_counts(e))) return rc;
-        }
-    } else if (M > 0 && (rc = ransac_dev(e, M, lean))) {
-        return rc;
-    }
-    li.n_predicted = np;
-    li.n_matches = M;
-    if (!budget_active) { // measurement budget counts of a step it did not bind in
-        e->bud_recs_n = 0;
-        e->bud_predicted = e->bud_selected = np;
-    }
-    int ni = 0, no = 0;
-    if (M > 0) {
-        li.n_hypotheses = e->h_counts[CNT_RS_NEXT];
-        ni = e->h_counts[CNT_RS_BEST];
-        no = M - ni;
-        // + updateMapFeatures for the low-innovation inliers (MapManagement.cpp:88-113), same launch
-        // (device-count step whose first batch ended the loop: the launch enqueued behind that batch has done this)
-        if (!partitioned) launch_partition(e, e->d.matches, M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, true, d_desc, e->d.work_idx);
-    }
-    // patch normals: the estimator runs behind the frame's last update on the inliers and the rescued; d.msel is
-    // overwritten by the rescue, so each list is copied behind its partition
-    const bool normals = use_ncc && e->pn_on;
-    if (normals && ni > 0)
-        HIPCHK(hipMemcpyAsync(e->d.pn_list, e->d.msel, (size_t)ni * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
-    li.n_inliers = ni;
-    li.n_outliers = no;
-    tm.mark();
-    // 7. low-innovation update (:430)
-    if ((rc = update_dev(e, ni, step_kind, 1, lean))) return rc;
-    tm.mark();
-    // 8-9. re-predict the outliers with the updated state / covariance, rescue (:473-506): rescued matches join the inliers
-    // (EKF.cpp:552-556).  An outlier that is not re-predicted has pred_vis = 0 and is not rescued.
-    int nr = 0;
-    EarlyGather early; // the second update's gather / assembly, where it is already enqueued for the count this stage left on the device
-    if (no > 0) {
-        int nop = 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (dev_counts) {
-                launch_predict_features(e, e->d.work_idx, no, false);
-                launch_hp_rows(e, e->d.plist_sub, no, false, cnt + CNT_NPRED_SUB);
-                const int seq_p = next_publish_seq(e);
-                // rescueOutliers (EKF.cpp:84-97) and the partition it feeds in one launch
-                launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc, nullptr, seq_p, true);
-                // The second update's first launch goes behind the partition before the host polls for the rescued count, so the GPU
-                // does not wait for the host between the two: sized by the outlier count, it reads the rescued count on the device
-                // and writes update scratch only -- nothing at all behind a failed first update, where this stage runs again below.
-                // (Only where the partition publishes the counters itself: a copy of the counter block made behind this launch could show
-                // the error flag of the SECOND update's first diagonal block as if the first update had failed.)
-                early = seq_p > 0 ? launch_early_gather(e, no, cnt + CNT_NRESC, step_kind) : EarlyGather();
-                rc = wait_counts(e, seq_p);
-            } else {
-                rc = predict_measurements_dev(e, e->d.work_idx, no, &nop, false, lean);
-            }
-            if (rc) return rc;
-            if (e->h_counts[CNT_ERR]) early = EarlyGather();
-            if (!e->h_counts[CNT_ERR]) break;
-            // the first update failed (seen at this stage's read-back; everything behind it was frozen, a fused partition did
-            // nothing and the inliers are still in d.msel): run it again or skip it (recover_failed_update), then this stage again
-            if ((rc = recover_failed_update(e, &status))) return rc;
-        }
-        if (dev_counts) {
-            nr = e->h_counts[CNT_NRESC];
-        } else if (nop > 0) {
-            launch_rescue(e, e->d.mout, no);
-            launch_partition(e, e->d.mout, no, e->d.mask, e->d.msel, nullptr, cnt + CNT_NRESC, true, d_desc);
-            if ((rc = read_counts(e))) return rc;
-            nr = e->h_counts[CNT_NRESC];
-        }
-    }
-    li.n_rescued = nr;
-    tm.mark();
-    if (normals && nr > 0)
-        HIPCHK(hipMemcpyAsync(e->d.pn_list + ni, e->d.msel, (size_t)nr * sizeof(EkfMatch), hipMemcpyDeviceToDevice, e->stream));
-    // 10. high-innovation update (:529-532)
-    // (this update's route decides whether the early launch serves it: launch_update)
-    if ((rc = update_dev(e, nr, step_kind, 2, lean, early))) return rc;
-    tm.mark();
-    if (normals) launch_ncc_normal(e, ni + nr); // its two counters travel with the step's last read-back
-    if (dev_counts && e->async_errors) {
-        e->err_unread = true; // reported by the next step, ekf_synchronize or ekf_get_state
-    } else {
-        if ((rc = read_counts(e))) return rc;
-        if (normals) {
-            e->pn_counts[0] = e->h_counts[CNT_PN_UPD];
-            e->pn_counts[1] = e->h_counts[CNT_PN_SKIP];
-        }
-        if (detect) {
-            e->step_kp_detected = e->h_counts[CNT_KP_FOUND];
-            e->step_kp_kept = std::min(e->step_kp_detected, e->kcap);
-        }
-        if ((rc = recover_failed_update(e, &status))) return rc;
-    }
-    tm.finish();
-    li.status = status;
-    li.n_sweep_retries = e->sweep_retries - retries0;
-    if (info) *info = li;
-    return status;
-}
-
 int ekf_set_async_errors(EkfEngine *e, int on)
 {
     if (!e) return EKF_ERR_INVALID_ARG;
@@ -2333,16 +1593,6 @@ int ekf_set_sweep_mode(EkfEngine *e, int mode)
     if (!e || mode < EKF_SWEEP_PAIRS || mode > EKF_SWEEP_LAUNCHES) return EKF_ERR_INVALID_ARG;
     e->sweep_mode = mode;
     return EKF_OK;
-}
-
-int ekf_step(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_kp, EkfStepInfo *info)
-{
-    if (!e || n_kp < 0 || (n_kp > 0 && (!kps || !desc32))) return EKF_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    int rc = upload_keypoints(e, kps, desc32, n_kp);
-    if (rc) return rc;
-    e->step_dt = e->frame_interval;
-    return step_dev(e, e->d.kps, e->d.kdesc, n_kp, info);
 }
 
 int ekf_frames_upload(EkfEngine *e, int n_frames, const int32_t *kp_counts, const EkfKeypoint *kps_concat,
@@ -2382,7 +1632,9 @@ int ekf_step_frame(EkfEngine *e, int frame, EkfStepInfo *info)
     HIPCHK(hipSetDevice(e->device));
     const size_t off = (size_t)e->frames.offset[frame];
     e->step_dt = staged_interval(e, frame);
-    return step_dev(e, e->frames.kps + off, e->frames.desc + off * e->desc_bytes, e->frames.count[frame], info);
+    StepInput in;
+    in.d_kps = e->frames.kps + off; in.d_desc = e->frames.desc + off * e->desc_bytes; in.n_kp = e->frames.count[frame];
+    return run_step(e, in, info);
 }
 
 // ------------------------------------------------------------------------------------- NCC matcher (mode B)
@@ -2621,7 +1873,7 @@ static int ensure_kp_scratch(EkfEngine *e, int det_cap)
 
 // the step's keypoints: masked detection into d.kps (the first kcap in raster order), their descriptors into d.kdesc; the
 // count stays on the device (counts[CNT_KP_FOUND]) for k_match and k_brief -- no read-back
-static int detect_step_keypoints(EkfEngine *e)
+int ekf::detect_step_keypoints(EkfEngine *e)
 {
     if (!e->img.valid) {
         e->err = "keypoint matcher: no image uploaded";
@@ -2636,8 +1888,13 @@ static int detect_step_keypoints(EkfEngine *e)
 
 static int step_image_dev(EkfEngine *e, EkfStepInfo *info)
 {
-    if (e->image_matcher == EKF_IMAGE_MATCHER_KEYPOINTS) return step_dev(e, e->d.kps, e->d.kdesc, e->kcap, info, false, true);
-    return step_dev(e, nullptr, nullptr, 0, info, true);
+    StepInput in;
+    in.source = STEP_NCC;
+    if (e->image_matcher == EKF_IMAGE_MATCHER_KEYPOINTS) {
+        in.source = STEP_DETECT_KEYPOINTS;
+        in.d_kps = e->d.kps; in.d_desc = e->d.kdesc; in.n_kp = e->kcap;
+    }
+    return run_step(e, in, info);
 }
 
 int ekf_set_image_matcher(EkfEngine *e, int matcher, double min_response)
@@ -2747,7 +2004,7 @@ static int ensure_wide_tables(EkfEngine *e, int parts)
     return EKF_OK;
 }
 
-static int match_ncc_dev(EkfEngine *e, int *n_matches)
+int ekf::match_ncc_dev(EkfEngine *e, int *n_matches)
 {
     if (!e->img.valid) {
         e->err = "NCC matcher: no image uploaded";
@@ -2832,8 +2089,7 @@ int ekf_refine_patch_normals(EkfEngine *e, const EkfMatch *matches, int M)
     if (M > 0) HIPCHK(hipMemcpyAsync(e->d.pn_list, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
     launch_ncc_normal(e, M);
     if ((rc = read_counts(e))) return rc; // (synchronises: the caller's list has been read)
-    e->pn_counts[0] = e->h_counts[CNT_PN_UPD];
-    e->pn_counts[1] = e->h_counts[CNT_PN_SKIP];
+    harvest_pn_counts(e);
     return check_async(e);
 }
 
@@ -3412,4 +2668,3 @@ int ekf_timing_p_update_launches(EkfEngine *e, int capacity, int32_t *m_rows, fl
     return EKF_OK;
 }
 
-} // extern "C"

@@ -550,13 +550,47 @@ void launch_camera_ahead(const EkfEngine *e, double tau, double *d_out); // read
 // full (idx == nullptr) or subset prediction; fills tables, compacted list and CNT_NPRED / CNT_NPRED_SUB
 bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool state_only, bool defer_compact = false);
 bool launch_predict_with_features(EkfEngine *e, int count, double dt); // step path: prepare, then covariance strips + all features in one launch
-// d_count != nullptr: n_list is an upper bound, the list's length is read on the device
-void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted = false, const int *d_count = nullptr, bool from_flags = false,
-                    bool gates = false);
-// keypoints kps / kdesc; d_npred != nullptr: n_pred is an upper bound, the number of predictions is read on the device; d_nkp
-// likewise for n_kp
-void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_pred, int n_kp, const int *d_npred = nullptr,
-                  bool with_ransac_init = false, const int *d_nkp = nullptr);
+// the H P rows and S_i of the features in d_list (kernels_predict.hip has the details of from_flags and gates)
+struct HpRowsCall {
+    const int *d_list = nullptr;
+    int n_list = 0;
+    bool count_predicted = false; // timesPredicted++ of the listed features (EKF.cpp:572)
+    const int *d_count = nullptr; // not null: n_list is an upper bound, the list's length is read on the device
+    bool from_flags = false;      // the compaction of the predicted list was left to this launch (launch_predict_*'s return value)
+    bool gates = false;           // also write the descriptor matcher's gates (a full prediction)
+};
+void launch_hp_rows(EkfEngine *e, const HpRowsCall &c);
+// descriptor matching of the predictions in d.plist against the keypoints kps / kdesc
+struct MatchCall {
+    const EkfKeypoint *kps = nullptr;
+    const uint8_t *kdesc = nullptr;
+    int n_pred = 0, n_kp = 0;
+    const int *d_npred = nullptr;  // not null: n_pred is an upper bound, the number of predictions is read on the device
+    const int *d_nkp = nullptr;    // likewise for n_kp (keypoints detected on the device)
+    bool with_ransac_init = false; // the compaction also sets the RANSAC loop state, the feature -> match index and the records
+};
+void launch_match(EkfEngine *e, const MatchCall &c);
+// The two stable partitions of a step (k_partition, kernels_match.hip).  After RANSAC: d.matches by d.best_flags into the inliers
+// (d.msel; timesMatched++ and the map descriptor replaced by the keypoint's, MapManagement.cpp:88-113) and the outliers (d.mout,
+// their features into d.work_idx: the work list of the re-prediction).
+struct RansacPartition {
+    int M = 0;                     // matches
+    const int *d_M = nullptr;      // not null: M is an upper bound for the launch, the kernel reads the count
+    bool behind_ransac = false;    // enqueued behind the first batch of hypotheses, before the host has seen its outcome: does
+                                   // nothing unless that batch ended the loop (k_partition)
+    const uint8_t *d_kdesc = nullptr; // the frame's keypoint descriptors (null: NCC matches have none)
+};
+void launch_ransac_partition(EkfEngine *e, const RansacPartition &c);
+// After the outliers' re-prediction: d.mout by the rescue mask d.mask into d.msel, the count into counts[CNT_NRESC], the same
+// bookkeeping for the rescued.
+struct RescuePartition {
+    int n_outliers = 0;
+    const uint8_t *d_kdesc = nullptr;
+    bool fused_rescue = false; // the launch computes the mask itself (rescueOutliers, EKF.cpp:84-97) instead of reading launch_rescue's
+    int publish_seq = 0;       // > 0: the launch also publishes the counter block under this sequence number (publish_counts_block)
+};
+void launch_rescue_partition(EkfEngine *e, const RescuePartition &c);
+void launch_outlier_idx(EkfEngine *e, const EkfMatch *src, int M, int *idx);
 // d_M != nullptr (RANSAC launchers): M is an upper bound, the number of matches is read on the device
 void launch_match_index(EkfEngine *e, int M, const int *d_M = nullptr);
 // sharded filter: per-rank boundaries of a feature-sorted match list -> counts[CNT_SHARD0 ..]

@@ -195,21 +195,20 @@ k_match_compact(const int *plist, int n_pred, const int *mt_valid, const int *mt
     if (tid == 1023) *out_count = total;
 }
 
-void launch_match(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *kdesc, int n_pred, int n_kp, const int *d_npred,
-                  bool with_ransac_init, const int *d_nkp)
+void launch_match(EkfEngine *e, const MatchCall &c)
 {
-    if (n_pred <= 0) {
+    if (c.n_pred <= 0) {
         (void)hipMemsetAsync(e->d.counts + CNT_NMATCH, 0, sizeof(int), e->stream);
-        if (with_ransac_init) launch_ransac_init(e, e->N);
+        if (c.with_ransac_init) launch_ransac_init(e, e->N);
         return;
     }
-    k_match<<<n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, kps,
-                                           kdesc, n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
-                                           e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, d_npred, 0,
-                                           d_nkp, e->match_gates_valid ? (const Gate *)e->d.match_gates : nullptr);
-    k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
-                                               kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, d_npred,
-                                               with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N,
+    k_match<<<c.n_pred, 256, 0, e->stream>>>(e->d.plist, e->d.pred_uv, e->d.pred_S, e->d.feat_desc, c.kps,
+                                           c.kdesc, c.n_kp, e->cfg.par.matchingCompCoefSecondBestVSFirst,
+                                           e->d.mt_valid, e->d.mt_kp, e->d.mt_dist, e->desc_bytes, e->desc_f32 ? 1 : 0, c.d_npred, 0,
+                                           c.d_nkp, e->match_gates_valid ? (const Gate *)e->d.match_gates : nullptr);
+    k_match_compact<<<1, 1024, 0, e->stream>>>(e->d.plist, c.n_pred, e->d.mt_valid, e->d.mt_kp, e->d.mt_dist,
+                                               c.kps, 0, e->d.matches, e->d.counts + CNT_NMATCH, c.d_npred,
+                                               c.with_ransac_init ? e->d.counts : nullptr, e->d.match_of_feat, e->d.best_flags, e->N,
                                                e->d.ransac_rec, e->d.feat_pos, e->d.feat_type, e->d.feat_covpos);
 }
 
@@ -279,7 +278,7 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
         if (publish_seq > 0) publish_counts_block(counts, mirror, publish_seq);
         return;
     }
-    // behind_ransac: enqueued behind a frame's FIRST batch of hypotheses, before the host has seen its outcome (launch_partition):
+    // behind_ransac: enqueued behind a frame's FIRST batch of hypotheses, before the host has seen its outcome (RansacPartition):
     // the match count is the device's, and a loop that batch did not finish leaves everything to the launch behind the loop
     if (behind_ransac && !counts[CNT_RS_DONE]) return;
     if (d_M) M = *d_M;
@@ -361,22 +360,27 @@ k_partition(const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, Ek
     }
 }
 
-void launch_partition(EkfEngine *e, const EkfMatch *src, int M, const uint8_t *flags, EkfMatch *dst1, EkfMatch *dst0,
-                      int *cnt1, bool map_update, const uint8_t *d_kdesc, int *d_idx0, int publish_seq, bool rescue, const int *d_M,
-                      bool behind_ransac)
+void launch_ransac_partition(EkfEngine *e, const RansacPartition &c)
 {
-    // d_M: M is an upper bound for the launch, the kernel reads the count (see k_partition for behind_ransac)
-    if (M <= 0) {
-        if (cnt1) (void)hipMemsetAsync(cnt1, 0, sizeof(int), e->stream);
-        return;
-    }
-    k_partition<<<1, 1024, 0, e->stream>>>(src, M, flags, dst1, dst0, cnt1, d_kdesc, e->d.feat_desc,
-                                           map_update ? e->d.feat_times_matched : nullptr, e->desc_bytes, d_idx0, e->d.counts,
-                                           e->d_mirror, e->d_mirror ? publish_seq : 0, rescue ? e->d.mask : nullptr, e->d.pred_vis,
-                                           e->d.pred_uv, e->d.pred_S, e->cfg.par.ransacChi2Threshold, d_M, behind_ransac ? 1 : 0);
+    if (c.M <= 0) return;
+    k_partition<<<1, 1024, 0, e->stream>>>(e->d.matches, c.M, e->d.best_flags, e->d.msel, e->d.mout, nullptr, c.d_kdesc, e->d.feat_desc,
+                                           e->d.feat_times_matched, e->desc_bytes, e->d.work_idx, e->d.counts, e->d_mirror, 0, nullptr,
+                                           e->d.pred_vis, e->d.pred_uv, e->d.pred_S, e->cfg.par.ransacChi2Threshold, c.d_M,
+                                           c.behind_ransac ? 1 : 0);
 }
 
-
+void launch_rescue_partition(EkfEngine *e, const RescuePartition &c)
+{
+    int *cnt = e->d.counts + CNT_NRESC;
+    if (c.n_outliers <= 0) {
+        (void)hipMemsetAsync(cnt, 0, sizeof(int), e->stream);
+        return;
+    }
+    k_partition<<<1, 1024, 0, e->stream>>>(e->d.mout, c.n_outliers, e->d.mask, e->d.msel, nullptr, cnt, c.d_kdesc, e->d.feat_desc,
+                                           e->d.feat_times_matched, e->desc_bytes, nullptr, e->d.counts, e->d_mirror,
+                                           e->d_mirror ? c.publish_seq : 0, c.fused_rescue ? e->d.mask : nullptr, e->d.pred_vis,
+                                           e->d.pred_uv, e->d.pred_S, e->cfg.par.ransacChi2Threshold, nullptr, 0);
+}
 
 
 
@@ -441,7 +445,7 @@ void launch_outlier_idx(EkfEngine *e, const EkfMatch *src, int M, int *idx)
     if (M > 0) k_outlier_idx<<<(M + 255) / 256, 256, 0, e->stream>>>(src, M, idx);
 }
 
-// counter block -> GPU-writable host page, then the sequence number the host polls (engine.cpp read_counts)
+// counter block -> GPU-writable host page, then the sequence number the host polls (step.cpp read_counts)
 __global__ void k_publish_counts(const int *counts, int *mirror, int seq)
 {
     const int t = threadIdx.x;

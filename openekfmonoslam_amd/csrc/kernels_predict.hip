@@ -322,7 +322,7 @@ k_predict_cov_features(int nb_cov, T *P, int ld, int n, RowMap rm, const double 
 }
 
 // launch_predict + launch_predict_features(e, nullptr, count, false, true) of the step path in two launches instead of three (or
-// four); returns whether the compaction of the predicted list is left to launch_hp_rows(..., from_flags = true)
+// four); returns whether the compaction of the predicted list is left to launch_hp_rows with HpRowsCall::from_flags
 bool launch_predict_with_features(EkfEngine *e, int count, double dt)
 {
     e->match_gates_valid = false; // pred_uv is rewritten: the gates come with the H P rows of this prediction
@@ -368,7 +368,7 @@ void launch_compact(EkfEngine *e, const int *flag, const int *idx, int count, in
 // state_only: pixel predictions into the scratch tables (vis2/uv2, list plist_sub, counter CNT_NPRED_SUB) so the
 // tables the following stages consume stay untouched.
 // defer_compact (the step's full prediction, more than 256 features): the compaction is left to the launch of k_hp_rows that follows
-// (launch_hp_rows(..., from_flags = true)); returns whether it was
+// (launch_hp_rows with HpRowsCall::from_flags); returns whether it was
 bool launch_predict_features(EkfEngine *e, const int *d_idx, int count, bool state_only, bool defer_compact)
 {
     const bool sub = state_only || d_idx != nullptr;
@@ -557,32 +557,32 @@ k_hp_rows(const T *P, int ld, int n, const int *list, const int *feat_type, cons
 // gates (a full prediction of an unsharded engine: d_list is the predicted list the matcher will walk): chunk 0 also writes the
 // descriptor matcher's gate of every feature into d.match_gates, and the table is valid until something rewrites pred_S or pred_uv
 // -- every other launch of this kernel, every pixel prediction, the measurement budget's selector (match_gates_valid, engine.h)
-void launch_hp_rows(EkfEngine *e, const int *d_list, int n_list, bool count_predicted, const int *d_count, bool from_flags, bool gates)
+void launch_hp_rows(EkfEngine *e, const HpRowsCall &c)
 {
-    unsigned *tp = count_predicted ? e->d.feat_times_predicted : nullptr;
+    unsigned *tp = c.count_predicted ? e->d.feat_times_predicted : nullptr;
     // (Only above 256 listed features: there the launch is several rounds of workgroups bound by the pass over P, and chunk 0's serial
     // chain hides behind the other workgroups' loads (N = 1000: k_match 15.1 -> 12.9 us, this kernel's full pass + 0.4).  A small
     // map's launch is one round, the chain is its critical path, and it loses here what the matcher gains -- N = 200: the full
     // pass + 2.4 us against k_match 8.9 -> 6.8.)
-    Gate *gt = gates && e->shard_world == 1 && n_list > 256 ? (Gate *)e->d.match_gates : nullptr;
+    Gate *gt = c.gates && e->shard_world == 1 && c.n_list > 256 ? (Gate *)e->d.match_gates : nullptr;
     e->match_gates_valid = gt != nullptr;
-    if (n_list <= 0) return;
+    if (c.n_list <= 0) return;
     const int chunks_f = (e->n + 256 * 4 - 1) / (256 * 4), chunks_d = (e->n + 256 * 2 - 1) / (256 * 2);
-    const int *flag = from_flags ? e->d.work_flag : nullptr;
-    int *lo = from_flags ? e->d.plist : nullptr, *co = from_flags ? e->d.counts + CNT_NPRED : nullptr;
-    const int gx = n_list + (from_flags ? 1 : 0);
+    const int *flag = c.from_flags ? e->d.work_flag : nullptr;
+    int *lo = c.from_flags ? e->d.plist : nullptr, *co = c.from_flags ? e->d.counts + CNT_NPRED : nullptr;
+    const int gx = c.n_list + (c.from_flags ? 1 : 0);
     if (e->exact && e->f32)
-        k_hp_rows<float, double><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, d_list, e->d.feat_type,
+        k_hp_rows<float, double><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, c.d_list, e->d.feat_type,
                                                         e->d.feat_covpos, e->d.Hs, e->d.Hf, (double *)e->d.HP,
-                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
+                                                        e->d.pred_S, e->rm, e->d.HPc, tp, c.d_count, flag, c.n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
     else if (e->f32)
-        k_hp_rows<float, float><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, d_list, e->d.feat_type,
+        k_hp_rows<float, float><<<dim3(gx, chunks_f), 256, 0, e->stream>>>((const float *)e->d.P, e->ldP, e->n, c.d_list, e->d.feat_type,
                                                         e->d.feat_covpos, e->d.Hs, e->d.Hf, (float *)e->d.HP,
-                                                        e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
+                                                        e->d.pred_S, e->rm, e->d.HPc, tp, c.d_count, flag, c.n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
     else
-        k_hp_rows<double, double><<<dim3(gx, chunks_d), 256, 0, e->stream>>>((const double *)e->d.P, e->ldP, e->n, d_list,
+        k_hp_rows<double, double><<<dim3(gx, chunks_d), 256, 0, e->stream>>>((const double *)e->d.P, e->ldP, e->n, c.d_list,
                                                          e->d.feat_type, e->d.feat_covpos, e->d.Hs, e->d.Hf,
-                                                         (double *)e->d.HP, e->d.pred_S, e->rm, e->d.HPc, tp, d_count, flag, n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
+                                                         (double *)e->d.HP, e->d.pred_S, e->rm, e->d.HPc, tp, c.d_count, flag, c.n_list, lo, co, e->d.counts, gt, e->d.pred_uv);
 }
 
 // predictMeasurementState on the current state into an EkfPrediction array (device), all features.

@@ -49,7 +49,7 @@ k_ransac_hyp(const double *st, CamD cam, double thr, const RansacRec *rec, const
     const int h = h0 + blockIdx.x;
     if (h >= M) return;
     // sharded filter: this rank evaluates the hypotheses [h_lo, h_hi) -- those of the features it owns, whose H P rows (the gain
-    // columns) it holds; the others' support counts and masks arrive by an all-gather (engine.cpp: ransac_dev)
+    // columns) it holds; the others' support counts and masks arrive by an all-gather (step.cpp: ransac_dev)
     if (h < h_lo || h >= h_hi) return;
     const int tid = threadIdx.x;
     const int nthr = blockDim.x; // 256 for small maps, HYP_THREADS otherwise

@@ -1924,7 +1924,7 @@ static UpdateRouteIn route_input(EkfEngine *e, const UpdateCall &call)
 }
 
 // The gather / assembly launch of the update that follows a step's rescue stage, enqueued BEFORE the host knows how many matches
-// were rescued (engine.cpp step_dev): M_max bounds the grid, d_M is the count on the device, the matches are in d.msel.  The
+// were rescued (step.cpp step_device_counts): M_max bounds the grid, d_M is the count on the device, the matches are in d.msel.  The
 // launch depends on the route only through same_gather_launch's fields (update_route.h), so it goes ahead when the route of the
 // largest and of the smallest possible update agree in them; the route is computed without its side effects (the back-off
 // bookkeeping stays in update_impl).  Returns whether it launched and what it assumed: the step passes that in the update's call,
@@ -1972,7 +1972,7 @@ static int update_impl(EkfEngine *e, const UpdateCall &call)
     if (r.consumed_backoff) --e->ps_backoff;
     if (r.persist && ++e->ps_ok_streak >= 256) e->ps_backoff_len = 0;
     if (!r.col_rb.empty()) e->last_col_rb = r.col_rb; // (ekf_shard_counters)
-    e->last_update.call = call; // what a retry needs (engine.cpp: recover_failed_update)
+    e->last_update.call = call; // what a retry needs (step.cpp: recover_failed_update)
     e->last_update.sym = e->p_exact_sym;
     e->last_update.persist = r.persist;
 

@@ -9,7 +9,7 @@ Model   : downdate x 2/G (a rank computes both triangles of its own rows); rows 
           dependent chain (CHAIN_US per 32-row panel, the fast configuration's measured launch period); the GEMM / G; the inverse
           and everything else replicated; per update a rank receives (G-1)/G of the five digit planes of B (5 B per element) and of the
           columns of S (8 m^2 B; until round 4, above 2048 rows: of the rows of G, 8 B per element) over G-1 xGMI links of LINK_GBS each, not overlapped with compute.
-Round 6: matching and the RANSAC hypotheses are divided by feature ownership (csrc/engine.cpp: match_sharded_dev, ransac_dev): their
+Round 6: matching and the RANSAC hypotheses are divided by feature ownership (csrc/step.cpp: match_sharded_dev, ransac_dev): their
 stage times / G, and every exchange of a frame is charged a LATENCY (XCHG_LAT_US each: the grouped send / recv is enqueued on the
 engine's stream; 2 x S_i after the predictions, 3 match tables, 2 per RANSAC batch, and per update the diagonal of P, the columns of
 S and the digit planes) -- rounds 3-5 priced the bytes only.

@@ -1,7 +1,7 @@
 """Two PROCESSES, one GPU, each stepping its own N = 1000 filter (EKF_PRECISION_F32_EXACT, persistent Cholesky sweep) for `frames`
 frames at the same time: the situation in which a persistent sweep may find the other process's workgroups on the CUs it needs,
 time out, and -- round 6 -- be run again on the launch-per-panel path without the caller seeing anything
-(csrc/engine.cpp: recover_failed_update).  Each worker reports the errors that surfaced (must be none), its retry count and a
+(csrc/step.cpp: recover_failed_update).  Each worker reports the errors that surfaced (must be none), its retry count and a
 checksum of its final state; the parent checks that both filters ended bitwise where a filter running ALONE ends.
 A retried update runs the launch-per-panel sweep -- the same arithmetic in another order of fp64 operations -- so the filters agree to
 rounding, not bitwise: 1e-8 for the fp64 engine; for the fp32-stored one the comparison is held to 1e-4 at 200 frames, the drift horizon

@@ -133,8 +133,8 @@ def _stepped(eng_mod, on, sweep=None):
 
 def test_full_steps_leave_their_records_and_totals(eng_mod):
     """Three frames at N = 50.  The first update of a step runs on the inliers; its second update runs on the list the rescue
-    partition leaves in d.msel, the rescued matches (step_dev: update_dev(e, nr, ...) behind launch_partition(... d.mout ->
-    d.msel)), so stage 2 has n_rescued matches."""
+    partition leaves in d.msel, the rescued matches (step.cpp: high_innovation_update behind launch_rescue_partition, d.mout ->
+    d.msel), so stage 2 has n_rescued matches."""
     e, seq = _stepped(eng_mod, True)
     nis_sum, rows_sum, updates, stage2 = 0.0, 0, 0, 0
     for t in range(3):

@@ -1,5 +1,5 @@
 """GPU: the second update's gather / assembly launch is enqueued behind the rescue stage's partition BEFORE the host has read the
-rescued count (device-count steps, engine.cpp step_dev): its grid is sized by the outlier count and the kernel reads the count
+rescued count (device-count steps, step.cpp step_device_counts): its grid is sized by the outlier count and the kernel reads the count
 (k_gather_assemble with d_M).  A device-count step must give what a host-count step gives (ekf_keep_step_predictions forces the
 host counts, and with them the host-sized launch) bit for bit, at every size of the second update where the device-side decoding
 of the grid changes.

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libekf_engine.so")
-SOURCES = ["engine.cpp", "step.cpp", "kernels_predict.hip", "kernels_match.hip", "kernels_ransac.hip", "kernels_update.hip",
+SOURCES = ["engine.cpp", "map_host.cpp", "step.cpp", "kernels_predict.hip", "kernels_match.hip", "kernels_ransac.hip", "kernels_update.hip",
            "kernels_pupdate.hip", "kernels_pexact.hip", "kernels_map.hip", "kernels_ncc.hip", "kernels_gemm.hip", "kernels_detect.hip",
            "kernels_consistency.hip", "kernels_budget.hip", "kernels_external.hip", "kernels_fixedmap.hip", "kernels_mapblob.hip"]
 # the decision-making stages (projection, gates, dead-bands) are compiled without FMA contraction so their fp64

@@ -13,6 +13,7 @@
 #include "../../include/ekf_engine.h"
 #include "device_buffers.h"
 #include "device_math.h"
+#include "map_blob.h" // the per-feature row sizes
 #include "patch_normal.h"
 #include "update_route.h" // NB, LD_ALIGN, B_SWEEP_MAX, round_up and the route of an update
 
@@ -666,9 +667,11 @@ void launch_ncc_normal(EkfEngine *e, int M);
 // through the three kernels of DESIGN.md 4.8 instead (d.wide_list / d.wide_part sized for the current frame: engine.cpp)
 // coef > 0: the distinctiveness test of DESIGN.md 4.10 (d.mt_rival, CNT_RIVAL_WITH / CNT_RIVAL_REJ; with wide, d.wide_part holds two tables)
 void launch_match_ncc(EkfEngine *e, int n_pred, bool subpix, bool wide, double coef);
-constexpr int NCC_TT = 121;                // bytes of one 11 x 11 template; d.tmpl / d.wtmpl hold 3 levels per feature
-constexpr int WARP_S = 41, WARP_SS = WARP_S * WARP_S; // template warp: side and bytes of one source patch; d.wsrc holds 3 per feature
-constexpr int WPOSE_DOUBLES = 9;           // ... and its capture pose record in d.wpose: r0 (3), q0 (4), capture pixel (2)
+// (the per-feature row sizes are stated once, in map_blob.h)
+constexpr int NCC_TT = mapblob::TEMPLATE_LEVEL_BYTES; // bytes of one 11 x 11 template; d.tmpl / d.wtmpl hold 3 levels per feature
+constexpr int WARP_S = mapblob::WARP_SOURCE_SIDE, WARP_SS = WARP_S * WARP_S; // template warp: side and bytes of one source patch; d.wsrc holds 3 per feature
+constexpr int WPOSE_DOUBLES = mapblob::WARP_POSE_DOUBLES; // ... and its capture pose record in d.wpose: r0 (3), q0 (4), capture pixel (2)
+static_assert(sizeof(PatchNormalRec) == mapblob::PATCH_NORMAL_BYTES, "a row of d.wnorm is a row of the PATCH_NORMALS section");
 constexpr int NCC_WIDE_TILE = 32;          // coarse candidates per tile side
 constexpr int NCC_WIDE_SLOT_BYTES = 80;    // sizeof(WideSlot), kernels_ncc.hip
 constexpr int NCC_WIDE_PARTIAL_BYTES = 16; // sizeof(WidePartial)

@@ -24,7 +24,12 @@ enum { SEC_X13 = 0, SEC_FEAT_POS, SEC_FEAT_TYPE, SEC_DESC, SEC_TIMES_PREDICTED, 
 enum { P_TRIANGLE = 0, P_FULL = 1 };
 // bits of section_mask (EKF_MAP_* of ekf_engine.h)
 constexpr uint32_t MASK_TEMPLATES = 1, MASK_WARP_SOURCES = 2, MASK_PATCH_NORMALS = 4, MASK_ALL = 7;
-constexpr int TEMPLATE_BYTES = 363, WARP_SOURCE_BYTES = 3 * 1681, WARP_POSE_DOUBLES = 9, PATCH_NORMAL_BYTES = 48;
+// A feature's row in the optional sections.  The one place these sizes are stated: engine.h defines NCC_TT, WARP_S and WPOSE_DOUBLES
+// from them and ties sizeof(PatchNormalRec) to the last; feature_tables.h sizes the device tables by them.
+constexpr int TEMPLATE_LEVELS = 3;                                                       // pyramid levels of a template and of a source patch
+constexpr int TEMPLATE_LEVEL_BYTES = 11 * 11, TEMPLATE_BYTES = TEMPLATE_LEVELS * TEMPLATE_LEVEL_BYTES; // 363
+constexpr int WARP_SOURCE_SIDE = 41, WARP_SOURCE_BYTES = TEMPLATE_LEVELS * WARP_SOURCE_SIDE * WARP_SOURCE_SIDE; // 3 x 1681
+constexpr int WARP_POSE_DOUBLES = 9, PATCH_NORMAL_BYTES = 48;
 constexpr int32_t MAX_N = 1 << 24, MAX_DESC_BYTES = 4096; // what the size arithmetic below is safe for in 64 bits
 static_assert(sizeof(EkfCamera) == 104, "the CAMERA section is the bytes of EkfCamera");
 

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY: map management (csrc/kernels_map.hip and its host halves in csrc/engine.cpp) restated in numpy in
+"""TEST INFRASTRUCTURE ONLY: map management (csrc/kernels_map.hip and its host halves in csrc/map_host.cpp) restated in numpy in
 np.longdouble -- adding a batch of features, removing features, converting an inverse-depth feature to XYZ, the linearity index --
 with the per-entry tolerances of every value the device computes, and the scenes the stage tests run on
 (tests/test_gpu_map_stages.py on the device, tests/test_map_ref_cpu.py against the oracle and for the input conditions).

@@ -1,5 +1,5 @@
 """ekf_convert_all_inverse_depth_to_depth (k_convert_all_prepare, k_convert_all_P in csrc/kernels_map.hip; host half in
-csrc/engine.cpp) through the C ABI, PER ENTRY against tests/convert_all_ref.py (numpy, np.longdouble): every entry of P' and of
+csrc/map_host.cpp) through the C ABI, PER ENTRY against tests/convert_all_ref.py (numpy, np.longdouble): every entry of P' and of
 the new positions, the layout, and everything the call must leave alone, at the sizes where 3-row features straddle the kernel's
 64-row tiles; then the selection, an asymmetric P, the single route's map, history independence, the refusals, the driver class
 and the sample program.

@@ -161,8 +161,8 @@ def golden_frames():
 NF = 12  # captured features of the golden-frame engines
 
 
-def golden_engine(eng_mod, frames, steps, cap=96, modes=True):
-    e = eng_mod.EkfEngine(s3_camera(320, 240), s3_params(), cap)
+def golden_engine(eng_mod, frames, steps, cap=96, modes=True, precision=F64, desc=None):
+    e = eng_mod.EkfEngine(s3_camera(320, 240), s3_params(), cap, precision=precision)
     e.set_sweep_mode(SWEEP_LAUNCHES)
     if modes:
         e.set_template_warp(True)
@@ -171,7 +171,7 @@ def golden_engine(eng_mod, frames, steps, cap=96, modes=True):
     e.upload_image(frames[0])
     uv = e.detect_new_features(NF, min_response=1e10)
     assert len(uv) == NF
-    e.add_features(uv)
+    e.add_features(uv, desc)
     e.capture_templates(np.arange(NF), uv)
     for t in range(1, 1 + steps):
         assert e.step_image(frames[t]).status == 0

@@ -1,5 +1,5 @@
 """Stage tests of map management (csrc/kernels_map.hip: k_addfeat_prepare / _rows / _corner, k_compact_P, k_linearity,
-k_convert_prepare / _rows / _apply; host halves ekf_add_features, compact_map, ekf_convert_inverse_depth_to_depth in csrc/engine.cpp)
+k_convert_prepare / _rows / _apply; host halves ekf_add_features, compact_map, ekf_convert_inverse_depth_to_depth in csrc/map_host.cpp)
 through the C ABI, PER ENTRY against tests/map_ref.py (numpy, np.longdouble), at the sizes where the launches change shape.
 
 Every bound is derived, not measured (map_ref.py: u_store |ref| + K u64 sum|terms|, K counted from the kernel's operations; moved

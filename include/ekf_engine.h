@@ -312,6 +312,50 @@ int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M);
 int ekf_set_fixed_map(EkfEngine *e, int on);
 int ekf_get_fixed_map(const EkfEngine *e, int *on, int64_t *updates);
 
+/* Iterated EKF update (opt-in: with 1 pass everything is the engine without it, bit for bit).  Gauss-Newton on
+ * the update's own MAP cost: the camera measurement is linearised again at the new estimate and the update is solved again from
+ * the PRIOR.  With x^, P the state and covariance before the update, z the matched pixels, R = pixelErrorX I and x^0 = x^, pass
+ * i = 0 .. K - 1 forms
+ *     h_i, H_i = the predictions and Jacobians of the matched features at x^i (P is still the prior)
+ *     nu_i     = z - h_i - H_i (x^ - x^i)      (plain differences of the stored parameters, the quaternion included)
+ *     S_i      = H_i P H_i' + R,   x^(i+1) = x^ + P H_i' inv(S_i) nu_i
+ * The passes before the last are state-only updates (q is not normalised, P is not touched, as ekf_update_only_state); the last is
+ * the covariance update P+ = sym(P) - B'B with B = inv(L) H_(K-1) P, followed by the normalisation of q and its Jacobian on P.  The
+ * dead-bands of ekf_update apply to nu_i and to the whole step from x^.  iterations = 1 is ekf_update, bit for bit.
+ *
+ * The iteration ends early, and the pass that then runs is the covariance pass: (tol > 0) once a pass moved no state by tol standard
+ * deviations of the prior -- step[i] < tol -- and when a matched feature is not predicted at x^i (it left the image): the update is
+ * then finished from the last linearisation point at which every match was predicted.  Undamped Gauss-Newton need not contract
+ * (large innovations on a fresh map): the per-pass steps of the record show it.
+ *
+ * ekf_update_iterated: the stage; arguments, validation, preconditions and failure as ekf_update (S of a pass not positive
+ * definite: EKF_ERR_NOT_POSITIVE_DEFINITE, x and P as before the call, the remaining passes not run).  iterations 1 ..
+ * EKF_MAX_UPDATE_ITERATIONS, tol >= 0 and finite.  ekf_set_update_iterations: the mode of ekf_step, ekf_step_frame, ekf_step_image
+ * and ekf_step_staged_image -- both updates of a step are iterated; such a step reads its counts back after every stage (as with
+ * ekf_keep_step_predictions) and launches no early gather.  Default 1, 0.  Filter consistency (ekf_set_consistency) records the
+ * covariance pass alone, with nu_(K-1).  After an iterated update the prediction tables of the matched features (what
+ * ekf_predict_measurements left) hold the predictions, Jacobians and H P rows at x^(K-1).
+ *
+ * EKF_ERR_INVALID_ARG with a message and nothing written: a sharded engine; iterations outside 1 .. 8; tol < 0 or not finite;
+ * iterations > 1 while the fixed-map mode is on, and ekf_set_fixed_map(on) while iterations > 1 (the fixed-map update has no
+ * state-only form).  EKF_PRECISION_F32 is allowed.  The first use allocates 212 bytes per feature of the engine's capacity.
+ *
+ * ekf_get_iteration_records: one record per iterated update of the last ekf_update_iterated or step (0 .. 2, in the order they
+ * ran; a step with iterations = 1 keeps none).  ekf_get_linearisation_point: x^(K-1) of the last iterated update -- the 13 camera
+ * values and 6 doubles per feature of the map as it is now, ekf_num_features (feature_pos may be NULL); EKF_ERR_INVALID_ARG before
+ * the first, and again once the map was replaced or its layout changed (ekf_set_state, ekf_load_map, ekf_reset, features added,
+ * removed or converted): the point described the map that was.  Both synchronise the stream.
+ * out may be NULL (count only); capacity < *count -> EKF_ERR_CAPACITY with *count = number needed.
+ * A record whose pass failed: stop_reason = failed, passes_run = the passes that ran before it, x and P as before the update.  Inside a
+ * step, the covariance pass of the second update is retried (a timed-out persistent sweep) or found failed only at the step's last
+ * read-back: step[passes_run - 1] of that record was then taken from the frozen state and is |x^ - x^(K-1)|, and a failure shows in
+ * EkfStepInfo.status, not in the record. */
+int ekf_update_iterated(EkfEngine *e, const EkfMatch *matches, int M, int iterations, double tol);
+int ekf_set_update_iterations(EkfEngine *e, int iterations, double tol);
+int ekf_get_update_iterations(const EkfEngine *e, int *iterations, double *tol);
+int ekf_get_iteration_records(EkfEngine *e, EkfIterationRecord *out, int capacity, int *count);
+int ekf_get_linearisation_point(EkfEngine *e, double x13[13], double *feature_pos);
+
 /* -- stages ---------------------------------------------------------------------------------------------- */
 /* stateAndCovariancePrediction(State&, Matd&)            EKF/StateAndCovariancePrediction.h:41 (.cpp:244-253) */
 int ekf_predict(EkfEngine *e);

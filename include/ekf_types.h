@@ -150,6 +150,20 @@ typedef struct EkfExternalUpdate {
     int32_t applied;            /* 1: x and P were updated; 0: the gate rejected it, nothing changed */
 } EkfExternalUpdate;            /* 144 bytes, no padding */
 
+/* Iterated update (ekf_update_iterated / ekf_set_update_iterations): one record per iterated update of the last call.  No
+ * counterpart in the reference, which linearises once. */
+#define EKF_MAX_UPDATE_ITERATIONS 8
+enum { EKF_ITER_STOP_COUNT = 0, EKF_ITER_STOP_TOL = 1, EKF_ITER_STOP_FEATURE_LEFT = 2, EKF_ITER_STOP_FAILED = 3 };
+
+typedef struct EkfIterationRecord {
+    int32_t stage;       /* 0 = ekf_update_iterated, 1 = a step's first (low-innovation) update, 2 = its second                   */
+    int32_t passes_run;  /* the result is the iterated update of this many passes (1: the plain update)                          */
+    int32_t stop_reason; /* EKF_ITER_STOP_*: the pass count, the tolerance, a matched feature left the image, a sweep failed      */
+    int32_t _pad;
+    double step[EKF_MAX_UPDATE_ITERATIONS]; /* step[i] = max_j |x_j^(i+1) - x_j^i| / sqrt(P_jj) over the state columns with P_jj > 0,
+                                             * P the covariance before the update; 0 from passes_run on                           */
+} EkfIterationRecord; /* 80 bytes, no padding */
+
 /* What the header of a map blob says (ekf_save_map / ekf_load_map / ekf_map_blob_info; the format: DESIGN.md 9.3).  No
  * counterpart in the reference, which cannot save its map. */
 typedef struct EkfMapBlobInfo {

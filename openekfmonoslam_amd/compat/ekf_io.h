@@ -829,6 +829,22 @@ public:
         fixedMap_ = on;
     }
     bool fixedMap() const { return fixedMap_; }
+    // Iterated update (ekf_set_update_iterations): both updates of a step linearise the measurement again at every
+    // new estimate, up to `iterations` passes (1: the plain update); tol > 0 ends the iteration once a pass moved no state by tol
+    // standard deviations.  At any time, it takes effect with the next step.  output.yml and log.txt do not change.  Throws for
+    // iterations outside 1 .. 8, a tol that is negative or not finite, and above one pass while the fixed-map mode is on.
+    void setUpdateIterations(int iterations, double tol = 0.0)
+    {
+        chk(ekf_set_update_iterations(e_, iterations, tol), "ekf_set_update_iterations");
+    }
+    // one record per iterated update of the last step (passes run, why it stopped, the normalised step of every pass)
+    void iterationRecords(std::vector<EkfIterationRecord> &out)
+    {
+        int n = 0;
+        out.resize(2);
+        chk(ekf_get_iteration_records(e_, out.data(), (int)out.size(), &n), "ekf_get_iteration_records");
+        out.resize((size_t)n);
+    }
     // Frame intervals (ekf_set_frame_interval): the interval the prediction of every following step runs over, in
     // units of the frame period linearAccelSD / angularAccelSD were tuned for (default 1; a frame after k dropped ones: k + 1); at
     // any time, it takes effect with the next step.  Once it has been called log.txt gains one line per step, "Frame interval:

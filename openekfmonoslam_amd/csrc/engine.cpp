@@ -635,6 +635,10 @@ int ekf_set_fixed_map(EkfEngine *e, int on)
             e->err = std::string("ekf_set_fixed_map: ") + why;
             return EKF_ERR_INVALID_ARG;
         }
+        if (e->update_iterations > 1) { // the fixed-map update has no state-only form
+            e->err = "ekf_set_fixed_map: not available while ekf_set_update_iterations asks for more than one pass";
+            return EKF_ERR_INVALID_ARG;
+        }
         int rc = fixed_map_scratch(e);
         if (rc) return rc;
     }

@@ -72,6 +72,7 @@ enum {
     CNT_PN_SKIP,      // ... and listed features it left alone (no source patch, no usable level, solve not finite)
     CNT_RIVAL_WITH,   // distinctiveness test: accepted matches of the last NCC match that had a rival in the gate (k_ncc_match<.., true>)
     CNT_RIVAL_REJ,    // ... and those of them the test rejected
+    CNT_ITER_SMALL,   // iterated update: the normalised step of the pass just finished is below the call's tolerance (k_iter_step)
     CNT_COUNT = 40    // (publish_counts_block / k_publish_counts copy with the lanes t < 64; the mirror page holds 64 ints)
 };
 constexpr int MAX_SHARD_WORLD = 16;
@@ -106,6 +107,10 @@ struct ExtResult {
     EkfExternalUpdate out;
     int verdict, pad;
 };
+
+// iterated update: doubles of the state block in front of the feature parameters of a state image; updates of one
+// call that keep a record (a step's two)
+constexpr int ITER_X = ST_F, ITER_SLOTS = 2;
 
 // fixed-map update: x_save is written by the strip kernel for the tail, whose workgroups each need the camera state
 // as it was while one of them rewrites it; updates is incremented by the tail of every update that was applied
@@ -264,6 +269,14 @@ struct DeviceArrays {
     int *bud_all = nullptr;                // the list before the selection (the compaction writes d.plist from it)
     int *bud_flag = nullptr;               // selected?
     EkfMeasurementRank *bud_recs = nullptr; // ekf_get_measurement_ranks
+    // iterated update (ekf_update_iterated / ekf_set_update_iterations; one group, allocated by the first use).  A state
+    // image is ITER_X doubles of the state block (x13, R) followed by the 6 N feature parameters
+    double *iter_uv = nullptr;    // 2 per feature: pred_uv + H_i (x^ - x^i) of the matched features, the table a pass i >= 1 forms nu from
+    double *iter_snap = nullptr;  // x^: the state image as it was before the update
+    double *iter_lin = nullptr;   // two state images used in turn: the linearisation points x^(i-1) and x^i
+    double *iter_diag = nullptr;  // diag(P) before the update, by state index (ncap doubles)
+    double *iter_step = nullptr;  // ITER_SLOTS x EKF_MAX_UPDATE_ITERATIONS: the normalised step of every pass of an update of the last call
+    int *iter_idx = nullptr;      // the matched features, update order: the sub-list of a pass's prediction
     MapBlobCtl *mb_ctl = nullptr; // map blob (ekf_save_map / ekf_load_map; allocated by the first of them)
     float *Pdiag = nullptr;     // sharded exact configuration: diagonal of P, n floats, completed by an exchange
     int8_t *Bstage = nullptr;   // ... and the digit planes of B in the exchange layout [column][plane][k / 16][16]
@@ -402,6 +415,11 @@ struct EkfEngine {
     int fm_rows = 0;               // rows of each of the two tables in d.fm_gain
     bool consistency = false;      // ekf_set_consistency: every covariance update is followed by k_consistency
     int cons_epoch = 0;            // bumped when a step or an ekf_update begins with the mode on (ConsCtl::epoch)
+    int update_iterations = 1;     // ekf_set_update_iterations: passes of both updates of the step functions; 1: the plain update
+    double update_iter_tol = 0.0;  // ... and the normalised step below which the next pass is the last (0: by count alone)
+    std::vector<EkfIterationRecord> iter_records; // the iterated updates of the last call (their steps are in d.iter_step until asked for)
+    int iter_lin_sel = -1;         // which image of d.iter_lin the last iterated update linearised its covariance pass at (-1: none yet)
+    int iter_lin_N = 0;            // ... and the features it holds
     double frame_interval = 1.0;   // ekf_set_frame_interval: the dt of ekf_predict and of every step function
     double step_dt = 1.0;          // the interval of the step being run: frame_interval, or the staged table's entry of its frame
     std::vector<double> staged_dt; // ekf_set_staged_intervals: per index of a pre-staged sequence, kept on the host (the value is a kernel argument)
@@ -650,7 +668,19 @@ void launch_map_unpack(EkfEngine *e, const void *staging, int n, int elem_bytes,
 void launch_external_update(EkfEngine *e, int m);
 // filter consistency (kernels_consistency.hip): NIS and the per-match innovations of the update whose sweep was just enqueued, from
 // d.zvec, the M matches and the prediction tables -> d.cons_ctl / d.cons_recs, recorded under `stage`; does nothing when the error flag is set
-void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage);
+// uv_tab: the prediction table the update formed nu from (UpdateCall::pred_uv, or d.pred_uv)
+void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage, const double *uv_tab);
+// iterated update (kernels_iterate.hip); a state image: engine.h DeviceArrays::iter_snap
+// _snapshot: the state -> d.iter_snap and image 0 of d.iter_lin, diag(P) -> d.iter_diag, the matches' features -> d.iter_idx, steps[0..8) = 0
+// _step: max_j |x_j - prev_j| / sqrt(P_jj) over the state columns with P_jj > 0 -> *step_out, x being the live state and prev image
+//   `prev` of d.iter_lin; cur >= 0: the live state -> image cur, and counts[CNT_ITER_SMALL] = (tol > 0 and the step is below it)
+// _shift_restore: d.iter_uv of the M matches from the prediction tables, x^ and image `lin`; then the live state <- x^ (all features)
+// _load: the live state <- image `lin`.  The two that write the state leave it alone while the filter is frozen, unless even_frozen
+// (the host rebuilds the tables of a failed pass in front of its retry and puts x^ back itself).
+void launch_iter_snapshot(EkfEngine *e, const EkfMatch *matches, int M, double *steps);
+void launch_iter_step(EkfEngine *e, int prev, int cur, double *step_out, double tol);
+void launch_iter_shift_restore(EkfEngine *e, const EkfMatch *matches, int M, int lin, bool even_frozen = false);
+void launch_iter_load(EkfEngine *e, int lin, bool even_frozen = false);
 // measurement budget (kernels_budget.hip): S_i of the np features in d.plist -> d.pred_S, their keys, ranks, records and selected flags
 // (rank < K, or all when np <= K) -> d.bud_*; launch_compact (k_compact) then turns flags into a list
 void launch_budget_select(EkfEngine *e, int np, int K);

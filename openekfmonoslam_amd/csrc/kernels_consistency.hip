@@ -76,10 +76,10 @@ k_consistency(const double *zvec, const EkfMatch *matches, int M, const double *
     }
 }
 
-void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage)
+void launch_consistency(EkfEngine *e, const EkfMatch *matches, int M, int stage, const double *uv_tab)
 {
     if (M <= 0 || M > e->cap || !e->d.cons_ctl || !e->d.cons_recs) return;
-    k_consistency<<<1, 256, 0, e->stream>>>(e->d.zvec, matches, M, e->d.pred_uv, e->d.pred_S, e->cfg.cam.pixelErrorX, e->d.counts,
+    k_consistency<<<1, 256, 0, e->stream>>>(e->d.zvec, matches, M, uv_tab, e->d.pred_S, e->cfg.cam.pixelErrorX, e->d.counts,
                                            stage, e->cons_epoch, e->cap, e->d.cons_ctl, e->d.cons_recs);
 }
 

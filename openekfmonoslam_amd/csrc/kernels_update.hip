@@ -1591,7 +1591,7 @@ static int exchange_p_diag(EkfEngine *e, const UpdateRoute &r)
     return e->exchange_hook(e, EKF_XCHG_PDIAG, e->d.Pdiag, sizeof(float), drb, "the diagonal of P");
 }
 
-#define GATHER_ARGS matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, e->d.pred_uv, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
+#define GATHER_ARGS matches, M, m_pad, (const TB *)e->d.HP, (TB *)e->d.G, ld, n_pad, uv_tab, e->d.Hs, e->d.Hf, e->d.feat_type, e->d.feat_covpos, e->d.nu, \
                     e->d.mHs, e->d.mHf, e->d.mpos, e->d.mdim, e->d.HPc, e->d.Gc, EXACT ? e->d.Bexp : nullptr
 
 // grid.x of the gather: 16 bytes of a row per thread -- or one workgroup per row where nothing is copied (bookkeeping, row map, its
@@ -1603,9 +1603,9 @@ static int gather_grid_x(const UpdateRoute &r)
 }
 
 // gather and the assembly of S in one launch (the assembly reads the prediction tables, not the gather's output).
-// d_M: r.M is an upper bound and the kernel reads the count (k_gather_assemble)
+// d_M: r.M is an upper bound and the kernel reads the count (k_gather_assemble); uv_tab: the prediction table behind nu (UpdateCall::pred_uv)
 template <typename T, typename TB, bool EXACT>
-static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const EkfMatch *matches, const int *d_M)
+static void launch_gather_assemble(EkfEngine *e, const UpdateRoute &r, const EkfMatch *matches, const int *d_M, const double *uv_tab)
 {
     const int M = r.M, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
     double *V = e->d.Dinv, *W = inv_W(e, r);
@@ -1625,6 +1625,7 @@ template <typename T, typename TB, bool EXACT>
 static int gather_and_assemble(EkfEngine *e, const UpdateRoute &r, const UpdateCall &call)
 {
     const EkfMatch *matches = call.matches;
+    const double *uv_tab = call.pred_uv ? call.pred_uv : e->d.pred_uv;
     int rc;
     hipStream_t s = e->stream;
     const int M = r.M, m = r.m, m_pad = r.m_pad, n = r.n, n_pad = r.n_pad, ld = e->ldP, ldS = e->ldS, ldw = e->ldW;
@@ -1633,7 +1634,7 @@ static int gather_and_assemble(EkfEngine *e, const UpdateRoute &r, const UpdateC
     float *Wf = inv_Wf<TB>(e, r);
     dim3 grid(gather_grid_x<TB>(r), m_pad);
     if (r.merged_ga) {
-        if (!early_gather_serves(call.early, r)) launch_gather_assemble<T, TB, EXACT>(e, r, matches, nullptr);
+        if (!early_gather_serves(call.early, r)) launch_gather_assemble<T, TB, EXACT>(e, r, matches, nullptr, uv_tab);
     } else if (apriori && !sharded) // a-priori column scales from the diagonal of the covariance itself
         k_gather<TB, T><<<grid, 256, 0, s>>>(GATHER_ARGS, (const T *)e->d.P, ld, n, planes_b || sym_g ? e->d.Grow : nullptr, e->px_scale_shift);
     else
@@ -1871,7 +1872,7 @@ static int downdate_and_tail(EkfEngine *e, const UpdateRoute &r, const UpdateCal
     hipStream_t s = e->stream;
     const int n = r.n, ld = e->ldP;
     // filter consistency: z is final in d.zvec and the error flag tells whether this sweep failed
-    if (e->consistency && (r.update_cov || r.fixed_map)) launch_consistency(e, call.matches, r.M, call.stage);
+    if (e->consistency && (r.update_cov || r.fixed_map)) launch_consistency(e, call.matches, r.M, call.stage, call.pred_uv ? call.pred_uv : e->d.pred_uv);
     if (r.fixed_map) {
         // the camera's strip of P and the camera state (kernels_fixedmap.hip): Y' X with Y = B[:, 0:13], X = B where the sweep formed
         // the rows of B, Y = K_c', X = G (the gathered rows of H P) where it did not
@@ -1939,7 +1940,7 @@ static EarlyGather early_gather_impl(EkfEngine *e, int M_max, const int *d_M, in
     in.M = 1;
     const UpdateRoute lo = choose_update_route(in);
     if (hi.refusal || lo.refusal || !hi.merged_ga || !same_gather_launch(hi, lo)) return EarlyGather();
-    launch_gather_assemble<T, TB, EXACT>(e, hi, call.matches, d_M);
+    launch_gather_assemble<T, TB, EXACT>(e, hi, call.matches, d_M, e->d.pred_uv);
     EarlyGather g;
     g.launched = true;
     g.planes_b = hi.planes_b; g.apriori = hi.apriori; g.persist = hi.persist; g.b_in_sweep = hi.b_in_sweep;

@@ -67,6 +67,7 @@ static void map_replaced(EkfEngine *e)
     e->n_step_preds = 0;
     e->bud_recs_n = e->bud_predicted = e->bud_selected = 0; // measurement budget: the records belong to the map they were made on
     e->last_match_warped = false;
+    e->iter_lin_sel = -1; // iterated update: the linearisation point was one of the map that was (ekf_get_linearisation_point)
     refresh_row_map(e);
 }
 
@@ -79,6 +80,7 @@ static void map_layout_changed(EkfEngine *e)
 {
     e->n_pred = 0;
     e->last_match_warped = false;
+    e->iter_lin_sel = -1; // iterated update: the linearisation point has the features and the order of the layout that was
     refresh_row_map(e);
 }
 

@@ -420,6 +420,204 @@ static int recover_failed_update(EkfEngine *e, int *status)
     return EKF_OK;
 }
 
+// --------------------------------------------------------------------------------- iterated update
+// the mode's scratch, on its first use (DeviceArrays::iter_*)
+static int iterate_scratch(EkfEngine *e)
+{
+    if (e->d.iter_uv) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const size_t image = ITER_X + 6 * (size_t)e->cap;
+    auto g = e->bufs.group();
+    g.alloc(&e->d.iter_uv, 2 * (size_t)e->cap);
+    g.alloc(&e->d.iter_snap, image);
+    g.alloc(&e->d.iter_lin, 2 * image);
+    g.alloc(&e->d.iter_diag, (size_t)e->ncap);
+    g.alloc(&e->d.iter_step, (size_t)ITER_SLOTS * EKF_MAX_UPDATE_ITERATIONS);
+    g.alloc(&e->d.iter_idx, (size_t)e->cap);
+    if (g.commit() != hipSuccess) return alloc_failed(e, g.status(), "iterated update scratch");
+    return EKF_OK;
+}
+
+// why an update of `iterations` passes is not available on this engine, or null
+static const char *iterations_refusal(const EkfEngine *e, int iterations, double tol)
+{
+    if (iterations < 1 || iterations > EKF_MAX_UPDATE_ITERATIONS) return "iterations must be 1 .. 8";
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return "tol must be finite and not negative";
+    if (e->shard_world > 1) return "not available on a sharded engine";
+    if (iterations > 1 && e->fixed_map) return "more than one pass is not available while the fixed-map mode is on";
+    return nullptr;
+}
+
+// The covariance update with the matches in e->d.msel[0..M) in up to K passes, recorded as `stage`; the record goes to
+// e->iter_records, its steps to slot iter_records.size() of d.iter_step.  Pass 0 is today's update from the tables of the caller's
+// prediction; pass i >= 1 predicts the matched features again at x^i (a sub-list prediction: no counter of the map moves), shifts
+// the predictions to the prior (k_iter_shift_restore) and runs the update from x^ with that table.  Two launches per extra pass
+// beside the prediction's and the update's own, and no read-back but the prediction's -- which also brings the tolerance flag, the
+// number predicted and the error flag of the pass before.  *status: as recover_failed_update (a pass whose S is not positive
+// definite: x and P are those before the update, the remaining passes are not run); returns a hard error or EKF_OK.
+static int iterated_update_dev(EkfEngine *e, int M, int stage, int K, double tol, int *status)
+{
+    if (M <= 0) return EKF_OK; // Update.cpp:292
+    int rc;
+    if ((rc = iterate_scratch(e))) return rc;
+    const int slot = (int)e->iter_records.size();
+    if (slot >= ITER_SLOTS) {
+        e->err = "more iterated updates in one call than records";
+        return EKF_ERR_INVALID_ARG;
+    }
+    EkfIterationRecord rec;
+    std::memset(&rec, 0, sizeof(rec));
+    rec.stage = stage;
+    rec.stop_reason = EKF_ITER_STOP_COUNT;
+    double *steps = e->d.iter_step + (size_t)slot * EKF_MAX_UPDATE_ITERATIONS;
+    launch_iter_snapshot(e, e->d.msel, M, steps);
+    int lin = 0; // the image of d.iter_lin that holds the linearisation point of the pass about to run
+    bool last = K == 1;
+    for (int i = 0;; ++i) {
+        if (i >= 1) { // the live state is x^i
+            int np = 0;
+            PredictCall sub;
+            sub.d_idx = e->d.iter_idx; sub.count = M;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                launch_iter_step(e, lin, lin ^ 1, steps + (i - 1), tol);
+                if ((rc = predict_measurements_dev(e, sub, &np))) return rc;
+                if (!e->h_counts[CNT_ERR]) break;
+                // pass i - 1 failed (seen at this read-back; everything behind it left x = x^ alone): run it again or give up
+                // (recover_failed_update), then this pass's preamble again.  The prediction above ran at x^ and overwrote the tables
+                // of pass i - 1, which its retry gathers from: they are formed again at x^(i-1) first, and x^ is put back
+                if (i >= 2) {
+                    launch_iter_load(e, lin, /*even_frozen*/ true);
+                    if ((rc = predict_measurements_dev(e, sub, &np))) return rc;
+                    launch_iter_shift_restore(e, e->d.msel, M, lin, /*even_frozen*/ true);
+                }
+                int st = EKF_OK;
+                if ((rc = recover_failed_update(e, &st))) return rc;
+                if (st) {
+                    rec.passes_run = i - 1;
+                    rec.stop_reason = EKF_ITER_STOP_FAILED;
+                    e->iter_records.push_back(rec);
+                    *status = st;
+                    return EKF_OK;
+                }
+            }
+            if (np < M) {
+                // a matched feature is not predicted at x^i: finish from x^(i-1), where all of them were, by predicting there again
+                rec.stop_reason = EKF_ITER_STOP_FEATURE_LEFT;
+                last = true;
+                launch_iter_load(e, lin);
+                if ((rc = predict_measurements_dev(e, sub, &np))) return rc;
+            } else {
+                lin ^= 1;
+                if (tol > 0.0 && e->h_counts[CNT_ITER_SMALL]) {
+                    rec.stop_reason = EKF_ITER_STOP_TOL;
+                    last = true;
+                }
+                if (i == K - 1) last = true;
+            }
+            launch_iter_shift_restore(e, e->d.msel, M, lin);
+        }
+        UpdateCall call;
+        call.matches = e->d.msel; call.M = M; call.kind = last ? UPDATE_COV : UPDATE_STATE_ONLY; call.stage = stage;
+        call.pred_uv = i >= 1 ? e->d.iter_uv : nullptr;
+        if ((rc = launch_update(e, call)) || (rc = check_async(e))) return rc;
+        if (last) {
+            rec.passes_run = rec.stop_reason == EKF_ITER_STOP_FEATURE_LEFT ? i : i + 1;
+            break;
+        }
+    }
+    launch_iter_step(e, lin, -1, steps + (rec.passes_run - 1), 0.0); // the last pass's step, to the normalised state
+    e->iter_lin_sel = lin;
+    e->iter_lin_N = e->N;
+    e->iter_records.push_back(rec);
+    return EKF_OK;
+}
+
+int ekf_update_iterated(EkfEngine *e, const EkfMatch *matches, int M, int iterations, double tol)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (const char *why = iterations_refusal(e, iterations, tol)) {
+        e->err = std::string("ekf_update_iterated: ") + why;
+        return EKF_ERR_INVALID_ARG;
+    }
+    int rc = validate_matches(e, matches, M);
+    if (rc) return rc;
+    e->iter_records.clear();
+    if (M == 0) return EKF_OK;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(e->d.msel, matches, (size_t)M * sizeof(EkfMatch), hipMemcpyHostToDevice, e->stream));
+    if (e->consistency) ++e->cons_epoch; // the record of this call: the covariance pass
+    int status = EKF_OK;
+    const int retries0 = e->sweep_retries;
+    if ((rc = iterated_update_dev(e, M, /*stage*/ 0, iterations, tol, &status))) return rc;
+    if (status) return status;
+    rc = finish_update(e);
+    EkfIterationRecord &rec = e->iter_records.back();
+    if (rc == EKF_ERR_NOT_POSITIVE_DEFINITE || rc == EKF_ERR_NON_FINITE || rc == EKF_ERR_TIMEOUT) {
+        rec.stop_reason = EKF_ITER_STOP_FAILED; // the covariance pass: x and P are those before the call
+        rec.passes_run -= 1;                    // ... and the passes before it are all that ran
+    } else if (!rc && e->sweep_retries != retries0) {
+        // the covariance pass timed out and was run again: its step was taken from the frozen state, take it again
+        launch_iter_step(e, e->iter_lin_sel, -1, e->d.iter_step + (rec.passes_run - 1), 0.0);
+    }
+    return rc;
+}
+
+int ekf_set_update_iterations(EkfEngine *e, int iterations, double tol)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (const char *why = iterations_refusal(e, iterations, tol)) {
+        e->err = std::string("ekf_set_update_iterations: ") + why;
+        return EKF_ERR_INVALID_ARG;
+    }
+    e->update_iterations = iterations;
+    e->update_iter_tol = tol;
+    return EKF_OK;
+}
+
+int ekf_get_update_iterations(const EkfEngine *e, int *iterations, double *tol)
+{
+    if (!e) return EKF_ERR_INVALID_ARG;
+    if (iterations) *iterations = e->update_iterations;
+    if (tol) *tol = e->update_iter_tol;
+    return EKF_OK;
+}
+
+int ekf_get_iteration_records(EkfEngine *e, EkfIterationRecord *out, int capacity, int *count)
+{
+    if (!e || !count || capacity < 0) return EKF_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    int rc = take_pending_error(e);
+    if (rc) return rc;
+    const int n = (int)e->iter_records.size();
+    *count = n;
+    if (!out || n == 0) return EKF_OK;
+    if (capacity < n) return EKF_ERR_CAPACITY;
+    for (int k = 0; k < n; ++k) {
+        out[k] = e->iter_records[k];
+        HIPCHK(hipMemcpy(out[k].step, e->d.iter_step + (size_t)k * EKF_MAX_UPDATE_ITERATIONS, sizeof(out[k].step), hipMemcpyDeviceToHost));
+        for (int i = std::max(0, out[k].passes_run); i < EKF_MAX_UPDATE_ITERATIONS; ++i) out[k].step[i] = 0.0;
+    }
+    return EKF_OK;
+}
+
+int ekf_get_linearisation_point(EkfEngine *e, double x13[13], double *feature_pos)
+{
+    if (!e || !x13) return EKF_ERR_INVALID_ARG;
+    // (the map's host side clears iter_lin_sel wherever the map is replaced or its layout changes; the count is checked all the same:
+    // feature_pos is sized by the caller from the map as it is now)
+    if (e->iter_lin_sel < 0 || !e->d.iter_lin || e->iter_lin_N != e->N) {
+        e->err = "ekf_get_linearisation_point: no iterated update has run on this map";
+        return EKF_ERR_INVALID_ARG;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const double *img = e->d.iter_lin + (size_t)e->iter_lin_sel * (ITER_X + 6 * (size_t)e->cap);
+    HIPCHK(hipMemcpy(x13, img + ST_X, 13 * sizeof(double), hipMemcpyDeviceToHost));
+    if (feature_pos && e->iter_lin_N > 0) HIPCHK(hipMemcpy(feature_pos, img + ITER_X, (size_t)e->iter_lin_N * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
 int ekf::finish_update(EkfEngine *e)
 {
     int rc = read_counts(e);
@@ -532,6 +730,8 @@ struct StepRun {
     bool lean = false;  // sharded: rows of H.P travel when consumed, not after every prediction
     int budget = 0;     // measurement budget K where it can bind, else 0
     bool normals = false, detect = false; // what the last read-back also carries: the patch-normal and the keypoint counters
+    int iterations = 1; // passes of both updates (ekf_set_update_iterations; > 1 on the host-count schedule only)
+    double iter_tol = 0.0;
     int np = 0, M = 0, ni = 0, no = 0, nr = 0; // predicted, matches, inliers, outliers, rescued
     EkfStepInfo li;
     int status;         // of the step: EKF_OK, or why an update was skipped (recover_failed_update)
@@ -567,7 +767,8 @@ static void take_ransac_result(StepRun &s)
 static int low_innovation_update(StepRun &s)
 {
     s.tm.mark();
-    const int rc = update_dev(s.e, s.ni, s.kind, /*stage*/ 1, s.lean, EarlyGather());
+    const int rc = s.iterations > 1 ? iterated_update_dev(s.e, s.ni, /*stage*/ 1, s.iterations, s.iter_tol, &s.status)
+                                    : update_dev(s.e, s.ni, s.kind, /*stage*/ 1, s.lean, EarlyGather());
     s.tm.mark();
     return rc;
 }
@@ -577,7 +778,8 @@ static int low_innovation_update(StepRun &s)
 static int high_innovation_update(StepRun &s, const EarlyGather &early)
 {
     s.li.n_rescued = s.nr;
-    const int rc = update_dev(s.e, s.nr, s.kind, /*stage*/ 2, s.lean, early);
+    const int rc = s.iterations > 1 ? iterated_update_dev(s.e, s.nr, /*stage*/ 2, s.iterations, s.iter_tol, &s.status)
+                                    : update_dev(s.e, s.nr, s.kind, /*stage*/ 2, s.lean, early);
     s.tm.mark();
     return rc;
 }
@@ -797,11 +999,12 @@ static int step_host_counts(StepRun &s, const StepInput &in, EkfStepInfo *info)
 }
 
 // Whether a step can leave its counts on the device: descriptor matcher on keypoints the host supplied, no image loaded, no kept
-// predictions, one GPU, no binding measurement budget.  Everything else needs a count on the host between two stages
+// predictions, one GPU, no binding measurement budget, plain (un-iterated) updates.  Everything else needs a count on the host between two stages
 // (step_host_counts says what for).
 static bool counts_stay_on_device(const EkfEngine *e, const StepInput &in, bool budget_active)
 {
-    return in.source == STEP_KEYPOINTS && !e->img.valid && !e->keep_step_preds && e->shard_world == 1 && !budget_active;
+    return in.source == STEP_KEYPOINTS && !e->img.valid && !e->keep_step_preds && e->shard_world == 1 && !budget_active &&
+           e->update_iterations == 1;
 }
 
 int ekf::run_step(EkfEngine *e, const StepInput &in, EkfStepInfo *info)
@@ -809,8 +1012,15 @@ int ekf::run_step(EkfEngine *e, const StepInput &in, EkfStepInfo *info)
     const bool budget_active = e->budget_K > 0 && e->budget_K < e->N; // measurement budget: with K >= N it cannot bind
     const int kind = e->fixed_map ? UPDATE_FIXED_MAP : UPDATE_COV;
     const int retries0 = e->sweep_retries;
+    e->iter_records.clear();
+    if (e->update_iterations > 1 && e->fixed_map) { // (the setters refuse the combination: nothing reaches this)
+        e->err = "iterated updates are not available while the fixed-map mode is on";
+        return EKF_ERR_INVALID_ARG;
+    }
     if (!counts_stay_on_device(e, in, budget_active)) {
         StepRun s(e, kind, EKF_OK, retries0);
+        s.iterations = e->update_iterations;
+        s.iter_tol = e->update_iter_tol;
         s.lean = e->shard_world > 1;
         s.budget = budget_active ? e->budget_K : 0;
         s.normals = in.source == STEP_NCC && e->pn_on;

@@ -42,6 +42,8 @@ struct UpdateCall {
     bool lean = false;           // sharded step: each rank gathered the rows of the matches it owns, an exchange completes them
     bool force_launches = false; // the launch-per-panel sweep whatever sweep_mode says (the retry of a timed-out persistent sweep)
     EarlyGather early;           // this update's merged gather / assembly launch may be enqueued already
+    const double *pred_uv = nullptr; // the prediction table nu = z - uv is formed from, 2 per feature; null: the engine's d.pred_uv.  A pass
+                                     // of the iterated update hands in the predictions shifted by H (x^ - x^i)
 };
 
 struct UpdateRouteIn {
@@ -241,11 +243,13 @@ inline bool early_gather_serves(const EarlyGather &g, const UpdateRoute &r)
 }
 
 // the retry of an update whose persistent sweep timed out: the same update on the launch-per-panel sweep, every launch its own
-// (no lean exchange -- a sharded update's sweep is never persistent -- and no early gather)
+// (no lean exchange -- a sharded update's sweep is never persistent -- and no early gather; the same prediction table: the retry
+// of a pass of the iterated update repeats THAT pass)
 inline UpdateCall retry_of(const UpdateCall &c)
 {
     UpdateCall r;
     r.matches = c.matches; r.M = c.M; r.kind = c.kind; r.stage = c.stage;
+    r.pred_uv = c.pred_uv;
     r.force_launches = true;
     return r;
 }

@@ -119,6 +119,23 @@ assert CONSISTENCY_DTYPE.itemsize == C.sizeof(EkfUpdateConsistency) == 24
 assert INNOVATION_DTYPE.itemsize == C.sizeof(EkfInnovation) == 48
 
 
+MAX_UPDATE_ITERATIONS = 8  # EKF_MAX_UPDATE_ITERATIONS
+ITER_STOP_COUNT, ITER_STOP_TOL, ITER_STOP_FEATURE_LEFT, ITER_STOP_FAILED = 0, 1, 2, 3  # EKF_ITER_STOP_*
+
+
+class EkfIterationRecord(C.Structure):
+    """One iterated update of the last call (ekf_get_iteration_records); 80 bytes, no padding."""
+
+    _fields_ = [("stage", C.c_int32), ("passes_run", C.c_int32), ("stop_reason", C.c_int32), ("_pad", C.c_int32),
+                ("step", C.c_double * MAX_UPDATE_ITERATIONS)]
+
+
+# step[i] = max_j |x_j^(i+1) - x_j^i| / sqrt(P_jj) over the prior's positive variances; 0 from passes_run on
+ITERATION_RECORD_DTYPE = np.dtype([("stage", "<i4"), ("passes_run", "<i4"), ("stop_reason", "<i4"), ("_pad", "<i4"),
+                                   ("step", "<f8", (MAX_UPDATE_ITERATIONS,))])
+assert ITERATION_RECORD_DTYPE.itemsize == C.sizeof(EkfIterationRecord) == 80
+
+
 class EkfMeasurementRank(C.Structure):
     """One predicted feature of a step with the measurement budget active (ekf_get_measurement_ranks); 32 bytes, no padding."""
 

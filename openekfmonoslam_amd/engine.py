@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
+from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, ITERATION_RECORD_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
                        MEASUREMENT_RANK_DTYPE, NCC_RIVAL_DTYPE,
                        PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapBlobInfo, EkfMapPoint, EkfParams, EkfStepInfo)
 
@@ -122,6 +122,11 @@ ABI = {
     "ekf_update_fixed_map": (_i, [_vp, _vp, _i]),
     "ekf_set_fixed_map": (_i, [_vp, _i]),
     "ekf_get_fixed_map": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "ekf_update_iterated": (_i, [_vp, _vp, _i, _i, C.c_double]),
+    "ekf_set_update_iterations": (_i, [_vp, _i, C.c_double]),
+    "ekf_get_update_iterations": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_double)]),
+    "ekf_get_iteration_records": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
+    "ekf_get_linearisation_point": (_i, [_vp, _vp, _vp]),
     "ekf_rescue": (_i, [_vp, _vp, _i, _vp]),
     "ekf_step": (_i, [_vp, _vp, _vp, _i, C.POINTER(EkfStepInfo)]),
     "ekf_frames_upload": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -695,6 +700,39 @@ class EkfEngine:
         on, k = _i(0), C.c_int64(0)
         self._chk(self.L.ekf_get_fixed_map(self.h, C.byref(on), C.byref(k)))
         return bool(on.value), int(k.value)
+
+    # ---- iterated update
+    def update_iterated(self, matches, iterations, tol=0.0, allow_errors=()):
+        """The covariance update in up to `iterations` passes (ekf_update_iterated): the measurement is linearised again at every
+        new estimate and the update solved again from the prior; iterations = 1 is update().  tol > 0: a pass that moved no state by
+        tol prior standard deviations makes the next pass the last.  Arguments and errors as update()."""
+        matches = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        return self._chk(self.L.ekf_update_iterated(self.h, _p(matches), len(matches), int(iterations), float(tol)), allow_errors)
+
+    def set_update_iterations(self, iterations, tol=0.0):
+        """both updates of every step run up to `iterations` passes (ekf_set_update_iterations); 1, the default: the plain updates.
+        Refused on a sharded engine and, above 1, while the fixed-map mode is on."""
+        self._chk(self.L.ekf_set_update_iterations(self.h, int(iterations), float(tol)))
+
+    def update_iterations(self):
+        """(iterations, tol) of the step functions"""
+        k, t = _i(0), C.c_double(0.0)
+        self._chk(self.L.ekf_get_update_iterations(self.h, C.byref(k), C.byref(t)))
+        return int(k.value), float(t.value)
+
+    def iteration_records(self):
+        """ITERATION_RECORD_DTYPE [0..2]: the iterated updates of the last update_iterated() or step (stage, passes_run, stop_reason,
+        step[8]); synchronises the stream"""
+        out = np.zeros(2, dtype=ITERATION_RECORD_DTYPE)
+        n = _i(0)
+        self._chk(self.L.ekf_get_iteration_records(self.h, _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def linearisation_point(self):
+        """(x13, feature_pos [N, 6]) at which the last iterated update linearised its covariance pass; synchronises the stream"""
+        x, fp = np.zeros(13), np.zeros((max(self.N, 1), 6))
+        self._chk(self.L.ekf_get_linearisation_point(self.h, _p(x), _p(fp)))
+        return x, fp[: self.N].copy()
 
     def rescue(self, outliers):
         outliers = np.ascontiguousarray(outliers, dtype=MATCH_DTYPE)

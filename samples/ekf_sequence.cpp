@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -34,6 +34,9 @@
 // --load-map FILE (likewise): the filter starts from such a file instead of initialising on the first frame, which is then stepped
 // on like the others (ImageEKF::loadMap); with --fixed-map-from 0 the run localises on the loaded map from its first step, with
 // the templates of the run that saved it.  The modes (--warp-templates, --patch-normals, ...) are not in the file: give them again.
+// --iterations K [--iteration-tol T] (likewise): both updates of every step are iterated EKF updates of up to K passes
+// (ImageEKF::setUpdateIterations); T > 0 ends an iteration once a pass moved no state by T standard deviations.  Under
+// the step line the passes and the last normalised step of each update are printed.
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -73,15 +76,19 @@ int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false, convertAll = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
-    int budget = 0, fixedFrom = -1;
+    int budget = 0, fixedFrom = -1, iterations = 1;
+    double iterationTol = 0.0;
     std::string fixesFile, timesFile, saveMapFile, loadMapFile;
     double timeUnit = 1.0;
     for (int i = 1; i < argc; ++i)
         if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes" ||
              std::string(argv[i]) == "--fixed-map-from" || std::string(argv[i]) == "--timestamps" || std::string(argv[i]) == "--time-unit" ||
-             std::string(argv[i]) == "--save-map" || std::string(argv[i]) == "--load-map") &&
+             std::string(argv[i]) == "--save-map" || std::string(argv[i]) == "--load-map" || std::string(argv[i]) == "--iterations" ||
+             std::string(argv[i]) == "--iteration-tol") &&
             i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
+            else if (std::string(argv[i]) == "--iterations") iterations = std::atoi(argv[i + 1]);
+            else if (std::string(argv[i]) == "--iteration-tol") iterationTol = std::atof(argv[i + 1]);
             else if (std::string(argv[i]) == "--timestamps") timesFile = argv[i + 1];
             else if (std::string(argv[i]) == "--save-map") saveMapFile = argv[i + 1];
             else if (std::string(argv[i]) == "--load-map") loadMapFile = argv[i + 1];
@@ -103,7 +110,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -120,7 +127,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty() && saveMapFile.empty() && loadMapFile.empty()) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty() && saveMapFile.empty() && loadMapFile.empty() && iterations == 1) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -148,6 +155,7 @@ int main(int argc, const char *argv[])
         extendedKalmanFilter.setConsistency(consistency);
         extendedKalmanFilter.setMeasurementBudget(budget);
         extendedKalmanFilter.setConvertAll(convertAll);
+        if (iterations != 1 || iterationTol != 0.0) extendedKalmanFilter.setUpdateIterations(iterations, iterationTol);
         std::vector<PositionFix> fixes;
         if (!fixesFile.empty()) readPositionFixes(fixesFile, fixes);
         std::FILE *csv = 0;
@@ -171,6 +179,13 @@ int main(int argc, const char *argv[])
                         info.n_predicted, info.n_matches, info.n_inliers, info.n_rescued, ekf_num_features(extendedKalmanFilter.engine()),
                         x[0], x[1], x[2]);
             if (extendedKalmanFilter.fixedMap()) std::printf("        fixed map: on\n");
+            if (iterations > 1) {
+                std::vector<EkfIterationRecord> recs;
+                extendedKalmanFilter.iterationRecords(recs);
+                for (size_t k = 0; k < recs.size(); ++k)
+                    std::printf("        iterated update %d: passes %d stop %d last step %.3g\n", recs[k].stage, recs[k].passes_run, recs[k].stop_reason,
+                                recs[k].passes_run > 0 ? recs[k].step[recs[k].passes_run - 1] : 0.0);
+            }
             if (!intervals.empty()) std::printf("        frame interval: dt = %g\n", extendedKalmanFilter.frameInterval());
             for (size_t k = 0; k < fixes.size(); ++k)
                 if (fixes[k].frame == extendedKalmanFilter.steps()) {

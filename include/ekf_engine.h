@@ -312,6 +312,40 @@ int ekf_update_fixed_map(EkfEngine *e, const EkfMatch *matches, int M);
 int ekf_set_fixed_map(EkfEngine *e, int on);
 int ekf_get_fixed_map(const EkfEngine *e, int *on, int64_t *updates);
 
+/* Relocalisation on the map (no counterpart in the reference).  Every matcher of a step searches inside the gate
+ * of the PREDICTED measurement, so a filter whose camera pose is far off -- tracking lost, or a map loaded for a session that starts
+ * somewhere else -- never recovers by stepping.  ekf_relocalise finds the pose from the map and one frame's keypoints alone:
+ *   1. every depth feature takes part, and every inverse-depth feature with rho > 0 and (max_rel_depth_sd == 0 or
+ *      sqrt(P[rho,rho]) / rho <= max_rel_depth_sd), as the world point ekf_get_map_points reports;
+ *   2. such a feature becomes a candidate when its smallest Hamming distance d1 over ALL keypoints (ties: the lower keypoint index)
+ *      is <= max_distance and (second_best_coef == 0 or d1 < second_best_coef * d2), d2 the smallest over the other keypoints;
+ *   3. hypothesis h = 0 .. hypotheses - 1 takes three candidates by splitmix64(seed + 3 h + k) mod C, solves P3P in closed form, scores
+ *      every solution against every candidate with the filter's own projection (inlier: predicted, and squared pixel error <=
+ *      inlier_px^2) and keeps its best: most inliers, then the smaller sum of squared inlier errors, then the lower solution index;
+ *   4. the best hypothesis by the same order (ties: the lowest h) is the result; found = its inliers >= min_inliers.
+ * With found and install != 0 the pose becomes the camera state (velocities as after ekf_reset), the camera's rows and columns of P
+ * become diag(sigma_position^2 x3, sigma_angle^2 / 4 x4, initLinearAccelSD^2 x3, initAngularAccelSD^2 x3) with zero cross terms, and
+ * the prediction tables are stale as after ekf_set_state: predict again.  The features, their block of P and every per-feature
+ * table are not written.  Without found, or with install == 0, nothing of the filter changes.  The pose is not refined: the filter's
+ * next step does that.
+ *
+ * ekf_relocalise takes n_kp keypoints with 32-byte descriptors from the host (n_kp = 0 is allowed); ekf_relocalise_image detects and
+ * describes them on the current image (ekf_image_upload; unmasked, threshold min_response, at most max_keypoints of them), and
+ * their count stays on the device.  Both synchronise the stream; a pending asynchronous error (ekf_set_async_errors) is reported
+ * first and nothing else is done, as ekf_update_external does.  Fewer than 3 candidates, or no valid hypothesis, is EKF_OK with
+ * found = 0.  EKF_ERR_INVALID_ARG with a message and nothing enqueued: a parameter outside the range stated in EkfRelocParams (NaN
+ * included), n_kp < 0 or > max_keypoints, a sharded engine, an engine that is not EKF_DESCRIPTOR_U8_HAMMING.  The first call
+ * allocates the scratch: about 120 bytes per feature of the engine's capacity and 88 bytes per hypothesis of the maximum.
+ *
+ * ekf_get_relocalise_candidates / _hypotheses: the candidate list (ascending feature order; inlier_mask, which may be NULL, marks
+ * the inliers of the best hypothesis) and the hypothesis records of the last call; *count is always set, out may be NULL to ask for
+ * it, and capacity < *count is EKF_ERR_CAPACITY (the convention of ekf_get_consistency). */
+int ekf_relocalise(EkfEngine *e, const EkfKeypoint *kps, const uint8_t *desc32, int n_kp, const EkfRelocParams *params,
+                   EkfRelocResult *out);
+int ekf_relocalise_image(EkfEngine *e, double min_response, const EkfRelocParams *params, EkfRelocResult *out);
+int ekf_get_relocalise_candidates(EkfEngine *e, EkfMatch *out, uint8_t *inlier_mask, int capacity, int *count);
+int ekf_get_relocalise_hypotheses(EkfEngine *e, EkfRelocHypothesis *out, int capacity, int *count);
+
 /* Iterated EKF update (opt-in: with 1 pass everything is the engine without it, bit for bit).  Gauss-Newton on
  * the update's own MAP cost: the camera measurement is linearised again at the new estimate and the update is solved again from
  * the PRIOR.  With x^, P the state and covariance before the update, z the matched pixels, R = pixelErrorX I and x^0 = x^, pass

@@ -178,6 +178,48 @@ typedef struct EkfMapBlobInfo {
     EkfCamera cam;         /* the camera the blob was saved under: reported, never compared                          */
 } EkfMapBlobInfo;          /* 40 + 104 = 144 bytes, no padding                                                       */
 
+/* Relocalisation on the map (ekf_relocalise): parameters, result and the record of one hypothesis.  No counterpart
+ * in the reference, which has no way back once tracking is lost. */
+#define EKF_RELOC_MAX_HYPOTHESES 4096
+
+typedef struct EkfRelocParams {
+    int32_t hypotheses;      /* 1..EKF_RELOC_MAX_HYPOTHESES                                                            */
+    int32_t min_inliers;     /* >= 4: inliers of the best hypothesis from which the pose counts as found               */
+    uint64_t seed;           /* the triple of hypothesis h comes from splitmix64(seed + 3 h + k), k = 0, 1, 2          */
+    double max_distance;     /* Hamming, >= 0: the best keypoint of a feature must be this close                       */
+    double second_best_coef; /* 0 = off, else (0,1]: ... and closer than coef times the second best                    */
+    double inlier_px;        /* > 0: reprojection error of an inlier, pixels                                           */
+    double max_rel_depth_sd; /* 0 = no filter, else an inverse-depth feature takes part when sd(rho) / rho is at most this */
+    double sigma_position;   /* > 0: standard deviation of the installed position, per axis                            */
+    double sigma_angle;      /* > 0, rad: ... and of the installed orientation (a quaternion component gets half of it) */
+    int32_t install;         /* != 0: a found pose replaces the camera state and the camera's rows and columns of P    */
+    int32_t _pad;
+} EkfRelocParams;            /* 72 bytes, no padding */
+
+typedef struct EkfRelocResult {
+    int32_t found;              /* 1: the best hypothesis has min_inliers inliers or more                               */
+    int32_t installed;          /* 1: found, and the pose was installed                                                 */
+    int32_t n_features_used;    /* features that took part                                                              */
+    int32_t n_candidates;       /* ... and those that found a keypoint                                                  */
+    int32_t n_hypotheses;
+    int32_t n_valid_hypotheses; /* hypotheses with one P3P solution or more                                             */
+    int32_t best_hypothesis;    /* -1: none was valid                                                                   */
+    int32_t n_inliers;
+    double rms_px;              /* sqrt(sum of squared inlier errors / n_inliers) of the best hypothesis                */
+    double r[3];                /* its pose (zeros when none was valid): camera position ...                            */
+    double q[4];                /* ... and orientation (w x y z, w >= 0), R(q) camera -> world                          */
+} EkfRelocResult;               /* 96 bytes, no padding */
+
+typedef struct EkfRelocHypothesis {
+    int32_t cand[3];     /* the three candidates (indices into the candidate list); -1 with fewer than 3 candidates     */
+    int32_t n_solutions; /* P3P solutions that passed every test, 0..4                                                  */
+    int32_t inliers;     /* of its best solution                                                                        */
+    int32_t _pad;
+    double sse;          /* sum of the squared inlier errors of that solution, added in candidate order                 */
+    double r[3];
+    double q[4];
+} EkfRelocHypothesis;    /* 88 bytes, no padding */
+
 /* Numeric constants of the reference, Core/EKFMath.h:37-41 (long double literals there; used as double). */
 #define EKF_EPSILON 2.22e-16
 #define EKF_DELTA 1.0e-12

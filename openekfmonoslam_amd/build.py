@@ -7,13 +7,13 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libekf_engine.so")
-SOURCES = ["engine.cpp", "map_host.cpp", "step.cpp", "kernels_predict.hip", "kernels_match.hip", "kernels_ransac.hip", "kernels_update.hip",
-           "kernels_pupdate.hip", "kernels_pexact.hip", "kernels_map.hip", "kernels_ncc.hip", "kernels_gemm.hip", "kernels_detect.hip",
-           "kernels_consistency.hip", "kernels_budget.hip", "kernels_external.hip", "kernels_fixedmap.hip", "kernels_mapblob.hip", "kernels_iterate.hip"]
+SOURCES = ["engine.cpp", "map_host.cpp", "step.cpp", "reloc_host.cpp", "kernels_reloc.hip", "kernels_predict.hip", "kernels_match.hip",
+           "kernels_ransac.hip", "kernels_update.hip", "kernels_pupdate.hip", "kernels_pexact.hip", "kernels_map.hip", "kernels_ncc.hip",
+           "kernels_gemm.hip", "kernels_detect.hip", "kernels_consistency.hip", "kernels_budget.hip", "kernels_external.hip", "kernels_fixedmap.hip", "kernels_mapblob.hip", "kernels_iterate.hip"]
 # the decision-making stages (projection, gates, dead-bands) are compiled without FMA contraction so their fp64
 # arithmetic rounds like the reference's scalar C++; the GEMM-shaped kernels keep contraction
 NO_CONTRACT = {"kernels_predict.hip", "kernels_match.hip", "kernels_ransac.hip", "kernels_ncc.hip", "kernels_detect.hip",
-               "kernels_budget.hip", "kernels_iterate.hip"}
+               "kernels_budget.hip", "kernels_iterate.hip", "kernels_reloc.hip"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-x", "hip"]
 FLAGS += os.environ.get("EKF_EXTRA_FLAGS", "").split()  # tuning experiments, e.g. -DPU_BK_VALUE=32

@@ -651,7 +651,8 @@ public:
              int imageMatcher = EKF_IMAGE_MATCHER_NCC, double keypointThreshold = 1e9)
         : e_(0), steps_(0), outputPath_(outputPath ? outputPath : ""), detectorThreshold_(detectorThreshold),
           keypoints_(imageMatcher == EKF_IMAGE_MATCHER_KEYPOINTS), patchNormals_(false), budget_(0), fixedMap_(false), convertAll_(false),
-          interval_(1.0), intervalSet_(false)
+          interval_(1.0), intervalSet_(false), keypointThreshold_(keypointThreshold), relocBelow_(0), relocFrames_(0), lostRun_(0),
+          relocParams_(), lastReloc_()
     {
         std::string err;
         if (!loadConfiguration(pathConfigFile, cam_, par_, run_, &err)) throw std::runtime_error("configuration: " + err);
@@ -698,8 +699,13 @@ public:
             if (intervalSet_) log_ << "Frame interval: dt = " << interval_ << std::endl;
         }
         EkfStepInfo info;
+        if (relocFrames_ > 0 && lostRun_ >= relocFrames_) { // setRelocalise: tracking counts as lost
+            relocalise(image, relocParams_);
+            lostRun_ = 0;
+        }
         if (out_.isOpened()) ekf_timing_reset(e_);
         chk(ekf_step_image(e_, image.data.data(), image.width, image.height, image.width * image.channels, image.channels, &info), "ekf_step_image");
+        if (relocFrames_ > 0) lostRun_ = info.n_inliers + info.n_rescued < relocBelow_ ? lostRun_ + 1 : 0;
         if (!outputPath_.empty()) writePredictionImage(image); // EKF.cpp:294-305
         if (budget_ > 0 && log_.is_open()) { // measurement budget: what the step's full prediction saw and what it handed on
             int predicted = 0, selected = 0;
@@ -895,6 +901,37 @@ public:
         logState();
         return info;
     }
+    // Relocalisation on the map (ekf_relocalise_image), keypoint matcher only: the camera pose from the map and the
+    // keypoints of `image` alone, wherever the filter believes the camera is.  With params.install a found pose replaces the camera
+    // state and the camera's rows and columns of P.  Throws with the NCC matcher and on an error code; not found is no error.
+    EkfRelocResult relocalise(const Image &image, const EkfRelocParams &params)
+    {
+        if (!keypoints_) throw std::runtime_error("relocalise: needs the keypoint matcher (EKF_IMAGE_MATCHER_KEYPOINTS)");
+        chk(ekf_image_upload(e_, image.data.data(), image.width, image.height, image.width * image.channels, image.channels), "ekf_image_upload");
+        EkfRelocResult out;
+        chk(ekf_relocalise_image(e_, keypointThreshold_, &params, &out), "ekf_relocalise_image");
+        if (log_.is_open()) {
+            if (out.found) log_ << "Relocalised: inliers=" << out.n_inliers << " candidates=" << out.n_candidates << " rms=" << out.rms_px << std::endl;
+            else log_ << "Relocalise failed" << std::endl;
+        }
+        lastReloc_ = out;
+        return out;
+    }
+    // Automatic recovery: after lostFrames consecutive steps with n_inliers + n_rescued < lostBelow the next step() relocalises on
+    // its image (params.install is set for it) before it steps, and log.txt gains "Relocalised: inliers=..." or "Relocalise
+    // failed" there.  lostFrames = 0 turns it off (the default).  Throws with the NCC matcher.
+    void setRelocalise(int lostBelow, int lostFrames, const EkfRelocParams &params)
+    {
+        if (!keypoints_) throw std::runtime_error("setRelocalise: needs the keypoint matcher (EKF_IMAGE_MATCHER_KEYPOINTS)");
+        if (lostBelow < 0 || lostFrames < 0) throw std::runtime_error("setRelocalise: negative argument");
+        relocBelow_ = lostBelow;
+        relocFrames_ = lostFrames;
+        relocParams_ = params;
+        relocParams_.install = 1;
+        lostRun_ = 0;
+    }
+    int lostRun() const { return lostRun_; } // consecutive steps below lostBelow so far
+    const EkfRelocResult &lastRelocalise() const { return lastReloc_; } // of the last relocalise(), called or automatic (zeros before)
     EkfEngine *engine() { return e_; }
     int steps() const { return steps_; }
     const EkfCamera &camera() const { return cam_; }
@@ -1001,6 +1038,11 @@ private:
     bool convertAll_;   // setConvertAll(on)
     double interval_;   // setFrameInterval(dt)
     bool intervalSet_;  // ... has been called: log.txt carries the interval of every step
+    double keypointThreshold_;       // the keypoint detector's threshold (the constructor's keypointThreshold)
+    int relocBelow_, relocFrames_;   // setRelocalise(lostBelow, lostFrames, ..); relocFrames_ = 0: off
+    int lostRun_;                    // consecutive steps below relocBelow_
+    EkfRelocParams relocParams_;
+    EkfRelocResult lastReloc_;
     EkfCamera cam_;
     EkfParams par_;
     RunParameters run_;

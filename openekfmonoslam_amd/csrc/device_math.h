@@ -114,6 +114,16 @@ __device__ __forceinline__ void dir_vec_t(const AngleTrig &t, double *m)
     m[2] = t.cp * t.ct;
 }
 
+// World point X of a feature's parameters y: (x y z) of a depth feature, (x0 y0 z0) + m(theta, phi) / rho of an inverse-depth one
+// (m = dir_vec of its angles, not read for the other kind).  The one copy of the formula (k_map_points, k_reloc_match).
+__host__ __device__ __forceinline__ void feature_world_point(const double *y, bool invd, const double *m, double *X)
+{
+    X[0] = y[0]; X[1] = y[1]; X[2] = y[2];
+    if (invd) {
+        X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
+    }
+}
+
 // Point of a feature in "camera axes" using rotation M (R' or inv(R)):
 // MeasurementPrediction.cpp:127-140 (inverse depth), :147-156 (depth)
 // (m: the direction vector of an inverse-depth feature, not read for the other kind)

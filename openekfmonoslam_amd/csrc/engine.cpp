@@ -1115,7 +1115,11 @@ static int ensure_kp_scratch(EkfEngine *e, int det_cap)
 
 // the step's keypoints: masked detection into d.kps (the first kcap in raster order), their descriptors into d.kdesc; the
 // count stays on the device (counts[CNT_KP_FOUND]) for k_match and k_brief -- no read-back
-int ekf::detect_step_keypoints(EkfEngine *e)
+int ekf::detect_step_keypoints(EkfEngine *e) { return detect_frame_keypoints(e, e->kp_min_response, true); }
+
+// the same two launches with the threshold and the mask as arguments (the step: its own threshold, masked; ekf_relocalise_image:
+// the caller's, unmasked)
+int ekf::detect_frame_keypoints(EkfEngine *e, double min_response, bool masked)
 {
     if (!e->img.valid) {
         e->err = "keypoint matcher: no image uploaded";
@@ -1123,7 +1127,7 @@ int ekf::detect_step_keypoints(EkfEngine *e)
     }
     int rc = ensure_kp_scratch(e, 0);
     if (rc) return rc;
-    launch_kp_detect(e, response_threshold(e->kp_min_response), true, e->d.kp_rowmask, e->d.kps, e->kcap, e->d.counts + CNT_KP_FOUND);
+    launch_kp_detect(e, response_threshold(min_response), masked, e->d.kp_rowmask, e->d.kps, e->kcap, e->d.counts + CNT_KP_FOUND);
     launch_brief(e, e->d.kps, nullptr, e->kcap, e->d.counts + CNT_KP_FOUND, e->d.kdesc);
     return check_async(e);
 }

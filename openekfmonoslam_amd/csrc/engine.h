@@ -128,6 +128,14 @@ struct MapBlobCtl {
     unsigned asym, pad;     // entries above the diagonal whose bits differ from their mirror's (k_map_asym)
 };
 
+// relocalisation (ekf_relocalise): the counts its kernels hand on, and the result its last kernel leaves
+constexpr int RELOC_MAX_HYP = EKF_RELOC_MAX_HYPOTHESES;
+struct RelocCtl {
+    int n_used, n_cand; // features that took part / candidates (k_reloc_compact)
+    int pad[2];
+    EkfRelocResult res; // k_reloc_select
+};
+
 // 1-point RANSAC: what a hypothesis needs of one match, gathered once per frame by the launch that writes the feature -> match index
 // (k_match_compact on the step path, k_match_index behind an arbitrary list) so that the hypotheses' workgroups read ONE contiguous
 // record per match instead of chasing match -> feature -> type / position / parameters through four tables each
@@ -278,6 +286,18 @@ struct DeviceArrays {
     double *iter_step = nullptr;  // ITER_SLOTS x EKF_MAX_UPDATE_ITERATIONS: the normalised step of every pass of an update of the last call
     int *iter_idx = nullptr;      // the matched features, update order: the sub-list of a pass's prediction
     MapBlobCtl *mb_ctl = nullptr; // map blob (ekf_save_map / ekf_load_map; allocated by the first of them)
+    // relocalisation (ekf_relocalise; one group of per-call scratch, allocated by the first call).  Not per-feature
+    // tables: nothing here outlives a call but the records the two getters read
+    RelocCtl *reloc_ctl = nullptr;
+    double *reloc_X = nullptr;     // 3 per feature: its world point
+    int *reloc_flag = nullptr;     // per feature: 0 takes no part, 1 takes part, 2 candidate
+    int *reloc_kp = nullptr;       // ... the candidate's keypoint
+    int *reloc_dist = nullptr;     // ... and its Hamming distance
+    EkfMatch *reloc_cand = nullptr; // the candidates, ascending feature order (cap records)
+    double *reloc_cX = nullptr;    // 3 per candidate: world point
+    double *reloc_cf = nullptr;    // 3 per candidate: bearing
+    uint8_t *reloc_mask = nullptr; // per candidate: inlier of the best hypothesis
+    EkfRelocHypothesis *reloc_hyp = nullptr; // RELOC_MAX_HYP records
     float *Pdiag = nullptr;     // sharded exact configuration: diagonal of P, n floats, completed by an exchange
     int8_t *Bstage = nullptr;   // ... and the digit planes of B in the exchange layout [column][plane][k / 16][16]
 };
@@ -655,6 +675,16 @@ constexpr int CA_TILE = 64, CA_CW = 132;
 // d.ca_rows (n_new rows), and the swap of the two buffers
 void launch_convert_all(EkfEngine *e, int count, int n_new);
 void launch_map_points(EkfEngine *e, EkfMapPoint *d_out); // read-only: state, map tables and P -> N records
+// relocalisation (kernels_reloc.hip): the four kernels of DESIGN.md 4.17 over the keypoints kps / kdesc, into the d.reloc_* scratch;
+// the last one writes the state and the camera strip of P when the pose is found and params->install is set
+struct RelocCall {
+    const EkfRelocParams *params = nullptr; // validated by the caller
+    const EkfKeypoint *kps = nullptr;
+    const uint8_t *kdesc = nullptr;
+    int n_kp = 0;
+    const int *d_nkp = nullptr; // not null: n_kp is the capacity, the number of keypoints is read on the device
+};
+void launch_relocalise(EkfEngine *e, const RelocCall &c);
 // map blob (kernels_mapblob.hip; layout: mapblob::P_TRIANGLE / P_FULL of map_blob.h).  _pack: the engine's P -> the flat section in
 // `staging`, its checksum -> *d_ctl (zeroed first).  _check: read-only pass over an uploaded section of n rows and elem_bytes per
 // element -> *d_ctl (zeroed first).  _unpack: such a section -> the engine's P (rows and columns below n; both triangles)

@@ -44,6 +44,7 @@ int exchange_rows(EkfEngine *e, int what, void *base, size_t row_bytes, const st
 int fixed_map_scratch(EkfEngine *e);
 int match_ncc_dev(EkfEngine *e, int *n_matches);
 int detect_step_keypoints(EkfEngine *e);
+int detect_frame_keypoints(EkfEngine *e, double min_response, bool masked);
 
 // ---- map_host.cpp: the optional per-feature tables (feature_tables.h), each group allocated whole and zeroed, or not at all.  Nothing
 // when the group exists; the caller has set the device and drained the stream.

@@ -412,12 +412,11 @@ k_map_points(const double *st, const double *feat_pos, const int *feat_type, con
         }
         if (lane == 0) {
             const double *x = st + ST_X, *y = feat_pos + 6 * (size_t)f;
-            double X[3] = {y[0], y[1], y[2]}, jw[18];
+            double X[3], jw[18], m[3] = {0.0, 0.0, 0.0};
+            if (invd) dir_vec(y[3], y[4], m);
+            feature_world_point(y, invd, m, X);
             if (invd) {
-                double m[3];
-                dir_vec(y[3], y[4], m);
                 inverse_depth_to_xyz_jacobian(y[3], y[4], y[5], m, jw);
-                X[0] += m[0] / y[5]; X[1] += m[1] / y[5]; X[2] += m[2] / y[5];
             } else {
                 for (int i = 0; i < 18; ++i) jw[i] = 0.0;
                 jw[0] = jw[7] = jw[14] = 1.0;

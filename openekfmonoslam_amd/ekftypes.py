@@ -171,6 +171,37 @@ class EkfMapBlobInfo(C.Structure):
 
 assert C.sizeof(EkfMapBlobInfo) == 144
 
+RELOC_MAX_HYPOTHESES = 4096  # EKF_RELOC_MAX_HYPOTHESES
+
+
+class EkfRelocParams(C.Structure):
+    """Parameters of ekf_relocalise; 72 bytes, no padding."""
+
+    _fields_ = [("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("seed", C.c_uint64), ("max_distance", C.c_double),
+                ("second_best_coef", C.c_double), ("inlier_px", C.c_double), ("max_rel_depth_sd", C.c_double),
+                ("sigma_position", C.c_double), ("sigma_angle", C.c_double), ("install", C.c_int32), ("_pad", C.c_int32)]
+
+
+class EkfRelocResult(C.Structure):
+    """What ekf_relocalise reports; 96 bytes, no padding."""
+
+    _fields_ = [("found", C.c_int32), ("installed", C.c_int32), ("n_features_used", C.c_int32), ("n_candidates", C.c_int32),
+                ("n_hypotheses", C.c_int32), ("n_valid_hypotheses", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("rms_px", C.c_double), ("r", C.c_double * 3), ("q", C.c_double * 4)]
+
+
+class EkfRelocHypothesis(C.Structure):
+    """One hypothesis of the last ekf_relocalise (ekf_get_relocalise_hypotheses); 88 bytes, no padding."""
+
+    _fields_ = [("cand", C.c_int32 * 3), ("n_solutions", C.c_int32), ("inliers", C.c_int32), ("_pad", C.c_int32),
+                ("sse", C.c_double), ("r", C.c_double * 3), ("q", C.c_double * 4)]
+
+
+RELOC_HYPOTHESIS_DTYPE = np.dtype([("cand", "<i4", (3,)), ("n_solutions", "<i4"), ("inliers", "<i4"), ("_pad", "<i4"), ("sse", "<f8"),
+                                   ("r", "<f8", (3,)), ("q", "<f8", (4,))])
+assert C.sizeof(EkfRelocParams) == 72 and C.sizeof(EkfRelocResult) == 96
+assert RELOC_HYPOTHESIS_DTYPE.itemsize == C.sizeof(EkfRelocHypothesis) == 88
+
 DESC_BYTES = 32
 FEATURE_DEPTH = 1
 FEATURE_INVERSE_DEPTH = 2

@@ -13,7 +13,8 @@ import numpy as np
 
 from .ekftypes import (CONSISTENCY_DTYPE, DESC_BYTES, INNOVATION_DTYPE, ITERATION_RECORD_DTYPE, KEYPOINT_DTYPE, MAP_POINT_DTYPE, MATCH_DTYPE,
                        MEASUREMENT_RANK_DTYPE, NCC_RIVAL_DTYPE,
-                       PREDICTION_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapBlobInfo, EkfMapPoint, EkfParams, EkfStepInfo)
+                       PREDICTION_DTYPE, RELOC_HYPOTHESIS_DTYPE, STATUS_NAMES, EkfCamera, EkfExternalUpdate, EkfMapBlobInfo, EkfMapPoint,
+                       EkfParams, EkfRelocParams, EkfRelocResult, EkfStepInfo)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libekf_engine.so")
@@ -122,6 +123,10 @@ ABI = {
     "ekf_update_fixed_map": (_i, [_vp, _vp, _i]),
     "ekf_set_fixed_map": (_i, [_vp, _i]),
     "ekf_get_fixed_map": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "ekf_relocalise": (_i, [_vp, _vp, _vp, _i, C.POINTER(EkfRelocParams), C.POINTER(EkfRelocResult)]),
+    "ekf_relocalise_image": (_i, [_vp, C.c_double, C.POINTER(EkfRelocParams), C.POINTER(EkfRelocResult)]),
+    "ekf_get_relocalise_candidates": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "ekf_get_relocalise_hypotheses": (_i, [_vp, _vp, _i, C.POINTER(_i)]),
     "ekf_update_iterated": (_i, [_vp, _vp, _i, _i, C.c_double]),
     "ekf_set_update_iterations": (_i, [_vp, _i, C.c_double]),
     "ekf_get_update_iterations": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_double)]),
@@ -458,6 +463,62 @@ class EkfEngine:
         out = EkfExternalUpdate()
         self._chk(self.L.ekf_fuse_feature_distance(self.h, int(i), int(j), float(d), float(sigma), float(gate_nis), C.byref(out)))
         return self._external_result(out)
+
+    # ---- relocalisation on the map
+    @staticmethod
+    def _reloc_params(hypotheses=256, min_inliers=6, seed=1, max_distance=48.0, second_best_coef=0.8, inlier_px=3.0,
+                      max_rel_depth_sd=0.0, sigma_position=0.05, sigma_angle=0.02, install=0):
+        p = EkfRelocParams()
+        p.hypotheses, p.min_inliers, p.seed = int(hypotheses), int(min_inliers), int(seed) & ((1 << 64) - 1)
+        p.max_distance, p.second_best_coef, p.inlier_px = float(max_distance), float(second_best_coef), float(inlier_px)
+        p.max_rel_depth_sd, p.sigma_position, p.sigma_angle = float(max_rel_depth_sd), float(sigma_position), float(sigma_angle)
+        p.install = int(install)
+        return p
+
+    @staticmethod
+    def _reloc_result(out):
+        d = {name: int(getattr(out, name)) for name, _ in EkfRelocResult._fields_[:8]}
+        d.update(rms_px=out.rms_px, r=np.array(out.r[:]), q=np.array(out.q[:]))
+        return d
+
+    def relocalise(self, kps, desc, allow_errors=(), **params):
+        """Finds the camera pose from the map and one frame's keypoints (KEYPOINT_DTYPE [K], uint8 [K, 32]) alone: global descriptor
+        match, P3P hypotheses, the filter's own projection as the score.  params: the fields of EkfRelocParams (hypotheses,
+        min_inliers, seed, max_distance, second_best_coef, inlier_px, max_rel_depth_sd, sigma_position, sigma_angle, install).
+        Returns the fields of EkfRelocResult as a dict; with install=1 a found pose replaces the camera state and the camera's rows
+        and columns of P.  With allow_errors, {"code": rc} for an allowed error code."""
+        kps = np.ascontiguousarray(kps, dtype=KEYPOINT_DTYPE)
+        desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(len(kps), -1) if len(kps) else np.zeros((0, DESC_BYTES), dtype=np.uint8)
+        if desc.shape[1] != DESC_BYTES:
+            raise ValueError("relocalise: 32-byte descriptors are needed")
+        p, out = self._reloc_params(**params), EkfRelocResult()
+        rc = self._chk(self.L.ekf_relocalise(self.h, _p(kps), _p(desc), len(kps), C.byref(p), C.byref(out)), allow_errors)
+        return {"code": rc} if rc else self._reloc_result(out)
+
+    def relocalise_image(self, min_response=1e9, allow_errors=(), **params):
+        """relocalise on the keypoints the detector and BRIEF-32 find in the current image (upload_image), unmasked; they and their
+        count stay on the device"""
+        p, out = self._reloc_params(**params), EkfRelocResult()
+        rc = self._chk(self.L.ekf_relocalise_image(self.h, float(min_response), C.byref(p), C.byref(out)), allow_errors)
+        return {"code": rc} if rc else self._reloc_result(out)
+
+    def relocalise_candidates(self):
+        """(MATCH_DTYPE [C], uint8 [C]): the candidates of the last relocalise in ascending feature order, and which of them are
+        inliers of its best hypothesis"""
+        n = _i(0)
+        self._chk(self.L.ekf_get_relocalise_candidates(self.h, None, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
+        mask = np.zeros(max(n.value, 1), dtype=np.uint8)
+        self._chk(self.L.ekf_get_relocalise_candidates(self.h, _p(out), _p(mask), len(out), C.byref(n)))
+        return out[: n.value].copy(), mask[: n.value].copy()
+
+    def relocalise_hypotheses(self):
+        """RELOC_HYPOTHESIS_DTYPE [hypotheses of the last relocalise]: cand, n_solutions, inliers, sse, r, q"""
+        n = _i(0)
+        self._chk(self.L.ekf_get_relocalise_hypotheses(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=RELOC_HYPOTHESIS_DTYPE)
+        self._chk(self.L.ekf_get_relocalise_hypotheses(self.h, _p(out), len(out), C.byref(n)))
+        return out[: n.value].copy()
 
     # ---- filter consistency (DESIGN.md 4.11)
     def set_consistency(self, on=True):

@@ -1,5 +1,5 @@
 // ekf_sequence -- the reference's sample program (kalmanFilter/samples/EKF/main.cpp:45-160) on the MI355X engine:
-//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]]
+//     ekf_sequence config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]] [--relocalise LOST_BELOW,LOST_FRAMES (keypoint matcher; with --load-map: relocalises on the first frame)]
 // reads imgdir/%05d.png from `first` (default 0; the reference hard-codes 90..6550) until `last` or the first missing
 // file, initialises the filter on the first frame, steps on the rest and, when outdir is given, writes
 // outdir/output.yml, log.txt and the prediction images in the reference's layout and, after the last frame, outdir/map.ply:
@@ -37,6 +37,13 @@
 // --iterations K [--iteration-tol T] (likewise): both updates of every step are iterated EKF updates of up to K passes
 // (ImageEKF::setUpdateIterations); T > 0 ends an iteration once a pass moved no state by T standard deviations.  Under
 // the step line the passes and the last normalised step of each update are printed.
+// --relocalise LOST_BELOW,LOST_FRAMES (likewise): the run uses the keypoint matcher (detector + BRIEF-32, the detector threshold is
+// detector_threshold) and recovers from tracking loss: after LOST_FRAMES consecutive steps with fewer than LOST_BELOW inliers the next
+// step first relocalises on its image (ImageEKF::setRelocalise, DESIGN.md 4.17: global descriptor match + P3P RANSAC on the map) and
+// "relocalised: ..." or "relocalise failed" is printed above its step line.  With --load-map AND --relocalise the first frame is
+// relocalised on once before it is stepped on, so a session may start anywhere in the mapped room.  --load-map alone does not
+// relocalise: the relocalisation matches BRIEF-32 descriptors, so it needs the keypoint matcher that --relocalise selects and a map
+// that was saved by a run with --relocalise (an NCC-template map has no descriptors to match).
 //
 //   g++ -std=c++11 -O2 samples/ekf_sequence.cpp -o ekf_sequence -Lopenekfmonoslam_amd -lekf_engine -lz
 //   (plus -Wl,-rpath,$PWD/openekfmonoslam_amd -Wl,-rpath,/opt/rocm/lib)
@@ -76,7 +83,7 @@ int main(int argc, const char *argv[])
 {
     bool warp = false, subpix = false, wide = false, normals = false, consistency = false, convertAll = false; // the flags are taken out of the argument list; the positional arguments keep their places
     double distinct = 0.0;
-    int budget = 0, fixedFrom = -1, iterations = 1;
+    int budget = 0, fixedFrom = -1, iterations = 1, lostBelow = -1, lostFrames = 0; // lostFrames > 0: --relocalise
     double iterationTol = 0.0;
     std::string fixesFile, timesFile, saveMapFile, loadMapFile;
     double timeUnit = 1.0;
@@ -84,11 +91,17 @@ int main(int argc, const char *argv[])
         if ((std::string(argv[i]) == "--ncc-distinct" || std::string(argv[i]) == "--budget" || std::string(argv[i]) == "--position-fixes" ||
              std::string(argv[i]) == "--fixed-map-from" || std::string(argv[i]) == "--timestamps" || std::string(argv[i]) == "--time-unit" ||
              std::string(argv[i]) == "--save-map" || std::string(argv[i]) == "--load-map" || std::string(argv[i]) == "--iterations" ||
-             std::string(argv[i]) == "--iteration-tol") &&
+             std::string(argv[i]) == "--iteration-tol" || std::string(argv[i]) == "--relocalise") &&
             i + 1 < argc) { // the flag and its value
             if (std::string(argv[i]) == "--budget") budget = std::atoi(argv[i + 1]);
             else if (std::string(argv[i]) == "--iterations") iterations = std::atoi(argv[i + 1]);
             else if (std::string(argv[i]) == "--iteration-tol") iterationTol = std::atof(argv[i + 1]);
+            else if (std::string(argv[i]) == "--relocalise") {
+                if (std::sscanf(argv[i + 1], "%d,%d", &lostBelow, &lostFrames) != 2 || lostBelow < 0 || lostFrames < 1) {
+                    std::fprintf(stderr, "%s: --relocalise wants LOST_BELOW,LOST_FRAMES (>= 0, >= 1)\n", argv[0]);
+                    return 2;
+                }
+            }
             else if (std::string(argv[i]) == "--timestamps") timesFile = argv[i + 1];
             else if (std::string(argv[i]) == "--save-map") saveMapFile = argv[i + 1];
             else if (std::string(argv[i]) == "--load-map") loadMapFile = argv[i + 1];
@@ -110,7 +123,7 @@ int main(int argc, const char *argv[])
             --i;
         }
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s config.yml imgdir/ [outdir/ [first [last [detector_threshold [f32]]]]] [--warp-templates] [--subpixel] [--wide-search] [--patch-normals] [--ncc-distinct COEF] [--consistency] [--budget K] [--position-fixes FILE] [--fixed-map-from FRAME] [--convert-all] [--timestamps FILE [--time-unit SECONDS]] [--save-map FILE] [--load-map FILE] [--iterations K [--iteration-tol T]] [--relocalise LOST_BELOW,LOST_FRAMES (keypoint matcher; with --load-map: relocalises on the first frame)]\n", argv[0]);
         return 2;
     }
     const std::string outputPath = argc > 3 ? argv[3] : "";
@@ -127,7 +140,7 @@ int main(int argc, const char *argv[])
             std::printf("No se puede iniciar Kalman Filter dado que no hay imagenes disponibles.\n");
             return 0;
         }
-        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty() && saveMapFile.empty() && loadMapFile.empty() && iterations == 1) {
+        if (precision == EKF_PRECISION_F64 && threshold == 1e9 && !warp && !subpix && !wide && distinct == 0.0 && !consistency && budget == 0 && fixesFile.empty() && fixedFrom < 0 && !convertAll && timesFile.empty() && saveMapFile.empty() && loadMapFile.empty() && iterations == 1 && lostFrames == 0) {
             // the reference's own three lines (samples/EKF/main.cpp:76-131): EKF(config, outputPath), init(image), step(image)
             EKF extendedKalmanFilter(argv[1], outputPath.c_str());
             extendedKalmanFilter.init(ekf_compat::matFromImage(image));
@@ -146,7 +159,13 @@ int main(int argc, const char *argv[])
             return 0;
         }
         // (a detector threshold, the fp32 configuration, the template warp, sub-pixel matches, the wide search, the distinctiveness test, the consistency records, a measurement budget, position fixes, a fixed map, the batch conversion, frame times or a map file asked for: the driver class with its extra arguments)
-        ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold);
+        ekf_compat::ImageEKF extendedKalmanFilter(argv[1], outputPath.c_str(), precision, threshold,
+                                                  lostFrames > 0 ? EKF_IMAGE_MATCHER_KEYPOINTS : EKF_IMAGE_MATCHER_NCC, threshold);
+        EkfRelocParams reloc = EkfRelocParams();
+        reloc.hypotheses = 256; reloc.min_inliers = 8; reloc.seed = 1;
+        reloc.max_distance = 48.0; reloc.second_best_coef = 0.8; reloc.inlier_px = 3.0; reloc.max_rel_depth_sd = 0.3;
+        reloc.sigma_position = 0.05; reloc.sigma_angle = 0.02; reloc.install = 1;
+        if (lostFrames > 0) extendedKalmanFilter.setRelocalise(lostBelow, lostFrames, reloc);
         extendedKalmanFilter.setTemplateWarp(warp);
         if (normals) extendedKalmanFilter.setPatchNormals(true);
         extendedKalmanFilter.setSubpixelMatches(subpix);
@@ -168,11 +187,22 @@ int main(int argc, const char *argv[])
         } else { // the first frame is a step like the others
             const EkfMapBlobInfo info = extendedKalmanFilter.loadMap(loadMapFile);
             std::printf("loaded map: %d features, %llu bytes\n", info.N, (unsigned long long)info.total_bytes);
+            if (lostFrames > 0) { // the session may start anywhere on the loaded map
+                const EkfRelocResult res = extendedKalmanFilter.relocalise(image, reloc);
+                if (res.found) std::printf("relocalised: inliers %d of %d candidates, rms %.3f px\n", res.n_inliers, res.n_candidates, res.rms_px);
+                else std::printf("relocalise failed: %d candidates, best %d inliers\n", res.n_candidates, res.n_inliers);
+            }
         }
         while (!image.empty()) {
             if (fixedFrom >= 0 && extendedKalmanFilter.steps() + 1 >= fixedFrom && !extendedKalmanFilter.fixedMap()) extendedKalmanFilter.setFixedMap(true);
             if (!intervals.empty()) extendedKalmanFilter.setFrameInterval(intervals[(size_t)extendedKalmanFilter.steps() + 1]);
+            const bool relocDue = lostFrames > 0 && extendedKalmanFilter.lostRun() >= lostFrames; // this step relocalises first
             const EkfStepInfo info = extendedKalmanFilter.step(image);
+            if (relocDue) {
+                const EkfRelocResult &res = extendedKalmanFilter.lastRelocalise();
+                if (res.found) std::printf("relocalised: inliers %d of %d candidates, rms %.3f px\n", res.n_inliers, res.n_candidates, res.rms_px);
+                else std::printf("relocalise failed: %d candidates, best %d inliers\n", res.n_candidates, res.n_inliers);
+            }
             double x[13];
             ekf_get_state(extendedKalmanFilter.engine(), x, 0, 0);
             std::printf("step %d: predicted %d matches %d li %d hi %d features %d  r = %.6f %.6f %.6f\n", extendedKalmanFilter.steps(),
